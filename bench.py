@@ -121,11 +121,29 @@ def set_mode(ctrl, mode, refs, paras, masks):
 
 
 def run_step(proc, ctrl, layers, mode, refs, paras, masks):
+    """one step: the six layer calls; returns their outputs"""
     set_mode(ctrl, mode, refs, paras, masks)
-    out = None
-    for l in layers:
-        out = proc(l["attn"], l["hidden_local"])
-    return out
+    return [proc(l["attn"], l["hidden_local"]) for l in layers]
+
+
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(outs, layers, path, seed=0):
+    """--dump-outputs: the outputs of one step as DIR/layer<i>_<L2|L3>.npy in float32, DUMP_BYTES in all at most.  An output
+    larger than its share is sampled by whole token rows, (rows, C): the row set comes from `seed` and the shape alone, so
+    every run with the same arguments writes the same rows."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(outs) - 4096  # (4096: room for the .npy header)
+    gen = torch.Generator().manual_seed(seed)
+    for i, (l, o) in enumerate(zip(layers, outs)):
+        if o.numel() * 4 > share:
+            rows = o.reshape(-1, o.shape[-1])
+            idx = torch.randperm(rows.shape[0], generator=gen)[: share // (4 * rows.shape[1])].sort().values
+            o = rows.index_select(0, idx.to(rows.device))
+        np.save(os.path.join(path, "layer%d_%s.npy" % (i, l["name"])), o.float().cpu().numpy())
 
 
 def cpu_baseline(layers, params, N, reps=3):
@@ -571,9 +589,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--reps", type=int, default=5,
+    ap.add_argument("--reps", type=int, default=1,
                     help="repetitions of the timed block of --steps steps (each bracketed by barrier + synchronize, max over "
                          "ranks); `value` is steps / the MEDIAN block time, min / max / every block in the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the six layer outputs of the last timed step to DIR/<name>.npy "
+                         "(float32, a seeded sample of token rows where the full outputs exceed 64 MB; rank 0's frames)")
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -643,9 +664,11 @@ def main():
         return float(t.item())
 
     def run_eager(k0, k):
+        outs = None
         with torch.no_grad():
             for s in range(k0, k0 + k):
-                run_step(proc, ctrl, layers, SCHEDULE[s % len(SCHEDULE)], refs, paras, masks)
+                outs = run_step(proc, ctrl, layers, SCHEDULE[s % len(SCHEDULE)], refs, paras, masks)
+        return outs
 
     # Setup, not a step: one untimed call sequence per attention mode, so that the per-batch index tables (row lists of
     # the cross-frame masks, trajectory-map checks -- constants of a batch of frames, built on first use) and every code
@@ -656,19 +679,22 @@ def main():
     torch.cuda.synchronize()
 
     run_eager(0, args.warmup)
-    # The timed block: EXACTLY --steps steps between barrier + synchronize on both sides, max over ranks -- repeated --reps
-    # times back to back.  The boxes of the pool differ by +- 5-8 % and a single 20-step sample cannot carry the headline
-    # (VERDICT r05): `value` = steps / the MEDIAN block; every block, min and max are in the line.  host_s: the time this
-    # rank's host needed to ISSUE the block (before the closing synchronize): N > 1 runs are host-bound when it nears dt.
+    # The timed block: EXACTLY --steps steps between barrier + synchronize on both sides, max over ranks.  --reps R > 1
+    # repeats it back to back (R x --steps timed steps): `value` = steps / the MEDIAN block; every block, min and max are in
+    # the line.  host_s: the time this rank's host needed to ISSUE the block (before the closing synchronize): N > 1 runs are
+    # host-bound when it nears dt.
     block_s, host_s = [], []
     for _ in range(max(args.reps, 1)):
         barrier()
         t0 = time.perf_counter()
-        run_eager(0, args.steps)
+        last_outs = run_eager(0, args.steps)
         t_issue = time.perf_counter() - t0
         barrier()
         block_s.append(max_over_ranks(time.perf_counter() - t0))
         host_s.append(t_issue)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_outs, layers, args.dump_outputs)
+    del last_outs
     dt = sorted(block_s)[len(block_s) // 2] if len(block_s) % 2 else 0.5 * sum(sorted(block_s)[len(block_s) // 2 - 1:len(block_s) // 2 + 1])
     host_ms_per_step = 1e3 * sorted(host_s)[len(host_s) // 2] / args.steps
     launch_mode = "eager"
@@ -817,8 +843,15 @@ def main():
                 import bench_full_step
 
                 fs = bench_full_step.measure(N=N, R=R, dev=device)
-                res["latent_delta"] = fs.pop("latent_delta", None)
+                ld = fs.pop("latent_delta", None)
+                res["latent_delta"] = ld and {k: ld[k] for k in ("fp16_latents", "fp32_latents", "steps", "modes", "init",
+                                                                 "pytorch_algorithms", "bar", "note")}
                 res["full_step"] = fs
+            # The line is read back whole: one of 36 KB was not, one of 16 KB was.  So the probes of the latent-delta study
+            # (gain, run-to-run, deterministic and unit-gain variants) and the per-kernel tables of the cfg3 and f3 legs stay
+            # out of it; tools/bench_full_step.py, bench_opt.py and bench_gmflow.py print the full records when run alone.
+            res["cfg3"].pop("kernel_avg_us", None)
+            res["f3_gmflow"].pop("attn_f32_launches", None)
             # the step of BASELINE.json's configs[2] (attention + feature optimisation + warp): what a denoising step costs
             # on the 15 of 20 steps the pipeline optimises features on (run_fresco.py:232)
             tot_ms = res["ms_per_step"] + res["cfg3"]["ms_per_step"]
@@ -875,7 +908,7 @@ def main():
     def emit():
         with out_lock:
             if rank == 0 and not printed[0]:
-                print(json.dumps(res), flush=True)
+                print(json.dumps(res, separators=(",", ":")), flush=True)
             printed[0] = True
 
     def bail():
@@ -1030,7 +1063,7 @@ def main():
         dog.cancel()
         emit()
     elif rank == 0:
-        print(json.dumps(res))
+        print(json.dumps(res, separators=(",", ":")))
     if world > 1:
         dist.destroy_process_group()
 

@@ -1,8 +1,6 @@
 """Import the UNMODIFIED reference modules from /root/reference on CPU (test infrastructure only).
 
-Used by ``make_golden.py`` (fixture generation, build container only) and by the optional
-``tests/test_oracle_vs_reference.py`` cross-check.  /root/reference does not exist on the GPU
-box, so nothing that runs there may import this module.
+Used by the ``make_*.py`` fixture generators only (build container); no test imports it.
 
 Recipe follows SURVEY.md Appendix B: the reference hard-imports cv2 and diffusers (absent here),
 so empty stub modules are registered first; only the names used at import time are provided

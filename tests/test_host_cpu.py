@@ -327,3 +327,26 @@ def test_attention_mask_forms_and_rejections():
         proc._masked_attention(q, torch.zeros(B, Lk + 1, 64), torch.zeros(B, Lk + 1, 64), 8, 0.3, b)  # Lk mismatch
     with pytest.raises(NotImplementedError):  # head dim 128: no larger kernel head dim to pad into
         proc._masked_attention(torch.zeros(B, 5, 1024), torch.zeros(B, Lk, 1024), torch.zeros(B, Lk, 1024), 8, 0.1, b)
+
+
+def test_patch_reference_rebinds_the_reference_names(monkeypatch):
+    """INTEGRATION.md recipe A: patch_reference(dh, pf, fu) rebinds every name the reference's diffusion_hacked, pipe_FRESCO
+    and flow_utils look up at call time to this package's, whatever fresco_amd exports at that moment
+    (stand-in modules here: the reference's own source is not part of this repository)."""
+    import types
+
+    import fresco_amd
+    from fresco_amd import opt as _opt, warp as _warp
+
+    rec_opt, rec_warp = (lambda *a, **k: None), (lambda *a, **k: None)
+    monkeypatch.setattr(_opt, "optimize_feature", rec_opt)
+    monkeypatch.setattr(_warp, "warp_tensor", rec_warp)
+    dh, pf, fu = (types.ModuleType(n) for n in ("src.diffusion_hacked", "src.pipe_FRESCO", "src.flow_utils"))
+    fresco_amd.patch_reference(dh, pf, fu)
+    assert dh.FRESCOAttnProcessor2_0 is fresco_amd.FRESCOAttnProcessor2_0
+    assert dh.AttentionControl is fresco_amd.AttentionControl
+    assert dh.optimize_feature is rec_opt and dh.warp_tensor is rec_warp and pf.warp_tensor is rec_warp
+    assert pf.step is fresco_amd.step and fu.get_mapping_ind is fresco_amd.get_mapping_ind
+    assert dh.get_mapping_ind is fresco_amd.get_mapping_ind
+    assert dh.flow_warp is fresco_amd.flow_warp and fu.flow_warp is fresco_amd.flow_warp
+    assert dh.adaptive_instance_normalization is fresco_amd.adaptive_instance_normalization
