@@ -46,20 +46,6 @@
 
 namespace fresco {
 
-// CUs of the current device (cached per device): the 256-row / 512-row workgroup choice below depends on it
-static int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus[dev] = n;
-    }
-    return cus[dev];
-}
-
-
 // ---------------------------------------------------------------------------------------------
 // pack: grid (nT, H, G), 256 threads.  Pack p of the image = K fragments of tile p || V^T fragments of tile p - 1: what
 // ONE loop step of attn_flash_kernel reads (PV(u) next to QK(u+1)); nT + 1 packs.
@@ -223,10 +209,7 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
             fv[buf][i] = *reinterpret_cast<const half8_t*>(wvp + st * 64 + i * 8);
         }
     };
-#ifndef KVP_ABL
-#define KVP_ABL 0
-#endif
-    if (!(KVP_ABL & 2)) fetch(0, 0);
+    fetch(0, 0);
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();  // rows[]
     {   // gather the 64 hidden rows into LDS: all of a thread's loads in flight, then its writes
@@ -237,7 +220,7 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
             const int row = c / CPR, dc = c % CPR;
             const int32_t r = rows[row];
             xv[i] = make_uint4(0, 0, 0, 0);
-            if (r >= 0 && !(KVP_ABL & 4)) xv[i] = *reinterpret_cast<const uint4*>(x + (int64_t)r * x_ld + dc * 8);
+            if (r >= 0) xv[i] = *reinterpret_cast<const uint4*>(x + (int64_t)r * x_ld + dc * 8);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -255,7 +238,7 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
 #pragma unroll
     for (int st = 0; st < NST; ++st) {
         const int buf = st & 1;
-        if (st + 1 < NST && !(KVP_ABL & 2)) fetch(st + 1, buf ^ 1);
+        if (st + 1 < NST) fetch(st + 1, buf ^ 1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < SK; ++i) {
@@ -269,7 +252,6 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    if ((KVP_ABL & 1) && ak[0][0] + av[1][3] != 12345.f) return;  // (ablation: no epilogue)
     // ---- K pieces: lane (key l31 of block b, hi), registers 4j .. 4j+3 = features 32 ft + 8 j + 4 hi + (0..3)
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -783,19 +765,18 @@ __global__ __launch_bounds__(512, 2) void attn_flash_kernel(const half_t* __rest
 }
 
 template <int D, int QB>
-static void launch_flash(const half_t* q, const char* img, half_t* out, int B, int H, int Lq, int M, int nT,
-                         int n_groups, float scale, float diag_bias, int64_t q_ld, const float* ktmax,
-                         hipStream_t st) {
+static int launch_flash(const half_t* q, const char* img, half_t* out, int B, int H, int Lq, int M, int nT,
+                        int n_groups, float scale, float diag_bias, int64_t q_ld, const float* ktmax,
+                        hipStream_t st) {
     using Cfg = AttnCfg<D>;
-    // (per device and cheap: set on every launch rather than cached in a process-global flag)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_flash_kernel<D, QB>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES);
+    if (int rc = allow_dyn_lds(&attn_flash_kernel<D, QB>, Cfg::LDS_BYTES)) return rc;
     const int nQblk = (Lq + 256 * QB - 1) / (256 * QB);
     const float log2e = 1.4426950408889634f;
     ProfScope ps(FRESCO_PROF_ATTN_FLASH, B * H, Lq, M, D, st);
     const int grid = H * nQblk * B;
     hipLaunchKernelGGL((attn_flash_kernel<D, QB>), dim3(grid), dim3(512), Cfg::LDS_BYTES, st, q, img,
                        ktmax, out, B, H, Lq, M, nT, B / n_groups, scale * log2e, diag_bias * log2e, q_ld);
+    return check_launch();
 }
 
 template <int D>
@@ -820,13 +801,11 @@ static int launch_attn(const half_t* q, const half_t* k, const half_t* v, const 
     if constexpr (D <= 48 && Cfg::MCOL) {
         const int grid2 = H * ((Lq + 511) / 512) * B;
         if (Lq > 256 && grid2 < device_cus())
-            launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
-        else
-            launch_flash<D, 2>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
+            return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
+        return launch_flash<D, 2>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
     } else {
-        launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
+        return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
     }
-    return check_launch();
 }
 
 static size_t attn_ws_bytes(int n_groups, int H, int M, int D) {
@@ -892,21 +871,18 @@ static int launch_kvproj_attn(const half_t* q, const half_t* x, int64_t x_ld, co
     {
         ProfScope ps(FRESCO_PROF_KV_PACK, n_groups, H, M, -D, st);  // (d < 0: the fused projection + pack launch)
         constexpr int lds = KvProjCfg<KIN, D>::LDS_BYTES;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&kvproj_pack_kernel<KIN, D>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (int rc = allow_dyn_lds(&kvproj_pack_kernel<KIN, D>, lds)) return rc;
         hipLaunchKernelGGL((kvproj_pack_kernel<KIN, D>), dim3(nT, H * D / 160, n_groups), dim3(320), lds, st, x, x_ld, x_rows,
                            Wk, Wv, img, ktmax, H, M, nT);
     }
     if constexpr (D <= 48 && Cfg::MCOL) {
         const int grid2 = H * ((Lq + 511) / 512) * B;
         if (Lq > 256 && grid2 < device_cus())
-            launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
-        else
-            launch_flash<D, 2>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
+            return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
+        return launch_flash<D, 2>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
     } else {
-        launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
+        return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
     }
-    return check_launch();
 }
 }  // namespace fresco
 

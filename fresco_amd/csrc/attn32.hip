@@ -16,7 +16,6 @@
 //
 // q (B, Lq, D), k (B, Lk, D), v (B, Lk, DV), out (B, Lq, DV), all fp32 row-major.  grid (ceil(Lq/128), B).
 #include "common.h"
-#include <stdlib.h>
 
 namespace fresco {
 
@@ -160,7 +159,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__
 //   * a wave owns 32 queries: Q fragments (hi, lo) resident in registers.
 // q (B, Lq, D), k (B, Lk, D), v (B, Lk, dv_real), out (B, Lq, dv_real) fp32.  grid (ceil(Lq/128), B), 256 threads.
 // ------------------------------------------------------------------------------------------------
-template <int D, int DV, int NPQ>  // NPQ = fp16 pieces of the Q / K operands: 2 (22 bits, 3 MFMAs) or 3 (33 bits, 6 MFMAs)
+template <int D, int DV, int NPQ>  // NPQ = fp16 pieces of the Q / K operands: 3 (33 bits, 6 MFMAs); 2 (22 bits) is not built
 __global__ __launch_bounds__(256, 2) void attn_f32s_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                             const float* __restrict__ v, float* __restrict__ out,
                                                             int Lq, int Lk, int dv_real, float scale_log2) {
@@ -603,14 +602,12 @@ static int launch_attn32p(const float* q, const float* k, const float* v, float*
     const int64_t wg8 = (int64_t)((Lq + 255) / 256) * B;
     if (can8 && wg8 >= 256) {
         if constexpr (can8) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32p_kernel<D, DV, 8>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            if (int rc = allow_dyn_lds(&attn_f32p_kernel<D, DV, 8>, lds)) return rc;
             hipLaunchKernelGGL((attn_f32p_kernel<D, DV, 8>), dim3((unsigned)wg8), dim3(512), lds, st, q, img, out, Lq, Lk, dv,
                                scale * 1.4426950408889634f, flag);
         }
     } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32p_kernel<D, DV, 4>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (int rc = allow_dyn_lds(&attn_f32p_kernel<D, DV, 4>, lds)) return rc;
         hipLaunchKernelGGL((attn_f32p_kernel<D, DV, 4>), dim3(((Lq + 127) / 128) * B), dim3(256), lds, st, q, img, out, Lq, Lk,
                            dv, scale * 1.4426950408889634f, flag);
     }
@@ -621,20 +618,8 @@ template <int D, int DV>
 static int launch_attn32(const float* q, const float* k, const float* v, float* out, int B, int Lq, int Lk, int dv,
                          float scale, hipStream_t st) {
     ProfScope ps(FRESCO_PROF_ATTN_F32, B, Lq, Lk, D, st);
-    // FRESCO_ATTN_F32=mfma32: the fp32-MFMA kernel (exact fp32 products; A/B measurements, and operands beyond fp16 range)
-    static const int use_f32_mfma = [] {
-        const char* e = getenv("FRESCO_ATTN_F32");
-        return (e && e[0] == 'm') ? 1 : ((e && e[0] == '2') ? 2 : 0);
-    }();
-    if (use_f32_mfma == 2)  // (22-bit logits: 3 MFMAs per product in both contractions; measurements)
-        hipLaunchKernelGGL((attn_f32s_kernel<D, DV, 2>), dim3((Lq + 127) / 128, B), dim3(256), 0, st, q, k, v, out, Lq, Lk,
-                           dv, scale * 1.4426950408889634f);
-    else if (use_f32_mfma)
-        hipLaunchKernelGGL((attn_f32_kernel<D, DV>), dim3((Lq + 127) / 128, B), dim3(256), 0, st, q, k, v, out, Lq, Lk,
-                           dv, scale * 1.4426950408889634f, (const int*)nullptr);
-    else
-        hipLaunchKernelGGL((attn_f32s_kernel<D, DV, 3>), dim3((Lq + 127) / 128, B), dim3(256), 0, st, q, k, v, out, Lq, Lk,
-                           dv, scale * 1.4426950408889634f);
+    hipLaunchKernelGGL((attn_f32s_kernel<D, DV, 3>), dim3((Lq + 127) / 128, B), dim3(256), 0, st, q, k, v, out, Lq, Lk, dv,
+                       scale * 1.4426950408889634f);
     return check_launch();
 }
 

@@ -24,6 +24,18 @@ static inline int check_launch() {
     return FRESCO_OK;
 }
 
+// Lets kernel `fn` take `bytes` of dynamic LDS on the current device: FRESCO_OK, or FRESCO_ELAUNCH with the HIP error
+// recorded.  The attribute is per device: the largest value set is remembered per (kernel, device), and the call is made
+// only when a launch needs more.  Thread-safe.
+int allow_dyn_lds(const void* fn, int bytes);
+template <typename... A>
+static inline int allow_dyn_lds(void (*fn)(A...), int bytes) {
+    return allow_dyn_lds(reinterpret_cast<const void*>(fn), bytes);
+}
+
+// CUs of the current device (cached per device; 256 if the query fails)
+int device_cus();
+
 // Opt-in kernel timing (fresco_prof_*): brackets selected launches with HIP events on the launch stream.
 struct ProfScope {
     bool on;

@@ -1,5 +1,9 @@
 #include "common.h"
 #include <string.h>
+#include <atomic>
+#include <map>
+#include <mutex>
+#include <utility>
 
 namespace fresco {
 static thread_local char g_last_error[256] = "";
@@ -7,6 +11,40 @@ void set_last_error(hipError_t e) {
     const char* s = hipGetErrorString(e);
     strncpy(g_last_error, s ? s : "unknown HIP error", sizeof(g_last_error) - 1);
     g_last_error[sizeof(g_last_error) - 1] = 0;
+}
+
+// ---- per-device launch settings ----------------------------------------------------------------------------------
+static std::mutex g_lds_mu;
+static std::map<std::pair<const void*, int>, int> g_lds;  // (kernel, device) -> dynamic LDS bytes allowed so far
+
+int allow_dyn_lds(const void* fn, int bytes) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) {
+        std::lock_guard<std::mutex> lock(g_lds_mu);
+        int& allowed = g_lds[{fn, dev}];
+        if (bytes <= allowed) return FRESCO_OK;
+        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e == hipSuccess) {
+            allowed = bytes;
+            return FRESCO_OK;
+        }
+    }
+    (void)hipGetLastError();  // (reported here, not again by the next check_launch)
+    set_last_error(e);
+    return FRESCO_ELAUNCH;
+}
+
+int device_cus() {
+    static std::atomic<int> cus[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    int n = cus[dev].load(std::memory_order_relaxed);
+    if (!n) {
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus[dev].store(n, std::memory_order_relaxed);
+    }
+    return n;
 }
 
 // ---- opt-in profiler: a fixed pool of event pairs, filled in launch order -------------------------

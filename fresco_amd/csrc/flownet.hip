@@ -901,8 +901,7 @@ extern "C" int fresco_fn_gemm(const void* a_hi, const void* a_lo, int64_t lda, c
 #define FN_LAUNCH(BN_, PATCH_)                                                                                                \
     do {                                                                                                                      \
         const int lds = (PATCH_) ? 2 * 2 * 24 * 1024 + FN_NS * 2 * (BN_) * 64 : FN_NS * (2 * FN_BM * 64 + 2 * (BN_) * 64);    \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fn_gemm_kernel<BN_, PATCH_>),                                \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);                                           \
+        if (int rc = allow_dyn_lds(&fn_gemm_kernel<BN_, PATCH_>, lds)) return rc;                                             \
         const int nb = (N + (BN_) - 1) / (BN_);                                                                               \
         hipLaunchKernelGGL((fn_gemm_kernel<BN_, PATCH_>), dim3(rb * nb), dim3(512), lds, st, ah, al, lda, cv, wh, wl, bias,   \
                            out, oh, ol, ldc, ldo, M, N, K, act, acc_scale, split_scale, sp, zeros, a_rows, out_rows,          \
@@ -989,7 +988,7 @@ extern "C" int fresco_fn_conv7_rgb(const float* x, const void* w_hi, const void*
     // fresco_fn_colstats_finish combines whole 256-row groups
     if (stats && (OW % 64 != 0 || ((int64_t)OH * OW) % 256 != 0)) return FRESCO_EUNSUPPORTED;
     const int lds = 2 * C7_ROWS * C7_PROW * 2 + 2 * 64 * C7_WROW;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fn_conv7_rgb_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (int rc = allow_dyn_lds(&fn_conv7_rgb_kernel, lds)) return rc;
     hipStream_t st = as_stream(stream);
     ProfScope ps(FRESCO_PROF_FN_GEMM, n_img * OH * OW, 64, 147, 7, st);
     hipLaunchKernelGGL(fn_conv7_rgb_kernel, dim3((OW + 255) / 256, (OH + 1) / 2, n_img), dim3(512), lds, st, x,

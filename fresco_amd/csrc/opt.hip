@@ -834,14 +834,8 @@ static void opt_closure(const OptWs& w, float* cs, const float* fwd_flow, const 
     const float kscale = 2.f / ((float)Bg * (float)C * (float)hw);
     const int S = chan_slices(hw, B, C);
     const dim3 egrid((hw + 255) / 256, (C + ECPT - 1) / ECPT, B);
-    // S V on fp16 MFMA (V = Vh + Vl) whenever rows are 16-byte aligned; FRESCO_OPT_SV=f32 forces the
-    // fp32-MFMA kernel (A/B measurements)
-    // (a pure function of the environment, initialised once, thread-safely)
-    static const int sv_mode = [] {
-        const char* e = getenv("FRESCO_OPT_SV");
-        return (e && e[0] == 'f' && e[1] == '3') ? 1 : 0;
-    }();
-    const bool f16_sv = (hw % 16 == 0) && sv_mode == 0;
+    // S V on fp16 MFMA (V = Vh + Vl) whenever rows are 16-byte aligned, else the fp32 kernel
+    const bool f16_sv = hw % 16 == 0;
     if (has_t && (parts & 2)) {
         dim3 sgrid((hw + 255) / 256, (C + OCPT - 1) / OCPT, chunk * L.n_pairs);
         ProfScope ps(FRESCO_PROF_OPT_TSIGN, B, C, hw, 0, st);
@@ -881,7 +875,7 @@ static void opt_closure(const OptWs& w, float* cs, const float* fwd_flow, const 
     }
     if (!(parts & 2)) return;
     ProfScope ps(FRESCO_PROF_OPT_ADAM, B, C, hw, 0, st);
-    const bool v_stored = !(has_s && (hw % 16 == 0) && sv_mode == 0 && C % 8 == 0);
+    const bool v_stored = !(has_s && f16_sv && C % 8 == 0);
     if (has_s) {
         if (v_stored)
             hipLaunchKernelGGL((chan_partial_kernel<1>), dim3((hw + 63) / 64, S, B), dim3(256), 0, st, w.vt, w.dvt,
@@ -1090,9 +1084,12 @@ static int opt_run_impl(SideStream* ctx, float* cs, const float* fwd_flow, const
         if (!split) {
             opt_fast_begin(ws, cs, chunk * N, C, hw, chunk * N, st);
             for (int it = 1; it <= iters; ++it)
-                opt_fast_closure(ws, cs, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, chunk, C, h, w, intra_weight,
-                                 has_t, 0, nullptr, nullptr, adam_args(it, lr, beta1, beta2, eps), st, L, chunk * N);
+                if (int rc = opt_fast_closure(ws, cs, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, chunk, C, h, w,
+                                              intra_weight, has_t, 0, nullptr, nullptr, adam_args(it, lr, beta1, beta2, eps),
+                                              st, L, chunk * N))
+                    return rc;
         } else {
+            int rc = FRESCO_OK;  // (on failure nothing more is issued, but the join below still runs)
             const OptWs w1 = ws_half(ws, 1, N, N, C, hw);
             float* cs1 = cs + (size_t)N * C * hw;
             const float* tg1 = target + (size_t)N * hw * hw;
@@ -1100,6 +1097,7 @@ static int opt_run_impl(SideStream* ctx, float* cs, const float* fwd_flow, const
             if (split == 4) {
                 // host issue order: front0(1) front1(1) | back0(1) front0(2) | back1(1) front1(2) | back0(2) front0(3) | ...
                 auto issue = [&](int half, int it, int parts) {
+                    if (rc) return;
                     FastSync y;
                     y.parts = parts;
                     const int par = it & 1;
@@ -1113,11 +1111,11 @@ static int opt_run_impl(SideStream* ctx, float* cs, const float* fwd_flow, const
                         y.wait_before_adam = half == 0 ? sd->gram_done[1][par] : (it < iters ? sd->gram_done[0][par ^ 1] : nullptr);
                     const AdamArgs a = adam_args(it, lr, beta1, beta2, eps);
                     if (half == 0)
-                        opt_fast_closure(ws, cs, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, 1, C, h, w, intra_weight, has_t,
-                                         0, nullptr, nullptr, a, st, L, chunk * N, &y);
+                        rc = opt_fast_closure(ws, cs, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, 1, C, h, w, intra_weight,
+                                              has_t, 0, nullptr, nullptr, a, st, L, chunk * N, &y);
                     else
-                        opt_fast_closure(w1, cs1, fwd_flow, bwd_flow, fwd_occ, bwd_occ, tg1, 1, C, h, w, intra_weight, has_t, 0,
-                                         nullptr, nullptr, a, sd->s, L, chunk * N, &y);
+                        rc = opt_fast_closure(w1, cs1, fwd_flow, bwd_flow, fwd_occ, bwd_occ, tg1, 1, C, h, w, intra_weight,
+                                              has_t, 0, nullptr, nullptr, a, sd->s, L, chunk * N, &y);
                 };
                 opt_fast_begin(w1, cs1, N, C, hw, chunk * N, sd->s);
                 issue(0, 1, 1);
@@ -1129,7 +1127,7 @@ static int opt_run_impl(SideStream* ctx, float* cs, const float* fwd_flow, const
                     if (it < iters) issue(1, it + 1, 1);
                 }
             } else
-            for (int it = 1; it <= iters; ++it) {
+            for (int it = 1; it <= iters && !rc; ++it) {
                 const AdamArgs a = adam_args(it, lr, beta1, beta2, eps);
                 const int par = it & 1;
                 FastSync y0, y1;
@@ -1140,12 +1138,13 @@ static int opt_run_impl(SideStream* ctx, float* cs, const float* fwd_flow, const
                     y1.record_after_sv = sd->sv_done[1][par];
                 }
                 if (it == 1 && split == 2) y0.record_after_gram = sd->mid;
-                opt_fast_closure(ws, cs, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, 1, C, h, w, intra_weight, has_t, 0,
-                                 nullptr, nullptr, a, st, L, chunk * N, &y0);
+                rc = opt_fast_closure(ws, cs, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, 1, C, h, w, intra_weight, has_t, 0,
+                                      nullptr, nullptr, a, st, L, chunk * N, &y0);
+                if (rc) break;
                 if (it == 1 && split == 2) (void)hipStreamWaitEvent(sd->s, sd->mid, 0);  // (recorded by the call above)
                 if (it == 1) opt_fast_begin(w1, cs1, N, C, hw, chunk * N, sd->s);
-                opt_fast_closure(w1, cs1, fwd_flow, bwd_flow, fwd_occ, bwd_occ, tg1, 1, C, h, w, intra_weight, has_t, 0,
-                                 nullptr, nullptr, a, sd->s, L, chunk * N, &y1);
+                rc = opt_fast_closure(w1, cs1, fwd_flow, bwd_flow, fwd_occ, bwd_occ, tg1, 1, C, h, w, intra_weight, has_t, 0,
+                                      nullptr, nullptr, a, sd->s, L, chunk * N, &y1);
             }
             // join: the caller's stream must not run past half 1.  If the event path fails, fall back to a host-side wait
             // for the side stream (correct, merely slower) and report the launch error
@@ -1153,6 +1152,7 @@ static int opt_run_impl(SideStream* ctx, float* cs, const float* fwd_flow, const
                 (void)hipStreamSynchronize(sd->s);
                 return FRESCO_ELAUNCH;
             }
+            if (rc) return rc;
         }
         return check_launch();
     }
@@ -1220,8 +1220,9 @@ extern "C" int fresco_opt_loss_grad(const float* cs, const float* fwd_flow, cons
     const TLayout L = {N, N, 1, nullptr, nullptr};
     if (opt_fast_ok(C, h, w, has_s)) {
         opt_fast_begin(ws, cs, chunk * N, C, h * w, chunk * N, st);
-        opt_fast_closure(ws, const_cast<float*>(cs), fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, chunk, C, h, w,
-                         intra_weight, has_t, 1, grad, loss, a, st, L, chunk * N);
+        if (int rc = opt_fast_closure(ws, const_cast<float*>(cs), fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, chunk, C, h, w,
+                                      intra_weight, has_t, 1, grad, loss, a, st, L, chunk * N))
+            return rc;
     } else
         opt_closure(ws, const_cast<float*>(cs), fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, chunk, N, C, h, w,
                     intra_weight, has_t, has_s, 1, grad, loss, a, st, L, chunk * N);
@@ -1288,8 +1289,10 @@ extern "C" int fresco_opt_sharded_step_part(float* cs, const float* halo_l, cons
         FastSync y;
         y.parts = part;
         y.halo_split = part == 3 ? 0 : 1;
-        opt_fast_closure(ws, cs, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, chunk, C, h, w, intra_weight, has_t, 0,
-                         nullptr, nullptr, adam_args(it, lr, beta1, beta2, eps), st, L, chunk * N_total, &y);
+        if (int rc = opt_fast_closure(ws, cs, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, chunk, C, h, w, intra_weight,
+                                      has_t, 0, nullptr, nullptr, adam_args(it, lr, beta1, beta2, eps), st, L, chunk * N_total,
+                                      &y))
+            return rc;
     } else
         opt_closure(ws, cs, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, chunk, n_loc, C, h, w, intra_weight, has_t,
                     has_s, 0, nullptr, nullptr, adam_args(it, lr, beta1, beta2, eps), st, L, chunk * N_total, part);

@@ -31,12 +31,8 @@ namespace fresco {
 constexpr int FAST_MAX_PART = 32;  // slices of the workspace's `part` / `dotp` arrays
 
 bool opt_fast_ok(int C, int h, int w, int has_s) {
-    static const int off = [] {
-        const char* e = getenv("FRESCO_OPT_GENERIC");
-        return (e && e[0] == '1') ? 1 : 0;
-    }();
     const int hw = h * w;
-    return !off && has_s && hw % 64 == 0 && C % 8 == 0 && 2 * ((C + 127) / 128) <= FAST_MAX_PART;
+    return has_s && hw % 64 == 0 && C % 8 == 0 && 2 * ((C + 127) / 128) <= FAST_MAX_PART;
 }
 
 // Work split of prep / adam: a thread owns K channel octets of one pixel, a 256-thread block 64 pixels x 4 such slices.
@@ -1358,9 +1354,6 @@ __global__ __launch_bounds__(256) void sv16_kernel(const half_t* __restrict__ vh
 // conflict-free (the padded S rows had 2-way conflicts: 25 % of the LDS cycles, profiles/r04_pmc_removed_gram16x_kernel.csv), and
 // three slots (72 KB) fit twice per CU: chunks arrive two steps ahead.
 // ------------------------------------------------------------------------------------------------
-#ifndef FRESCO_SV_SPLIT_READS
-#define FRESCO_SV_SPLIT_READS 1
-#endif
 constexpr int SB_TC = 128, SB_K = 32;
 constexpr int SB_VROW = SB_K * 2, SB_SROW = SB_K;
 constexpr int SB_NSLOT = 3;
@@ -1468,7 +1461,7 @@ __global__ __launch_bounds__(512, 4) void sv16b_kernel(const half_t* __restrict_
                 // of the LDS cycles in profiles/r05_pmc_opt_C640_h64.csv -- where two ds_read_b64 take 2 conflict-free cycles
                 // each (32-lane groups, 64 banks: the layout the swizzle was designed for).  The laundered offset keeps them apart.)
                 int sj = j * 32 * SB_SROW;
-                if (FRESCO_SV_SPLIT_READS && j > 0) asm volatile("" : "+v"(sj));
+                if (j > 0) asm volatile("" : "+v"(sj));
                 const u32x2 raw = *reinterpret_cast<const u32x2*>(base + rs + sj + us);
                 u32x4 w;
                 w[0] = __builtin_amdgcn_perm(0u, raw[0], 0x010c000cu);
@@ -1592,10 +1585,10 @@ void opt_fast_begin(const OptWs& w, const float* cs, int planes, int C, int hw, 
     hipLaunchKernelGGL(sumsq_partial_kernel, dim3(hw / 64, NPB, planes), dim3(256), 0, st, cs, w.part, C, hw, K, NPART);
 }
 
-void opt_fast_closure(const OptWs& w, float* cs, const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
-                      const float* bwd_occ, const float* target, int nck, int C, int h, int wd, float intra_weight,
-                      int has_t, int mode, float* gout, float* loss, AdamArgs a, hipStream_t st, const TLayout& Lin,
-                      int Bg, const FastSync* sync) {
+int opt_fast_closure(const OptWs& w, float* cs, const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
+                     const float* bwd_occ, const float* target, int nck, int C, int h, int wd, float intra_weight,
+                     int has_t, int mode, float* gout, float* loss, AdamArgs a, hipStream_t st, const TLayout& Lin,
+                     int Bg, const FastSync* sync) {
     const int hw = h * wd;
     TLayout L = Lin;
     if (!has_t) L = TLayout{Lin.n_loc, Lin.n_loc, 1, nullptr, nullptr};
@@ -1606,11 +1599,7 @@ void opt_fast_closure(const OptWs& w, float* cs, const float* fwd_flow, const fl
     const int NCT = (C + 127) / 128;  // channel tiles of the S V kernels
     const bool cm_tiled = sv_tiled_layout(hw, C);
     const bool small = hw <= 256 && C % 32 == 0;
-    // (round 6 experiment: FRESCO_GRAM_TILED_MIN_HW=256 sends the 16 x 16 planes to the DMA-staged 128 x 128 tile kernel instead
-    // of gram16s_kernel, whose row-strided 16-byte fragment loads sustain ~9 B/clk/CU; read per call: the tests switch it)
-    const char* mh_env = getenv("FRESCO_GRAM_TILED_MIN_HW");
-    const int min_hw = mh_env ? atoi(mh_env) : 512;
-    const bool big = gram_x_layout(hw, C, min_hw > 0 ? min_hw : 512);
+    const bool big = gram_x_layout(hw, C);
     const float kscale = 2.f / ((float)Bg * (float)C * (float)hw);
     const int parts = sync ? sync->parts : 3;
     const int halo_split = (sync && sync->halo_split && has_t && !L.circular) ? 1 : 0;
@@ -1658,14 +1647,7 @@ void opt_fast_closure(const OptWs& w, float* cs, const float* fwd_flow, const fl
             const bool zform = !(z_env && z_env[0] == '0') && gx_tiles_per_plane(hw) * Bg < 1024;
             if (zform) {
                 constexpr int ldsz = GZ_NS * GZ_SLOT;
-                static const bool oncez = [] {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16z_kernel<false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, ldsz);
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16z_kernel<true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, ldsz);
-                    return true;
-                }();
-                (void)oncez;
+                if (int rc = allow_dyn_lds(!gloss ? &gram16z_kernel<false> : &gram16z_kernel<true>, ldsz)) return rc;
                 const dim3 gridz(gz_tiles_per_plane(hw), 1, planes);
                 if (gloss)
                     hipLaunchKernelGGL(gram16z_kernel<true>, gridz, dim3(256), ldsz, st, w.vph, w.vpl, target, w.ssign, gloss, C,
@@ -1675,14 +1657,7 @@ void opt_fast_closure(const OptWs& w, float* cs, const float* fwd_flow, const fl
                                        hw, cm_tiled ? 1 : 0);
             } else {
                 constexpr int lds = GY_NS * GY_SLOT;
-                static const bool once = [] {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16y_kernel<false>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16y_kernel<true>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                    return true;
-                }();
-                (void)once;
+                if (int rc = allow_dyn_lds(!gloss ? &gram16y_kernel<false> : &gram16y_kernel<true>, lds)) return rc;
                 const dim3 grid(gx_tiles_per_plane(hw), 1, planes);
                 if (gloss)
                     hipLaunchKernelGGL(gram16y_kernel<true>, grid, dim3(512), lds, st, w.vph, w.vpl, target, w.ssign, gloss, C,
@@ -1708,42 +1683,22 @@ void opt_fast_closure(const OptWs& w, float* cs, const float* fwd_flow, const fl
                                    cm_tiled ? 1 : 0);
             } else if (coop && nt * nt * Bg < 512) {
                 constexpr int lds = GramCCfg<8>::LDS;
-                static const bool once = [] {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16c_kernel<8>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                    return true;
-                }();
-                (void)once;
+                if (int rc = allow_dyn_lds(&gram16c_kernel<8>, lds)) return rc;
                 hipLaunchKernelGGL(gram16c_kernel<8>, dim3(nt * nt, 1, planes), dim3(512), lds, st, w.vph, w.vpl, target,
                                    w.ssign, gloss, C, hw, cm_tiled ? 1 : 0);
             } else if (coop) {
                 constexpr int lds = GramCCfg<4>::LDS;
-                static const bool once = [] {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16c_kernel<4>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                    return true;
-                }();
-                (void)once;
+                if (int rc = allow_dyn_lds(&gram16c_kernel<4>, lds)) return rc;
                 hipLaunchKernelGGL(gram16c_kernel<4>, dim3(nt * nt, 1, planes), dim3(256), lds, st, w.vph, w.vpl, target,
                                    w.ssign, gloss, C, hw, cm_tiled ? 1 : 0);
             } else if (nt * nt * Bg < 512) {
                 constexpr int lds = 8 * 64 * GS_RS * 4;
-                static const bool once = [] {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16s_kernel<8>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                    return true;
-                }();
-                (void)once;
+                if (int rc = allow_dyn_lds(&gram16s_kernel<8>, lds)) return rc;
                 hipLaunchKernelGGL(gram16s_kernel<8>, dim3(nt * nt, 1, planes), dim3(512), lds, st, w.vph, w.vpl, target,
                                    w.ssign, gloss, C, hw, cm_tiled ? 1 : 0);
             } else {
                 constexpr int lds = 4 * 64 * GS_RS * 4;
-                static const bool once = [] {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gram16s_kernel<4>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-                    return true;
-                }();
-                (void)once;
+                if (int rc = allow_dyn_lds(&gram16s_kernel<4>, lds)) return rc;
                 hipLaunchKernelGGL(gram16s_kernel<4>, dim3(nt * nt, 1, planes), dim3(256), lds, st, w.vph, w.vpl, target,
                                    w.ssign, gloss, C, hw, cm_tiled ? 1 : 0);
             }
@@ -1757,14 +1712,6 @@ void opt_fast_closure(const OptWs& w, float* cs, const float* fwd_flow, const fl
         ProfScope ps(FRESCO_PROF_OPT_SV, planes, C, hw, 0, st);
         if (cm_tiled) {
             constexpr int lds128 = SB_NSLOT * (2 * 128 * SB_VROW + 256 * SB_SROW), lds64 = SB_NSLOT * (2 * 64 * SB_VROW + 256 * SB_SROW);
-            static const bool once = [] {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sv16b_kernel<128>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds128);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sv16b_kernel<64>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, lds64);
-                return true;
-            }();
-            (void)once;
             // whole tiles for the full rounds of the chip's 2 x 256 workgroup slots; the tiles of a last round that would
             // fill at most a quarter of the slots (or a launch smaller than one round) run as two half tiles each: measured
             // 116 -> 102 us at (1280, 32^2), 28 -> 21 us at (1280, 16^2); at (640, 64^2) -- 2.5 rounds -- the half-tile round
@@ -1776,19 +1723,23 @@ void opt_fast_closure(const OptWs& w, float* cs, const float* fwd_flow, const fl
             if (!tail_split || (rem > slots / 4 && tiles > slots)) rem = 0;
             if (tiles <= slots && tiles > slots / 2) rem = 0;  // (more than half a round of whole tiles: leave it)
             const int whole = tiles - rem;
-            if (whole > 0)
+            if (whole > 0) {
+                if (int rc = allow_dyn_lds(&sv16b_kernel<128>, lds128)) return rc;
                 hipLaunchKernelGGL(sv16b_kernel<128>, dim3(whole), dim3(512), lds128, st, w.vh, w.vl, w.ssign, w.dvt, w.dotp, C,
                                    hw, 2.f * coef, 0);
-            if (rem > 0)
+            }
+            if (rem > 0) {
+                if (int rc = allow_dyn_lds(&sv16b_kernel<64>, lds64)) return rc;
                 hipLaunchKernelGGL(sv16b_kernel<64>, dim3(2 * rem), dim3(512), lds64, st, w.vh, w.vl, w.ssign, w.dvt, w.dotp, C,
                                    hw, 2.f * coef, whole);
+            }
         } else {
             launch_sv16_plain(w.vh, w.vl, w.ssign, w.dvt, w.dotp, planes, C, hw, 2.f * coef, st);
         }
     }
     if (sync && sync->record_after_sv) (void)hipEventRecord(sync->record_after_sv, st);
     }  // parts & 1
-    if (!(parts & 2)) return;
+    if (!(parts & 2)) return FRESCO_OK;
     if (halo_split) launch_prep(2);  // (the halo frames have arrived: signs of the two boundary pairs)
     if (sync && sync->wait_before_adam) (void)hipStreamWaitEvent(st, sync->wait_before_adam, 0);
     {
@@ -1817,6 +1768,7 @@ void opt_fast_closure(const OptWs& w, float* cs, const float* fwd_flow, const fl
         else
             hipLaunchKernelGGL(opt_adam_kernel<false>, dim3(hw / 64, NPB, planes), dim3(256), 0, st, ka);
     }
+    return FRESCO_OK;
 }
 
 }  // namespace fresco

@@ -181,9 +181,7 @@ __host__ __device__ __forceinline__ bool sv_tiled_layout(int hw, int C) { return
 // (the condition under which gram16y_kernel runs: the pixel-major operand copies are then stored pre-tiled AND swizzled:
 // [plane][pixel tile of 128][channel chunk of 16][128 pixels][2 x 16-byte units], the two units of pixel row r swapped
 // when (r >> 3) & 1 -- the image a linear LDS-DMA copy needs for conflict-free ds_read_b128 on 32-byte rows)
-__host__ __device__ __forceinline__ bool gram_x_layout(int hw, int C, int min_hw = 512) {
-    return hw % 256 == 0 && hw >= min_hw && C % 32 == 0;
-}
+__host__ __device__ __forceinline__ bool gram_x_layout(int hw, int C) { return hw % 256 == 0 && hw >= 512 && C % 32 == 0; }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 struct AdamArgs {
@@ -207,7 +205,8 @@ bool opt_fast_ok(int C, int h, int w, int has_s);
 void opt_fast_begin(const OptWs& w, const float* cs, int planes, int C, int hw, int Bg, hipStream_t st);
 // one closure evaluation on `nck` CFG halves starting at the pointers given (w, cs, target already offset to the first
 // half); mode 0 = Adam step, mode 1 = write the gradient to gout.  Bg = global batch (normalises both loss terms);
-// sync (optional): events that order this pipeline against a second one on another stream
+// sync (optional): events that order this pipeline against a second one on another stream.  Returns FRESCO_OK, or
+// FRESCO_ELAUNCH (nothing more launched) when a kernel could not be given its dynamic LDS
 struct FastSync {
     hipEvent_t wait_before_gram = nullptr, record_after_gram = nullptr, record_after_sv = nullptr, wait_before_adam = nullptr;
     int parts = 3;  // 1: prep + gram + S V, 2: adam (a closure may be issued in two host calls)
@@ -215,10 +214,10 @@ struct FastSync {
     // that do (PrepArgs::phase 1 / 2) -- the neighbour exchange of the halo frames then runs under Gram + S V
     int halo_split = 0;
 };
-void opt_fast_closure(const OptWs& w, float* cs, const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
-                      const float* bwd_occ, const float* target, int nck, int C, int h, int wd, float intra_weight,
-                      int has_t, int mode, float* gout, float* loss, AdamArgs a, hipStream_t st, const TLayout& L,
-                      int Bg, const FastSync* sync = nullptr);
+int opt_fast_closure(const OptWs& w, float* cs, const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
+                     const float* bwd_occ, const float* target, int nck, int C, int h, int wd, float intra_weight,
+                     int has_t, int mode, float* gout, float* loss, AdamArgs a, hipStream_t st, const TLayout& L,
+                     int Bg, const FastSync* sync = nullptr);
 // the S V product on split-fp16 MFMAs for plain (un-tiled) operand layouts; dotp (optional): per-(128-channel tile)
 // partial sums of <V, dV> per pixel
 void launch_sv16_plain(const half_t* vh, const half_t* vl, const int8_t* ssign, float* dvt, float* dotp, int B, int C,

@@ -31,7 +31,7 @@
 // coalesced form (consecutive lanes = consecutive 16 bytes of a row) through a per-wave LDS region, all K chunks' loads in
 // flight before the first goes through LDS, the weight slabs' DMA prologue requested in front of them.  Same fragments, same
 // MFMA order: bit-identical outputs.  (16384, 640): single projection 29.9 -> 25.2 us, q,k,v 54.6 -> 49.8; (65536, 320),
-// HBM-bound in that phase: 59.0 -> 58.8 (profiles/r06_ab_proj_x_staging.txt; -DFRESCO_PROJ_X_DIRECT=1 builds the old form).
+// HBM-bound in that phase: 59.0 -> 58.8 (profiles/r06_ab_proj_x_staging.txt; the old form is in the commit history).
 #include "common.h"
 
 namespace fresco {
@@ -80,7 +80,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
-    const int row = blockIdx.x * (NWV * 32) + wave * 32 + l31;
     const int ft0 = blockIdx.y * tiles_per_split;
     const int ft1 = min(nF, ft0 + tiles_per_split);
     if (ft0 >= ft1) return;
@@ -153,21 +152,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
     if (AHEAD > 1 && nsteps > 1) stage(1, 1);
     if (AHEAD > 2 && nsteps > 2) stage(2, 2);
     // ---- x fragments (after the first weight slabs have been requested: their DMA runs under the x loads)
-#ifndef FRESCO_PROJ_X_DIRECT
-#define FRESCO_PROJ_X_DIRECT 0
-#endif
-    if (FRESCO_PROJ_X_DIRECT) {
-        // (rounds 1-5, kept as an A/B build switch: every lane loads its own row's fragments straight from global memory --
-        // 64 rows one row stride apart per instruction; the texture-address path serves that at ~9 B/clk/CU: 7.6 us for the
-        // 164 KB of a workgroup at K = 320, 15 us for the 328 KB at K = 640)
-        const int rr = row < M ? row : M - 1;
-        const half_t* xp = x + (int64_t)(x_rows ? x_rows[rr] : rr) * x_ld + hi * (Cfg::KC / 2);
-#pragma unroll
-        for (int kc = 0; kc < Cfg::NKC; ++kc)
-#pragma unroll
-            for (int ks = 0; ks < Cfg::KS; ++ks)
-                xf[kc * Cfg::KS + ks] = *reinterpret_cast<const half8_t*>(xp + kc * Cfg::KC + ks * 8);
-    } else {
+    {
         // (x_rows: problem row m reads input row x_rows[m] -- the gathered form, e.g. K / V of the selected tokens only)
         // Piece q = j * 64 + lane of the wave's 32 x (KC / 8) pieces of a K chunk: row q / (KC / 8), piece q % (KC / 8) --
         // consecutive lanes read consecutive 16 bytes of a row (KC * 2 contiguous bytes per row: ~10 lines per instruction
@@ -326,11 +311,9 @@ static int launch_linear(const half_t* x, int64_t x_ld, const int32_t* x_rows, c
                          half_t* out0, half_t* out1, half_t* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M,
                          int N, hipStream_t st) {
     using Cfg = ProjCfg<K, NWV>;
-    // (per device and cheap: set on every launch rather than cached in a process-global flag)
     const int lds_bytes = Cfg::BIAS_OFF + nw * N * 2;
     if (lds_bytes > 160 * 1024) return FRESCO_EUNSUPPORTED;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_kernel<K, NWV>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if (int rc = allow_dyn_lds(&linear_kernel<K, NWV>, lds_bytes)) return rc;
     const int nF = nw * N / Cfg::TF;
     const int row_blocks = (M + NWV * 32 - 1) / (NWV * 32);
     // enough workgroups for two rounds of the 256 CUs; every extra split re-reads x once

@@ -428,9 +428,9 @@ static int launch_temporal_mfma(const half_t* q, const half_t* k, const half_t* 
     const int RS = 16 * ((C / hsplit / 8) | 1);
     const size_t lds = (size_t)PB * N * (3 * RS + 4 + N);
     if (lds > 160 * 1024) return FRESCO_EUNSUPPORTED;
-    if (lds > 65536)  // (the attribute is per device, and setting it is cheap: no process-global flag)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_mfma_kernel<D, KT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds > 65536) {
+        if (int rc = allow_dyn_lds(&temporal_mfma_kernel<D, KT>, (int)lds)) return rc;
+    }
     dim3 grid((HW + PB - 1) / PB, chunk, hsplit);
     ProfScope ps(FRESCO_PROF_TEMPORAL, chunk * N, HW, H, D, st);
     hipLaunchKernelGGL((temporal_mfma_kernel<D, KT>), grid, dim3(NT), lds, st, q, k, v, fwd_map, mask, out, N, HW, H,
@@ -455,8 +455,7 @@ static int launch_temporal(const half_t* q, const half_t* k, const half_t* v, co
     const int want = (256 + N * H - 1) / (N * H);  // enough work items for every thread
     if (PB > want) PB = want;
     const size_t lds = (size_t)PB * per_traj;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal_attn_kernel<D>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds > 65536 ? lds : 65536));
+    if (int rc = allow_dyn_lds(&temporal_attn_kernel<D>, (int)(lds > 65536 ? lds : 65536))) return rc;
     dim3 grid((HW + PB - 1) / PB, chunk);
     ProfScope ps(FRESCO_PROF_TEMPORAL, chunk * N, HW, H, D, st);
     hipLaunchKernelGGL((temporal_attn_kernel<D>), grid, dim3(256), lds, st, q, k, v, fwd_map, mask, out, N, HW, H, PB,

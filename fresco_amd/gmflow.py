@@ -351,20 +351,15 @@ def _layer_native(layer, wts, src, src_s, tgt_s, grows, tgt_table=None):
     lin = lambda p: wts.get(p.weight, "lin")
     # q | k | v of one source (self-attention) as ONE product with three output matrices, k | v of the other image's tokens
     # (cross-attention) as one with two: the operand rows are read once instead of three / two times (round 6)
-    fuse = os.environ.get("FRESCO_GMFLOW_FUSE_QKV", "1") != "0"  # (A/B switch)
-    if fuse and src_s is tgt_s and tgt_table is None:
+    if src_s is tgt_s and tgt_table is None:
         qkv, _ = ops.fn_gemm(src_s, wts.get_stacked((layer.q_proj.weight, layer.k_proj.weight, layer.v_proj.weight)), 3 * C, C,
                              a_rows=table, out_blocks=3)
         q, k, v = qkv[0], qkv[1], qkv[2]
-    elif fuse:
+    else:
         q, _ = ops.fn_gemm(src_s, lin(layer.q_proj), C, C, a_rows=table)
         kv, _ = ops.fn_gemm(tgt_s, wts.get_stacked((layer.k_proj.weight, layer.v_proj.weight)), 2 * C, C, a_rows=ktable,
                             out_blocks=2)
         k, v = kv[0], kv[1]
-    else:
-        q, _ = ops.fn_gemm(src_s, lin(layer.q_proj), C, C, a_rows=table)
-        k, _ = ops.fn_gemm(tgt_s, lin(layer.k_proj), C, C, a_rows=ktable)
-        v, _ = ops.fn_gemm(tgt_s, lin(layer.v_proj), C, C, a_rows=ktable)
     scale = 1.0 / math.sqrt(C)
     outs_ = []
     for off, G, n in spans:

@@ -8,8 +8,13 @@
  *   - never allocates: scratch memory is passed in by the caller, sized by the matching
  *     *_workspace_bytes() query (host-only, no GPU needed);
  *   - asynchronous on `stream` (a hipStream_t passed as void*; NULL = the null stream);
- *   - no global state (except the opt-in fresco_prof_* timing log, and FRESCO_OPT_SV read once from the
- *     environment): concurrent calls on different streams / devices with disjoint buffers are safe.
+ *   - no global state (except the opt-in fresco_prof_* timing log and per-device caches of launch settings):
+ *     concurrent calls on different streams / devices with disjoint buffers are safe.
+ *
+ * Environment switches, for tests and measurement only:
+ *   read per call:          FRESCO_GRAM_Z, FRESCO_GRAM_COOP, FRESCO_GRAM_SPLIT_WG, FRESCO_OPT_SPLIT, FRESCO_OPT_SVTAIL;
+ *   read once per process:  FRESCO_FN_CONV_PATCH, FRESCO_FN_XCD_MAP;
+ *   read by fresco_amd:     FRESCO_GMFLOW_LIBRARY_OPS, FRESCO_HIP_LIB (the library file to load).
  *
  * Reference interface each entry point replaces (paths relative to the FRESCO tree):
  *   src/diffusion_hacked.py  = DH,  src/flow_utils.py = FU,  src/utils.py = UT,

@@ -351,3 +351,29 @@ def test_opt_context_owns_the_side_stream():
     [t.start() for t in ts]
     [t.join() for t in ts]
     assert torch.equal(outs[0], a) and torch.equal(outs[1], a)
+
+
+def test_second_device_runs_the_same_pipeline():
+    """The dynamic-LDS limit of a kernel is a per-device setting: a process that has run the optimisation on one GPU must
+    run it on another with the same results.  Between them the three shapes launch gram16c<8> (16 x 16), gram16z (32 x 32),
+    gram16y (64 x 64) and both sv16b tile shapes."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    import fresco_amd.ops as ops
+    from fresco_amd.warp import _prep_flow_occ
+    N = 8
+    for C, h in [(1280, 16), (1280, 32), (640, 64)]:
+        g = synth.gen(C + h)
+        x = torch.randn(2 * N, C, h, h, generator=g)
+        flows, occs = synth.make_flows(N, 4 * h, g)
+        # inputs made once on cuda:0 and copied: only the optimisation itself runs on both devices
+        prep = _prep_flow_occ(h, [f.to("cuda:0") for f in flows], [o.to("cuda:0") for o in occs], with_dilate=False)
+        target = O.gram_target(torch.randn(2 * N, C, h, h, generator=g).to("cuda:0"))
+        outs = []
+        for dev in ("cuda:0", "cuda:1"):
+            with torch.cuda.device(dev):
+                cs = x.to(dev)
+                ops.opt_run(cs, tuple(t.to(dev) for t in prep), target.to(dev), 100.0, 2, 2)
+                outs.append(cs.cpu())
+        assert torch.equal(outs[0], outs[1]), (C, h, int((outs[0] != outs[1]).sum()))
+        del prep, target
