@@ -85,6 +85,13 @@ SIGNATURES = {
     "fresco_ddpm_x0": (_i, [_vp] * 5 + [_i64, _f, _f, _f, _i, _vp]),
     "fresco_ddpm_prev": (_i, [_vp] * 4 + [_i64, _i64, _f, _f, _f, _i, _vp]),
     "fresco_gram_target": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "fresco_ebsynth_max_levels": (_i, [_i] * 5),
+    "fresco_ebsynth_workspace_bytes": (_sz, [_i] * 9),
+    "fresco_ebsynth_run": (_i, [_vp] * 6 + [_i] * 6 + [_f, _i, _i, _i, _vp, _vp, _vp, _i, _c.c_uint64, _vp, _vp, _vp,
+                                                     _vp, _sz, _vp]),
+    "fresco_ebsynth_stage_workspace_bytes": (_sz, [_i] * 4),
+    "fresco_ebsynth_resample": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
+    "fresco_ebsynth_stop_mask": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

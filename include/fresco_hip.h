@@ -69,6 +69,7 @@ const char* fresco_last_error(void);
 #define FRESCO_PROF_LINEAR 10 /* dims = {M, N, K, nw} */
 #define FRESCO_PROF_ATTN_F32 11 /* dims = {B, Lq, Lk, D} */
 #define FRESCO_PROF_FN_GEMM 12  /* dims = {M, N, K, kernel height (0: linear layer)} */
+#define FRESCO_PROF_EBSYNTH_LEVEL 13 /* one pyramid level of fresco_ebsynth_run: dims = {level, tw, th, patch} */
 int fresco_prof_enable(int capacity);
 int fresco_prof_disable(void);
 int fresco_prof_read(int max_records, int* tags, int* dims, float* ms);
@@ -482,6 +483,48 @@ int fresco_ddpm_x0(const void* xt, const void* eps_uncond, const void* eps_text,
                    void* stream);
 int fresco_ddpm_prev(const void* x0, const void* xt, const void* noise, void* out, int64_t n,
                      int64_t noise_period, float c_x0, float c_xt, float sigma, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (g)  Ebsynth -- guided patch-based synthesis that propagates a stylised keyframe to another frame (video_blend.py's
+ * second stage; the reference's ebsynthRun, src/ebsynth/deps/ebsynth/include/ebsynth.h).  Coarse to fine over an image
+ * pyramid: per level, PatchMatch (propagation at jumps 4, 2, 1 + random search) of the nearest-neighbour field (NNF,
+ * target pixel -> centre of its source patch) under the weighted SSD of style + guide channels plus a uniformity term,
+ * then a patch vote; a stop mask freezes pixels whose style stopped changing.  DESIGN.md section 9.
+ *   images  : uint8, channel-interleaved, row-major: src_style (src_h, src_w, n_style), src_guide (src_h, src_w,
+ *             n_guide), tgt_guide / tgt_modulation (tgt_h, tgt_w, n_guide); tgt_modulation may be NULL;
+ *             guide error per channel = guide_weights[c] * (mod/255) * diff^2
+ *   weights : HOST arrays of n_style / n_guide floats
+ *   levels  : -1 = fresco_ebsynth_max_levels(); per-level HOST arrays (coarse first) of `levels` ints
+ *   outputs : out_style (tgt_h, tgt_w, n_style) uint8, out_error (tgt_h, tgt_w) fp32 patch error of the final NNF,
+ *             out_nnf (tgt_h, tgt_w, 2) int32 (x, y) or NULL
+ * n_style <= 8, n_guide <= 24, odd patch >= 3, every side >= 2 * patch + 1, levels <= fresco_ebsynth_max_levels():
+ * FRESCO_EUNSUPPORTED otherwise, before any launch.  Same inputs and seed give bit-identical outputs.
+ * The whole pyramid runs on `stream` with no host synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+#define FRESCO_EBSYNTH_VOTE_PLAIN 1    /* weight 1            */
+#define FRESCO_EBSYNTH_VOTE_WEIGHTED 2 /* weight 1 / (1 + E)  */
+/* largest level count whose coarsest level keeps min(side of source, side of target) >= 2 * patch + 1 (0: none) */
+int fresco_ebsynth_max_levels(int src_w, int src_h, int tgt_w, int tgt_h, int patch);
+size_t fresco_ebsynth_workspace_bytes(int n_style, int n_guide, int src_w, int src_h, int tgt_w, int tgt_h,
+                                      int patch, int levels, int with_modulation);
+int fresco_ebsynth_run(const uint8_t* src_style, const uint8_t* src_guide, const uint8_t* tgt_guide,
+                       const uint8_t* tgt_modulation, const float* style_weights, const float* guide_weights,
+                       int n_style, int n_guide, int src_w, int src_h, int tgt_w, int tgt_h, float uniformity,
+                       int patch, int vote_mode, int levels, const int* search_vote_iters,
+                       const int* patchmatch_iters, const int* stop_threshold, int extra_pass_3x3, uint64_t seed,
+                       int32_t* out_nnf, uint8_t* out_style, float* out_error, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* Single stages of the run, with the run's kernels, on channel-interleaved uint8 images (for tests):
+ *   resample : bilinear downsample of an (ih, iw, nc <= 16) image to (oh, ow): sample point (x, y) * iw / ow, taps
+ *              clamped, truncated to a byte;
+ *   stop_mask: 255 where some of the ns <= 8 style channels changed by >= stop_threshold, dilated by the patch.
+ * workspace: fresco_ebsynth_stage_workspace_bytes(w, h, ow, oh) (w, h, w, h for the mask). */
+size_t fresco_ebsynth_stage_workspace_bytes(int w, int h, int ow, int oh);
+int fresco_ebsynth_resample(const uint8_t* in, int iw, int ih, int nc, uint8_t* out, int ow, int oh, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int fresco_ebsynth_stop_mask(const uint8_t* style_new, const uint8_t* style_old, int w, int h, int ns,
+                             int stop_threshold, int patch, uint8_t* mask, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 #ifdef __cplusplus
 }
