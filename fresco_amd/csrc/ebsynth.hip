@@ -103,8 +103,10 @@ __device__ __forceinline__ float occupancy(const EbLevel& L, const int* osnap, i
 }
 
 // One candidate: accepted iff err + lambda * occupancy drops (occupancies per `occupancy`; cur_occ is that of the
-// current best).  Accepted moves go to the live Omega with integer atomics (order-independent).  No contraction, so
-// the decision is the IEEE one the tests restate.
+// current best).  Accepted moves go to the live Omega with integer atomics (order-independent).  The decision is not
+// contracted, so given err it is the IEEE one the tests restate.  patch_error may be contracted (FMAs): its sum equals
+// the tests' exact one only while every weighted product and partial sum is an exact fp32 integer, which
+// tests/test_gpu_ebsynth_matrix.py checks on its inputs (integer weights, patch^2 * sum_c w_c * range_c^2 < 2^24).
 template <int RW, bool MOD>
 __device__ __forceinline__ void try_patch(const EbLevel& L, const int* osnap, int* olive, int ax, int ay, int2 c,
                                           int2 n0, int2& nbest, float& ebest, float& cur_occ) {

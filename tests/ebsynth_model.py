@@ -3,8 +3,10 @@
 Two schedules of the uniformity bookkeeping (Omega, the per-source-pixel patch coverage):
   omega="snapshot"  this repository's backend, bit for bit: every pass reads Omega from a pass-start snapshot plus the
                     pixel's own moves; other pixels' moves show from the next pass on; the random search runs all radii
-                    in one pass.  With integer-valued weights every error is an exact fp32 integer and the backend's
-                    NNF, E and image match this model exactly (tests/test_gpu_ebsynth.py).
+                    in one pass.  The backend's patch error may be contracted to FMAs; with integer-valued weights
+                    and patch^2 * sum_c w_c * range_c^2 < 2^24 every error and partial sum is an exact fp32 integer,
+                    and the backend's NNF, E and image match this model exactly (tests/test_gpu_ebsynth.py,
+                    tests/test_gpu_ebsynth_matrix.py).
   omega="live"      the reference GPU backend's ordering: Omega is updated after every candidate step and read live by
                     every pixel (all pixels advance in lockstep, one schedule the reference's concurrent atomics allow),
                     and each random-search radius is a pass of its own.
@@ -232,9 +234,18 @@ def patchmatch(L, om, nnf, E, mask, iters, seed, pass_id, omega, stats):
     return nnf, L.error(nnf), pass_id
 
 
+def per_level(v, levels):
+    if isinstance(v, (list, tuple)):
+        if len(v) != levels:
+            raise ValueError("%d per-level values given for %d pyramid levels" % (len(v), levels))
+        return [int(x) for x in v]
+    return [int(v)] * levels
+
+
 def run(ss, sg, tg, mod=None, sw=None, gw=None, uniformity=3500.0, patch=5, vote_mode="plain", levels=-1,
         svi=6, pmi=4, stop=5, extra_pass_3x3=False, seed=0, omega="snapshot", stats=None):
-    """The whole pyramid; returns (image, E, NNF).  Per-level arguments are ints (every level)."""
+    """The whole pyramid; returns (image, E, NNF).  The per-level arguments svi, pmi and stop take an int (every level)
+    or one value per level, coarse first, like ebsynth_run."""
     sh, swd, ns = ss.shape
     th, tw, ng = tg.shape
     sw = [1.0 / ns] * ns if sw is None else sw
@@ -242,6 +253,7 @@ def run(ss, sg, tg, mod=None, sw=None, gw=None, uniformity=3500.0, patch=5, vote
     top = max_levels(sh, swd, th, tw, patch)
     levels = top if levels == -1 else min(levels, top)
     stats = {"multi_accept": 0} if stats is None else stats
+    svi, pmi, stop = (per_level(v, levels) for v in (svi, pmi, stop))
     pass_id = 0
     nnf = None
     for level in range(levels):
@@ -262,15 +274,15 @@ def run(ss, sg, tg, mod=None, sw=None, gw=None, uniformity=3500.0, patch=5, vote
             pat, lam = (patch, uniformity) if p == 0 else (3, 0.0)
             ts = vote(lss, nnf, pat)
             mask = np.ones((lth, ltw), bool)
-            for v in range(svi):
+            for v in range(svi[level]):
                 L = Level(ts, ltg, lss, lsg, lmod, sw, gw, pat, lam)
-                if pmi > 0:
+                if pmi[level] > 0:
                     E = L.error(nnf)
-                    nnf, E, pass_id = patchmatch(L, om, nnf, E, mask, pmi, seed, pass_id, omega, stats)
+                    nnf, E, pass_id = patchmatch(L, om, nnf, E, mask, pmi[level], seed, pass_id, omega, stats)
                 else:
                     E = L.error(nnf)
                 new = vote(lss, nnf, pat, E if vote_mode == "weighted" else None)
-                if v < svi - 1:
-                    mask = stop_mask(new, ts, stop, pat)
+                if v < svi[level] - 1:
+                    mask = stop_mask(new, ts, stop[level], pat)
                 ts = new
     return ts, E, nnf

@@ -1,6 +1,7 @@
-"""Generate tests/golden/ebsynth_golden.npz by running the UNMODIFIED reference Ebsynth CPU backend.
+"""Generate tests/golden/ebsynth_golden.npz (and, with --wide, tests/golden/ebsynth_wide_golden.npz) by running the
+UNMODIFIED reference Ebsynth CPU backend.
 
-Run in the build container only:  python tests/golden/make_ebsynth_golden.py [--ref /path/to/FRESCO]
+Run in the build container only:  python tests/golden/make_ebsynth_golden.py [--ref /path/to/FRESCO] [--wide]
 
 The reference's CPU build (src/ebsynth/deps/ebsynth: ebsynth.cpp + ebsynth_cpu.cpp + ebsynth_nocuda.cpp) does not link
 as shipped: ebsynth.cpp dispatches to an ebsynthRunCuda that takes an outputErrorData argument, ebsynth_nocuda.cpp
@@ -12,6 +13,9 @@ weights), the reference's output image and its .bin error map, and the reference
 difference| and the mean-error ratio between a run on the inputs and runs on copies whose target guides are perturbed by
 1 LSB.  The random streams of two implementations differ, so the GPU tests compare quality against these numbers.
 
+  --wide              the cases outside the first file's shapes (WIDE_CASES): 8 RGB guides (style + guide channels in
+                      two 16-byte records) with mixed weights and patch 7, and an RGBA style with a target of another
+                      size than the source; own seeded random stream, the first file is left as it is
   --binary-only DIR   only build the reference binary into DIR (e.g. to time it elsewhere)
   --time BIN          time BIN on the 512x512 four-guide frame of video_blend.py (12 search/vote, 6 PatchMatch iters)
 """
@@ -28,6 +32,7 @@ from PIL import Image
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(HERE, "ebsynth_golden.npz")
+OUT_WIDE = os.path.join(HERE, "ebsynth_wide_golden.npz")
 
 STUB = r"""
 // ebsynthRunCuda with the signature ebsynth.cpp dispatches to; never called (ebsynthBackendAvailableCuda() is 0).
@@ -149,42 +154,93 @@ CASES = [
 ]
 
 
+# Outside the shapes above (--wide, written to OUT_WIDE): record width 2 and patch 7, and a 4-channel style with a target
+# of another size than the source.  name, style channels, source (h, w), target (h, w), guides [(channels, -weight or
+# None)], shift, binary args
+WIDE_CASES = [
+    ("eight_rgb_guides", 3, (56, 60), (56, 60),
+     [(3, 2.0), (3, None), (3, 0.5), (3, 1.0), (3, None), (3, 4.0), (3, 0.25), (3, None)], (2, -3),
+     ["-patchsize", "7", "-searchvoteiters", "4", "-patchmatchiters", "3"]),
+    ("rgba_style_resized_target", 4, (60, 68), (52, 77), [(3, None)], (-3, 2), []),
+]
+
+
+def make_wide_case(rng, ns, src_hw, tgt_hw, guide_kinds, shift):
+    """make_case, with a style of ns = 3 or 4 channels (the 4th an alpha in [64, 255], some of it below 255) and target
+    guides resized (bilinear) to tgt_hw before the shift and noise."""
+    h, w = src_hw
+    style = smooth_noise(rng, h, w, 3, 6)
+    if ns == 4:
+        style = np.concatenate([style, (64 + smooth_noise(rng, h, w, 1, 8).astype(np.int32) * 3 // 4)
+                                .astype(np.uint8)], -1)
+    guides = []
+    for c, wt in guide_kinds:
+        src = smooth_noise(rng, h, w, c, 5)
+        rs = src
+        if tuple(tgt_hw) != tuple(src_hw):
+            rs = np.stack([np.asarray(Image.fromarray(src[..., k]).resize(tgt_hw[::-1], Image.BILINEAR))
+                           for k in range(c)], -1)
+        tgt = shifted(rs, *shift).astype(np.int16) + rng.integers(-2, 3, rs.shape)
+        guides.append((src, np.clip(tgt, 0, 255).astype(np.uint8), wt))
+    return style, guides
+
+
+def reference_case(exe, d, rng, name, style, guides, args):
+    """Run the reference on one case and on two 1-LSB perturbations of its target guides; the arrays to store."""
+    img, err, _, cmd = run_reference(exe, d, style, guides, args, name)
+    st, sg, tg, counts = packed_inputs(d, name, len(guides))
+    # the reference's own spread: target guides perturbed by one LSB (seeded, two draws)
+    diffs, ratios = [], []
+    for k in range(2):
+        pg = []
+        for s, t, wt in guides:
+            p = t.astype(np.int16) + rng.integers(-1, 2, t.shape)
+            pg.append((s, np.clip(p, 0, 255).astype(np.uint8), wt))
+        img2, err2, _, _ = run_reference(exe, d, style, pg, args, name + "_p%d" % k)
+        diffs.append(float(np.abs(img2.astype(np.float64) - img).mean()))
+        ratios.append(float(err2.mean() / err.mean()))
+    print("%-12s out %s  mean E %.1f  spread: mean|d| %s  E ratio %s" %
+          (name, img.shape, err.mean(), ["%.3f" % v for v in diffs], ["%.3f" % v for v in ratios]))
+    return {
+        name + "/style": st,
+        name + "/source_guide": sg,
+        name + "/target_guide": tg,
+        name + "/guide_counts": np.array(counts, np.int32),
+        name + "/guide_weights_cli": np.array([-1.0 if wt is None else wt for _, _, wt in guides], np.float32),
+        name + "/args": np.array(args, dtype="U32"),
+        name + "/ref_out": img,
+        name + "/ref_err": err,
+        name + "/spread_mean_abs": np.array(diffs, np.float64),
+        name + "/spread_err_ratio": np.array(ratios, np.float64),
+    }
+
+
+def save(store, path):
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **store)
+    with open(path, "wb") as f:
+        f.write(buf.getvalue())
+    print("wrote %s (%d bytes)" % (path, len(buf.getvalue())))
+
+
 def generate(exe):
     rng = np.random.default_rng(20261015)
     store = {}
     with tempfile.TemporaryDirectory() as d:
         for name, (h, w), kinds, shift, args in CASES:
             style, guides = make_case(rng, h, w, kinds, shift)
-            img, err, _, cmd = run_reference(exe, d, style, guides, args, name)
-            st, sg, tg, counts = packed_inputs(d, name, len(guides))
-            # the reference's own spread: target guides perturbed by one LSB (seeded, two draws)
-            diffs, ratios = [], []
-            for k in range(2):
-                pg = []
-                for s, t, wt in guides:
-                    p = t.astype(np.int16) + rng.integers(-1, 2, t.shape)
-                    pg.append((s, np.clip(p, 0, 255).astype(np.uint8), wt))
-                img2, err2, _, _ = run_reference(exe, d, style, pg, args, name + "_p%d" % k)
-                diffs.append(float(np.abs(img2.astype(np.float64) - img).mean()))
-                ratios.append(float(err2.mean() / err.mean()))
-            print("%-12s out %s  mean E %.1f  spread: mean|d| %s  E ratio %s" %
-                  (name, img.shape, err.mean(), ["%.3f" % v for v in diffs], ["%.3f" % v for v in ratios]))
-            store[name + "/style"] = st
-            store[name + "/source_guide"] = sg
-            store[name + "/target_guide"] = tg
-            store[name + "/guide_counts"] = np.array(counts, np.int32)
-            store[name + "/guide_weights_cli"] = np.array([-1.0 if wt is None else wt for _, _, wt in guides],
-                                                          np.float32)
-            store[name + "/args"] = np.array(args, dtype="U32")
-            store[name + "/ref_out"] = img
-            store[name + "/ref_err"] = err
-            store[name + "/spread_mean_abs"] = np.array(diffs, np.float64)
-            store[name + "/spread_err_ratio"] = np.array(ratios, np.float64)
-    buf = io.BytesIO()
-    np.savez_compressed(buf, **store)
-    with open(OUT, "wb") as f:
-        f.write(buf.getvalue())
-    print("wrote %s (%d bytes)" % (OUT, len(buf.getvalue())))
+            store.update(reference_case(exe, d, rng, name, style, guides, args))
+    save(store, OUT)
+
+
+def generate_wide(exe):
+    rng = np.random.default_rng(20261016)
+    store = {}
+    with tempfile.TemporaryDirectory() as d:
+        for name, ns, src_hw, tgt_hw, kinds, shift, args in WIDE_CASES:
+            style, guides = make_wide_case(rng, ns, src_hw, tgt_hw, kinds, shift)
+            store.update(reference_case(exe, d, rng, name, style, guides, args))
+    save(store, OUT_WIDE)
 
 
 def time_frame(exe, runs=3):
@@ -207,6 +263,7 @@ def main():
                     help="root of the reference FRESCO checkout")
     ap.add_argument("--binary-only", metavar="DIR")
     ap.add_argument("--time", metavar="BIN")
+    ap.add_argument("--wide", action="store_true", help="write %s instead" % os.path.basename(OUT_WIDE))
     a = ap.parse_args()
     if a.time:
         time_frame(a.time)
@@ -216,7 +273,7 @@ def main():
         print(build_reference(a.ref, a.binary_only))
         return
     with tempfile.TemporaryDirectory() as d:
-        generate(build_reference(a.ref, d))
+        (generate_wide if a.wide else generate)(build_reference(a.ref, d))
 
 
 if __name__ == "__main__":

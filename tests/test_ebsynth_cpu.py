@@ -147,6 +147,19 @@ def test_host_queries():
     assert lib.fresco_ebsynth_workspace_bytes(3, 10, 64, 64, 64, 64, 4, -1, 0) == 0
 
 
+@pytest.mark.parametrize("ns,ng,rec", [(3, 13, 16), (3, 14, 32)])
+@pytest.mark.parametrize("with_mod", [0, 1])
+def test_workspace_bytes_at_the_record_width_boundary(ns, ng, rec, with_mod):
+    """16 style + guide channels fit one 16-byte record per pixel, 17 take two; a source 45x67 and a target 81x53 (sizes
+    whose byte counts are not multiples of the 256-byte alignment) give these exact byte counts."""
+    from fresco_amd import _lib
+    r256 = lambda n: (n + 255) // 256 * 256  # noqa: E731
+    S, T = 67 * 45, 53 * 81
+    want = (2 * r256(S * rec) + 3 * r256(T * rec) + 2 * r256(T * 8) + r256(T * 4) + 2 * r256(T) + 2 * r256(S * 4)
+            + with_mod * 2 * r256(T * rec))
+    assert _lib.load().fresco_ebsynth_workspace_bytes(ns, ng, 67, 45, 53, 81, 5, -1, with_mod) == want
+
+
 @pytest.mark.skipif(shutil.which(HIPCC) is None, reason="hipcc not found")
 def test_ebsynth_kernels_have_no_spills_or_scratch(tmp_path):
     """The method of tests/test_kernel_resources.py on ebsynth.hip: no kernel spills or uses scratch memory."""

@@ -1,6 +1,7 @@
 """Ebsynth HIP backend on the GPU: the deterministic stages against numpy restatements, known-answer shifts, quality
-parity with the reference CPU build on the golden cases (tests/golden/ebsynth_golden.npz, make_ebsynth_golden.py),
-bit-reproducibility, refused arguments, and the command line end to end."""
+parity with the reference CPU build on the golden cases (tests/golden/ebsynth_golden.npz and ebsynth_wide_golden.npz,
+make_ebsynth_golden.py), bit-reproducibility, refused arguments, and the command line end to end.  The exact-match
+matrix over record widths, patches and shapes is tests/test_gpu_ebsynth_matrix.py."""
 import os
 import struct
 import subprocess
@@ -20,6 +21,7 @@ import ebsynth_model  # noqa: E402
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "ebsynth_golden.npz")
+GOLDEN_WIDE = os.path.join(ROOT, "tests", "golden", "ebsynth_wide_golden.npz")
 DEV = "cuda:0"
 M64 = (1 << 64) - 1
 
@@ -138,6 +140,16 @@ def case():
                 mod=rng.integers(0, 256, (40, 44, 4), dtype=np.uint8), sw=[0.5, 0.25, 1.0], gw=[1.0, 0.5, 2.0, 0.25])
 
 
+@pytest.fixture(scope="module")
+def wide_case():
+    """8 style + 20 guide channels (two 16-byte records per pixel), a distinct fractional weight per channel"""
+    rng = np.random.default_rng(29)
+    return dict(ss=smooth(rng, 37, 43, 8), sg=smooth(rng, 37, 43, 20), tg=smooth(rng, 33, 40, 20),
+                mod=rng.integers(0, 256, (33, 40, 20), dtype=np.uint8),
+                sw=[float(v) for v in np.float32(rng.permutation(8) + 1) / np.float32(7)],
+                gw=[float(v) for v in np.float32(rng.permutation(20) + 1) / np.float32(13)])
+
+
 def test_stage_random_init_and_plain_vote(case):
     """levels = 1, no search: the NNF is the random initialisation, the image its plain vote, E stays 0."""
     c = case
@@ -149,18 +161,26 @@ def test_stage_random_init_and_plain_vote(case):
     assert float(err.abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("mode,with_mod", [("plain", False), ("weighted", False), ("weighted", True)])
-def test_stage_patch_error_and_vote(case, mode, with_mod):
+@pytest.mark.parametrize("which,mode,with_mod", [
+    pytest.param("case", "plain", False, id="plain-False"), pytest.param("case", "weighted", False, id="weighted-False"),
+    pytest.param("case", "weighted", True, id="weighted-True"),
+    pytest.param("wide_case", "plain", False, id="rw2-plain-False"),
+    pytest.param("wide_case", "weighted", False, id="rw2-weighted-False"),
+    pytest.param("wide_case", "weighted", True, id="rw2-weighted-True"),
+    pytest.param("wide_case", "plain", True, id="rw2-plain-True")])
+def test_stage_patch_error_and_vote(request, which, mode, with_mod):
     """levels = 1, one search/vote iteration, no PatchMatch: E = patch error of the initial NNF against the first plain
-    vote, then a plain or weighted vote with that E."""
-    c = case
+    vote, then a plain or weighted vote with that E.  Per-channel weights all differ, so E depends on each channel
+    reading its own weight; the wide case's second record holds style + guide bytes 16..27."""
+    c = request.getfixturevalue(which)
     mod = c["mod"] if with_mod else None
+    (sh, sw), (th, tw) = c["ss"].shape[:2], c["tg"].shape[:2]
     out, err, nnf = ebsynth_run(gpu(c["ss"]), gpu(c["sg"]), gpu(c["tg"]),
                                 target_modulation=None if mod is None else gpu(mod), style_weights=c["sw"],
                                 guide_weights=c["gw"], pyramid_levels=1, search_vote_iters=1, patchmatch_iters=0,
                                 vote_mode=mode, seed=5, return_nnf=True)
     n = nnf.cpu().numpy()
-    np.testing.assert_array_equal(n, random_nnf(40, 44, 48, 56, 2, 5))
+    np.testing.assert_array_equal(n, random_nnf(th, tw, sh, sw, 2, 5))
     v1 = vote(c["ss"], n, 5)
     e = patch_error(v1, c["tg"], c["ss"], c["sg"], n, c["sw"], c["gw"], 5, mod)
     np.testing.assert_allclose(err.cpu().numpy(), e, rtol=1e-5)
@@ -187,10 +207,13 @@ def test_stage_resample(ih, iw, oh, ow, nc):
     np.testing.assert_array_equal(got, resample(img, oh, ow))
 
 
-@pytest.mark.parametrize("thr,patch", [(5, 5), (1, 3), (0, 5), (40, 7)])
-def test_stage_stop_mask(thr, patch):
+@pytest.mark.parametrize("thr,patch,nc", [
+    pytest.param(5, 5, 3, id="5-5"), pytest.param(1, 3, 3, id="1-3"), pytest.param(0, 5, 3, id="0-5"),
+    pytest.param(40, 7, 3, id="40-7"), pytest.param(5, 5, 1, id="5-5-1ch"), pytest.param(1, 3, 8, id="1-3-8ch"),
+    pytest.param(3, 5, 8, id="3-5-8ch")])
+def test_stage_stop_mask(thr, patch, nc):
     rng = np.random.default_rng(thr)
-    old = rng.integers(0, 256, (37, 45, 3), dtype=np.uint8)
+    old = rng.integers(0, 256, (37, 45, nc), dtype=np.uint8)
     new = np.clip(old.astype(np.int32) + rng.integers(-6, 7, old.shape) * (rng.random(old.shape) < 0.02), 0,
                   255).astype(np.uint8)
     got = E.stop_mask(gpu(new), gpu(old), thr, patch).cpu().numpy()
@@ -267,8 +290,8 @@ def golden_cases():
     return sorted({k.split("/")[0] for k in z.files})
 
 
-def golden_args(name):
-    z = np.load(GOLDEN)
+def golden_args(name, path=GOLDEN):
+    z = np.load(path)
     g = lambda k: z[name + "/" + k]  # noqa: E731
     args = [str(a) for a in g("args")]
     cli = E.parse_cli(["-style", "s"] + sum([["-guide", "a", "b"] for _ in g("guide_counts")], []) + args)
@@ -281,8 +304,8 @@ def golden_args(name):
     return g, [float(np.float32(1.0) / np.float32(ns))] * ns, gw, cli
 
 
-def run_golden(name, seed):
-    g, sw, gw, cli = golden_args(name)
+def run_golden(name, seed, path=GOLDEN):
+    g, sw, gw, cli = golden_args(name, path)
     out, err = ebsynth_run(gpu(g("style")), gpu(g("source_guide")), gpu(g("target_guide")), style_weights=sw,
                            guide_weights=gw, uniformity=cli["uniformity"], patch_size=cli["patchsize"],
                            search_vote_iters=cli["searchvoteiters"], patchmatch_iters=cli["patchmatchiters"],
@@ -290,9 +313,9 @@ def run_golden(name, seed):
     return out.cpu().numpy(), err.cpu().numpy(), g
 
 
-def run_golden_model(name, seed):
+def run_golden_model(name, seed, path=GOLDEN):
     """the reference GPU backend's algorithm (live Omega, one pass per random-search radius), restated in numpy"""
-    g, sw, gw, cli = golden_args(name)
+    g, sw, gw, cli = golden_args(name, path)
     out, err, _ = ebsynth_model.run(g("style"), g("source_guide"), g("target_guide"), sw=sw, gw=gw,
                                     uniformity=cli["uniformity"], patch=cli["patchsize"], svi=cli["searchvoteiters"],
                                     pmi=cli["patchmatchiters"], stop=cli["stopthreshold"], seed=seed, omega="live")
@@ -318,6 +341,28 @@ def test_parity_with_reference_quality(name, seed):
         m_out, m_err = run_golden_model(name, seed)
         base_ratio = float(m_err.mean() / ref_err.mean())
         base_mad = float(np.abs(m_out.astype(np.float64) - ref_out).mean())
+    print("%s seed %d: mean E / CPU reference %.3f (bar %.3f), mean |out - CPU reference| %.3f (bar %.3f)"
+          % (name, seed, ratio, 1.10 * base_ratio, mad, base_mad + spread))
+    assert ratio <= 1.10 * base_ratio
+    assert mad <= base_mad + spread
+
+
+# Outside those shapes (tests/golden/ebsynth_wide_golden.npz, make_ebsynth_golden.py --wide): 8 RGB guides (3 + 24
+# channels, two 16-byte records) with mixed weights and patch 7, and an RGBA style whose target guide has another size
+# than the source.  Held to the small cases' bars: the numpy restatement of the reference's GPU algorithm on the same
+# inputs.
+@pytest.mark.parametrize("seed", [0, 7, 99])
+@pytest.mark.parametrize("name", ["eight_rgb_guides", "rgba_style_resized_target"])
+def test_parity_with_reference_quality_wide(name, seed):
+    out, err, g = run_golden(name, seed, GOLDEN_WIDE)
+    ref_out, ref_err = g("ref_out"), g("ref_err")
+    assert out.shape == ref_out.shape
+    ratio = float(err.mean() / ref_err.mean())
+    mad = float(np.abs(out.astype(np.float64) - ref_out).mean())
+    spread = 3.0 * float(g("spread_mean_abs").max()) + 1.0
+    m_out, m_err = run_golden_model(name, seed, GOLDEN_WIDE)
+    base_ratio = float(m_err.mean() / ref_err.mean())
+    base_mad = float(np.abs(m_out.astype(np.float64) - ref_out).mean())
     print("%s seed %d: mean E / CPU reference %.3f (bar %.3f), mean |out - CPU reference| %.3f (bar %.3f)"
           % (name, seed, ratio, 1.10 * base_ratio, mad, base_mad + spread))
     assert ratio <= 1.10 * base_ratio
