@@ -26,7 +26,7 @@ class FrescoHipError(RuntimeError):
 
 
 _c = ctypes
-_vp, _i, _f, _sz, _i64 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_size_t, _c.c_int64
+_vp, _i, _f, _d, _sz, _i64 = _c.c_void_p, _c.c_int, _c.c_float, _c.c_double, _c.c_size_t, _c.c_int64
 
 # name -> (restype, argtypes); must list every symbol include/fresco_hip.h declares
 SIGNATURES = {
@@ -92,6 +92,12 @@ SIGNATURES = {
     "fresco_ebsynth_stage_workspace_bytes": (_sz, [_i] * 4),
     "fresco_ebsynth_resample": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
     "fresco_ebsynth_stop_mask": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "fresco_blend_workspace_bytes": (_sz, [_i, _i]),
+    "fresco_blend_frame": (_i, [_vp] * 4 + [_i, _i, _d, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "fresco_bgr_to_lab_u8": (_i, [_vp, _vp, _i, _vp]),
+    "fresco_lab_to_bgr_u8": (_i, [_vp, _vp, _i, _vp]),
+    "fresco_histogram_blend": (_i, [_vp] * 3 + [_i, _i, _d, _d, _vp, _vp, _vp, _sz, _vp]),
+    "fresco_poisson_fusion": (_i, [_vp] * 4 + [_i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -526,6 +526,37 @@ int fresco_ebsynth_stop_mask(const uint8_t* style_new, const uint8_t* style_old,
                              int stop_threshold, int patch, uint8_t* mask, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * (h)  Video blending -- the per-frame step of video_blend.py process_seq that merges the forward and backward Ebsynth
+ * propagations of an in-between frame (src/ebsynth/blender: histogram_blend.blend, poisson_fusion).  DESIGN.md
+ * section 10.  Images are uint8 BGR (h, w, 3), masks uint8 (h, w) of 0 / 1, error maps fp32 (h, w), flow fp32
+ * (2, h, w) with the x plane first.  Sides 2..4096 (FRESCO_EUNSUPPORTED otherwise, before any launch); every call runs
+ * on `stream` with no host synchronisation, and same inputs give bit-identical outputs.
+ *   fresco_blend_frame: mask = 0 where weight1 d1 < (1 - weight1) d2, else 1 (all 0 at weight1 == 0, all 1 at
+ *     weight1 == 1), OR the previous mask warped by grid_sample(nearest, zeros, align_corners) at pixel + flow
+ *     (prev_mask and flow both NULL or both set; out_mask must not be prev_mask); the min-error image, its histogram
+ *     blend with weights (1 - weight1, weight1) and, with FRESCO_BLEND_GRADIENT, the Poisson fusion with the HOST
+ *     array grad_weight[3] (L, a, b), solved exactly.  9 launches with gradient blending, 3 without.
+ *   stage entry points (tests): Lab conversions of n_pixels; the histogram blend of a and b onto min_error's Lab
+ *     statistics; the Poisson fusion of blend_bgr with the gradients of i1 / i2 (i2 where mask > 0).  out_lab (nullable)
+ *     receives the Lab bytes that the final conversion to out_bgr reads.
+ * workspace: fresco_blend_workspace_bytes(w, h) for every call but the Lab conversions (0 for unsupported sides).
+ * ------------------------------------------------------------------------------------------ */
+#define FRESCO_BLEND_GRADIENT 1
+size_t fresco_blend_workspace_bytes(int w, int h);
+int fresco_blend_frame(const uint8_t* oa, const uint8_t* ob, const float* d1, const float* d2, int w, int h,
+                       double weight1, const uint8_t* prev_mask, const float* flow, int flags,
+                       const float* grad_weight, uint8_t* out_mask, uint8_t* out_bgr, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int fresco_bgr_to_lab_u8(const uint8_t* bgr, uint8_t* lab, int n_pixels, void* stream);
+int fresco_lab_to_bgr_u8(const uint8_t* lab, uint8_t* bgr, int n_pixels, void* stream);
+int fresco_histogram_blend(const uint8_t* a, const uint8_t* b, const uint8_t* min_error, int w, int h,
+                           double weight1, double weight2, uint8_t* out_bgr, uint8_t* out_lab, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int fresco_poisson_fusion(const uint8_t* blend_bgr, const uint8_t* i1, const uint8_t* i2, const uint8_t* mask, int w,
+                          int h, const float* grad_weight, uint8_t* out_bgr, uint8_t* out_lab, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
