@@ -13,7 +13,7 @@ from .warp import Dilate, adaptive_instance_normalization, calc_mean_std, flow_w
 from .hook import apply_FRESCO_opt, disable_FRESCO_opt, patch_reference
 from .mapping import cross_frame_masks, get_mapping_ind, get_single_mapping_ind
 from .step import predict_x0, step
-from .ebsynth import ebsynth_run
+from .ebsynth import ebsynth_run, ebsynth_run_batch
 from . import blend
 from .paras import (correlation_matrices, forward_backward_consistency_check, get_flow_and_interframe_paras,
                     get_intraframe_paras, interframe_paras_from_flows)
@@ -24,5 +24,5 @@ __all__ = [
     "disable_FRESCO_opt", "patch_reference", "get_mapping_ind", "get_single_mapping_ind", "cross_frame_masks",
     "step", "predict_x0", "get_flow_and_interframe_paras", "get_intraframe_paras", "interframe_paras_from_flows",
     "forward_backward_consistency_check", "correlation_matrices",
-    "ebsynth_run", "blend", "FrescoHipError", "LIB_PATH",
+    "ebsynth_run", "ebsynth_run_batch", "blend", "FrescoHipError", "LIB_PATH",
 ]

@@ -89,9 +89,14 @@ SIGNATURES = {
     "fresco_ebsynth_workspace_bytes": (_sz, [_i] * 9),
     "fresco_ebsynth_run": (_i, [_vp] * 6 + [_i] * 6 + [_f, _i, _i, _i, _vp, _vp, _vp, _i, _c.c_uint64, _vp, _vp, _vp,
                                                      _vp, _sz, _vp]),
+    "fresco_ebsynth_batch_workspace_bytes": (_sz, [_i] * 10),
+    "fresco_ebsynth_run_batch": (_i, [_i] + [_vp] * 6 + [_i] * 6 + [_f, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp,
+                                                              _vp, _vp, _sz, _vp]),
     "fresco_ebsynth_stage_workspace_bytes": (_sz, [_i] * 4),
     "fresco_ebsynth_resample": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
     "fresco_ebsynth_stop_mask": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "fresco_edge_guide": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "fresco_warp_nearest": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "fresco_blend_workspace_bytes": (_sz, [_i, _i]),
     "fresco_blend_frame": (_i, [_vp] * 4 + [_i, _i, _d, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "fresco_bgr_to_lab_u8": (_i, [_vp, _vp, _i, _vp]),

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "warp_nearest.h"
 
 namespace fresco {
 namespace {
@@ -110,17 +111,6 @@ __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// grid_sample(nearest, zeros, align_corners=True) of the previous mask at pixel + flow, through torch's normalise /
-// unnormalise round trip in fp32 (flow_utils.py bilinear_sample; ATen's CPU grid sampler), ties to even
-__device__ __forceinline__ uint8_t warp_nearest(const uint8_t* prev, const float* flow, int x, int y, int w, int h) {
-    const size_t q = size_t(y) * w + x;
-    const float cx = float(x) + flow[q], cy = float(y) + flow[size_t(w) * h + q];
-    const float gx = 2.0f * cx / float(w - 1) - 1.0f, gy = 2.0f * cy / float(h - 1) - 1.0f;
-    const float ix = rintf((gx + 1.0f) * (float(w - 1) / 2.0f)), iy = rintf((gy + 1.0f) * (float(h - 1) / 2.0f));
-    if (!(ix >= 0.0f && ix < float(w) && iy >= 0.0f && iy < float(h))) return 0;  // NaN falls out too
-    return prev[size_t(iy) * w + size_t(ix)];
 }
 
 template <int MODE>

@@ -2,7 +2,9 @@
 of FRESCO, video_blend.py, which runs the reference's Ebsynth binary once per in-between frame).
 
 ``ebsynth_run`` is the Python entry point: one call into libfresco_hip.so (``fresco_ebsynth_run``) runs the whole
-pyramid on the current stream.  ``python -m fresco_amd.ebsynth`` (and the shell shim ``fresco_amd/bin/ebsynth``) is a
+pyramid on the current stream.  ``ebsynth_run_batch`` runs n problems of one shape in one launch sequence
+(``fresco_ebsynth_run_batch``), each equal to its own ``ebsynth_run``; ``edge_guide`` and ``warp_nearest`` build
+video_blend.py's edge and warped guides on the GPU (fresco_amd.propagate drives all of them for the whole stage).  ``python -m fresco_amd.ebsynth`` (and the shell shim ``fresco_amd/bin/ebsynth``) is a
 drop-in for the reference binary's command line: same flags, channel counting and default weights, and the same
 ``<output>.png`` + ``<output>.bin`` files (recipe C).
 """
@@ -48,6 +50,32 @@ def _check_image(name, t, channels=None, hw=None):
         raise ValueError("%s is %dx%d, expected %dx%d" % ((name,) + tuple(t.shape[:2]) + tuple(hw)))
 
 
+def _prepare(style, source_guide, target_guide, target_modulation, style_weights, guide_weights, patch_size,
+             vote_mode, pyramid_levels, search_vote_iters, patchmatch_iters, stop_threshold):
+    """Checks and ctypes arguments shared by ebsynth_run and ebsynth_run_batch; images are (h, w, c) per problem (the
+    batch dimension already stripped from the shapes given)."""
+    if vote_mode not in VOTE_MODES:
+        raise ValueError("vote_mode must be one of %s, got %r" % (sorted(VOTE_MODES), vote_mode))
+    sh, sw, ns = (int(v) for v in style)
+    th, tw, ng = (int(v) for v in target_guide)
+    sweights = [1.0 / ns] * ns if style_weights is None else [float(v) for v in style_weights]
+    gweights = [1.0 / ng] * ng if guide_weights is None else [float(v) for v in guide_weights]
+    if len(sweights) != ns or len(gweights) != ng:
+        raise ValueError("style_weights / guide_weights need %d / %d values, got %d / %d"
+                         % (ns, ng, len(sweights), len(gweights)))
+    pyramid_levels = int(pyramid_levels)
+    if pyramid_levels != -1 and pyramid_levels < 1:
+        raise ValueError("pyramid_levels must be -1 or >= 1, got %d" % pyramid_levels)
+    top = max_pyramid_levels((sh, sw), (th, tw), patch_size)
+    levels = top if pyramid_levels == -1 else min(pyramid_levels, top)
+    c = _lib._c
+    return dict(sh=sh, sw=sw, ns=ns, th=th, tw=tw, ng=ng, levels=levels, top=top,
+                svi=_per_level("search_vote_iters", search_vote_iters, levels),
+                pmi=_per_level("patchmatch_iters", patchmatch_iters, levels),
+                stop=_per_level("stop_threshold", stop_threshold, levels),
+                sw_arr=(c.c_float * ns)(*sweights), gw_arr=(c.c_float * ng)(*gweights))
+
+
 def ebsynth_run(style, source_guide, target_guide, *, target_modulation=None, style_weights=None, guide_weights=None,
                 uniformity=3500.0, patch_size=5, vote_mode="plain", pyramid_levels=-1, search_vote_iters=6,
                 patchmatch_iters=4, stop_threshold=5, extra_pass_3x3=False, seed=0, return_nnf=False):
@@ -69,23 +97,9 @@ def ebsynth_run(style, source_guide, target_guide, *, target_modulation=None, st
     if target_modulation is not None:
         _check_image("target_modulation", target_modulation, channels=target_guide.shape[2],
                      hw=target_guide.shape[:2])
-    if vote_mode not in VOTE_MODES:
-        raise ValueError("vote_mode must be one of %s, got %r" % (sorted(VOTE_MODES), vote_mode))
-    sh, sw, ns = (int(v) for v in style.shape)
-    th, tw, ng = (int(v) for v in target_guide.shape)
-    sweights = [1.0 / ns] * ns if style_weights is None else [float(v) for v in style_weights]
-    gweights = [1.0 / ng] * ng if guide_weights is None else [float(v) for v in guide_weights]
-    if len(sweights) != ns or len(gweights) != ng:
-        raise ValueError("style_weights / guide_weights need %d / %d values, got %d / %d"
-                         % (ns, ng, len(sweights), len(gweights)))
-    pyramid_levels = int(pyramid_levels)
-    if pyramid_levels != -1 and pyramid_levels < 1:
-        raise ValueError("pyramid_levels must be -1 or >= 1, got %d" % pyramid_levels)
-    top = max_pyramid_levels((sh, sw), (th, tw), patch_size)
-    levels = top if pyramid_levels == -1 else min(pyramid_levels, top)
-    svi = _per_level("search_vote_iters", search_vote_iters, levels)
-    pmi = _per_level("patchmatch_iters", patchmatch_iters, levels)
-    stop = _per_level("stop_threshold", stop_threshold, levels)
+    a = _prepare(style.shape, source_guide.shape, target_guide.shape, target_modulation, style_weights, guide_weights,
+                 patch_size, vote_mode, pyramid_levels, search_vote_iters, patchmatch_iters, stop_threshold)
+    sh, sw, ns, th, tw, ng, levels = (a[k] for k in ("sh", "sw", "ns", "th", "tw", "ng", "levels"))
     ops._need_gpu(style, source_guide, target_guide, target_modulation)
 
     lib = _lib.load()
@@ -93,9 +107,6 @@ def ebsynth_run(style, source_guide, target_guide, *, target_modulation=None, st
     style, source_guide, target_guide = (t.contiguous() for t in (style, source_guide, target_guide))
     if target_modulation is not None:
         target_modulation = target_modulation.contiguous()
-    c = _lib._c
-    sw_arr = (c.c_float * ns)(*sweights)
-    gw_arr = (c.c_float * ng)(*gweights)
     nbytes = lib.fresco_ebsynth_workspace_bytes(ns, ng, sw, sh, tw, th, int(patch_size), levels,
                                                 int(target_modulation is not None))
     ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
@@ -103,13 +114,124 @@ def ebsynth_run(style, source_guide, target_guide, *, target_modulation=None, st
     err = torch.empty((th, tw), dtype=torch.float32, device=dev)
     nnf = torch.empty((th, tw, 2), dtype=torch.int32, device=dev) if return_nnf else None
     rc = lib.fresco_ebsynth_run(style.data_ptr(), source_guide.data_ptr(), target_guide.data_ptr(),
-                                ops._ptr(target_modulation), sw_arr, gw_arr, ns, ng, sw, sh, tw, th,
-                                float(uniformity), int(patch_size), VOTE_MODES[vote_mode], levels if top else -1,
-                                svi, pmi, stop, int(bool(extra_pass_3x3)), int(seed) & (2 ** 64 - 1), ops._ptr(nnf),
-                                out.data_ptr(), err.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
+                                ops._ptr(target_modulation), a["sw_arr"], a["gw_arr"], ns, ng, sw, sh, tw, th,
+                                float(uniformity), int(patch_size), VOTE_MODES[vote_mode],
+                                levels if a["top"] else -1, a["svi"], a["pmi"], a["stop"], int(bool(extra_pass_3x3)),
+                                int(seed) & (2 ** 64 - 1), ops._ptr(nnf), out.data_ptr(), err.data_ptr(),
+                                ws.data_ptr(), ws.numel(), ops._stream())
     _lib.check(rc, "fresco_ebsynth_run(style %dx%dx%d, target %dx%dx%d, patch %s)" % (sh, sw, ns, th, tw, ng,
                                                                                       patch_size))
     return (out, err, nnf) if return_nnf else (out, err)
+
+
+MAX_BATCH = 64  # FRESCO_EBSYNTH_MAX_BATCH
+
+
+def batch_workspace_bytes(n, n_style, n_guide, source_hw, target_hw, patch_size=5, with_modulation=False):
+    """Device bytes ``ebsynth_run_batch`` allocates for n problems of these shapes (0 if the library refuses them)."""
+    (sh, sw), (th, tw) = source_hw, target_hw
+    return int(_lib.load().fresco_ebsynth_batch_workspace_bytes(int(n), int(n_style), int(n_guide), int(sw), int(sh),
+                                                                 int(tw), int(th), int(patch_size), -1,
+                                                                 int(bool(with_modulation))))
+
+
+def _check_batch(name, t, channels=None, shape=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 4:
+        raise ValueError("%s must be a uint8 (N, H, W, C) tensor" % name)
+    if channels is not None and t.shape[3] != channels:
+        raise ValueError("%s has %d channels, expected %d" % (name, t.shape[3], channels))
+    if shape is not None and tuple(t.shape[:3]) != tuple(shape):
+        raise ValueError("%s is %s, expected %s x H x W = %s" % (name, tuple(t.shape[:3]), name, tuple(shape)))
+
+
+def ebsynth_run_batch(style, source_guide, target_guide, *, target_modulation=None, style_weights=None,
+                      guide_weights=None, uniformity=3500.0, patch_size=5, vote_mode="plain", pyramid_levels=-1,
+                      search_vote_iters=6, patchmatch_iters=4, stop_threshold=5, extra_pass_3x3=False, seeds=0,
+                      return_nnf=False, workspace=None):
+    """n ``ebsynth_run`` problems of one shape and one set of arguments in one launch sequence.
+
+    style (n, sh, sw, ns), source_guide (n, sh, sw, ng), target_guide (n, th, tw, ng) and target_modulation
+    (n, th, tw, ng, optional) are uint8 GPU tensors; ``seeds`` is one int for every problem or n ints.  Every other
+    argument is ``ebsynth_run``'s and applies to every problem.  Returns (images (n, th, tw, ns), errors (n, th, tw))
+    and, with ``return_nnf``, the NNFs (n, th, tw, 2): problem b equals ``ebsynth_run`` on its inputs and seed, bit for
+    bit.  1 <= n <= MAX_BATCH.  ``workspace``: an optional uint8 GPU tensor of at least ``batch_workspace_bytes``
+    (a caller running many batches of one shape can keep one)."""
+    _check_batch("style", style)
+    n = int(style.shape[0])
+    _check_batch("source_guide", source_guide, shape=style.shape[:3])
+    _check_batch("target_guide", target_guide, channels=source_guide.shape[3])
+    if int(target_guide.shape[0]) != n:
+        raise ValueError("target_guide holds %d problems, style %d" % (target_guide.shape[0], n))
+    if target_modulation is not None:
+        _check_batch("target_modulation", target_modulation, channels=target_guide.shape[3],
+                     shape=target_guide.shape[:3])
+    seeds = [int(seeds)] * n if isinstance(seeds, int) else [int(s) for s in seeds]
+    if len(seeds) != n:
+        raise ValueError("%d seeds given for %d problems" % (len(seeds), n))
+    a = _prepare(style.shape[1:], source_guide.shape[1:], target_guide.shape[1:], target_modulation, style_weights,
+                 guide_weights, patch_size, vote_mode, pyramid_levels, search_vote_iters, patchmatch_iters,
+                 stop_threshold)
+    sh, sw, ns, th, tw, ng, levels = (a[k] for k in ("sh", "sw", "ns", "th", "tw", "ng", "levels"))
+    ops._need_gpu(style, source_guide, target_guide, target_modulation)
+
+    lib = _lib.load()
+    dev = target_guide.device
+    style, source_guide, target_guide = (t.contiguous() for t in (style, source_guide, target_guide))
+    if target_modulation is not None:
+        target_modulation = target_modulation.contiguous()
+    if workspace is None:
+        nbytes = lib.fresco_ebsynth_batch_workspace_bytes(max(n, 1), ns, ng, sw, sh, tw, th, int(patch_size), levels,
+                                                          int(target_modulation is not None))
+        workspace = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+    out = torch.empty((n, th, tw, ns), dtype=torch.uint8, device=dev)
+    err = torch.empty((n, th, tw), dtype=torch.float32, device=dev)
+    nnf = torch.empty((n, th, tw, 2), dtype=torch.int32, device=dev) if return_nnf else None
+    seed_arr = (_lib._c.c_uint64 * max(n, 1))(*[s & (2 ** 64 - 1) for s in seeds])
+    rc = lib.fresco_ebsynth_run_batch(n, style.data_ptr(), source_guide.data_ptr(), target_guide.data_ptr(),
+                                      ops._ptr(target_modulation), a["sw_arr"], a["gw_arr"], ns, ng, sw, sh, tw, th,
+                                      float(uniformity), int(patch_size), VOTE_MODES[vote_mode],
+                                      levels if a["top"] else -1, a["svi"], a["pmi"], a["stop"],
+                                      int(bool(extra_pass_3x3)), seed_arr, ops._ptr(nnf), out.data_ptr(),
+                                      err.data_ptr(), workspace.data_ptr(), workspace.numel(), ops._stream())
+    _lib.check(rc, "fresco_ebsynth_run_batch(n %d, style %dx%dx%d, target %dx%dx%d, patch %s)"
+               % (n, sh, sw, ns, th, tw, ng, patch_size))
+    return (out, err, nnf) if return_nnf else (out, err)
+
+
+def _check_guide_input(name, img):
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() not in (3, 4):
+        raise ValueError("%s must be a uint8 (H, W, C) or (N, H, W, C) tensor" % name)
+    ops._need_gpu(img)
+    return img.contiguous() if img.dim() == 4 else img.contiguous()[None]
+
+
+def edge_guide(img):
+    """video_blend.py's edge guide on the GPU: cv2.filter2D(img, -1, [[0,-1,0],[-1,4,-1],[0,-1,0]]) with
+    BORDER_REFLECT_101, saturated, of a uint8 (h, w, c) or (n, h, w, c) tensor (sides >= 2, c <= 16)."""
+    x = _check_guide_input("img", img)
+    n, h, w, c = (int(v) for v in x.shape)
+    out = torch.empty_like(x)
+    rc = _lib.load().fresco_edge_guide(x.data_ptr(), out.data_ptr(), n, w, h, c, ops._stream())
+    _lib.check(rc, "fresco_edge_guide(%dx%dx%dx%d)" % (n, h, w, c))
+    return out if img.dim() == 4 else out[0]
+
+
+def warp_nearest(img, flow):
+    """flow_calc.warp(img, flow, 'nearest') on the GPU for a uint8 (h, w, c) or (n, h, w, c) tensor: grid_sample
+    (nearest, zeros, align_corners=True) at pixel + flow.  flow: float32 (2, h, w) / (1, 2, h, w) per image, or
+    (n, 2, h, w) for a batch (x plane first, as read_flow gives it)."""
+    x = _check_guide_input("img", img)
+    n, h, w, c = (int(v) for v in x.shape)
+    if not isinstance(flow, torch.Tensor) or flow.dtype != torch.float32 or flow.numel() != n * 2 * h * w \
+            or tuple(flow.shape[-3:]) != (2, h, w):
+        raise ValueError("flow must be float32 (n, 2, %d, %d) for %d image(s), got %s"
+                         % (h, w, n, tuple(getattr(flow, "shape", ()))))
+    ops._need_gpu(flow)
+    f = flow.contiguous()
+    out = torch.empty_like(x)
+    rc = _lib.load().fresco_warp_nearest(x.data_ptr(), f.data_ptr(), out.data_ptr(), n, w, h, c, ops._stream())
+    _lib.check(rc, "fresco_warp_nearest(%dx%dx%dx%d)" % (n, h, w, c))
+    return out if img.dim() == 4 else out[0]
 
 
 def _stage_ws(w, h, ow, oh, dev):
@@ -337,5 +459,6 @@ def main(argv=None):
     return 0
 
 
-__all__ = ["ebsynth_run", "max_pyramid_levels", "parse_cli", "pack_inputs", "num_channels", "write_error_bin",
+__all__ = ["ebsynth_run", "ebsynth_run_batch", "batch_workspace_bytes", "edge_guide", "warp_nearest",
+           "max_pyramid_levels", "parse_cli", "pack_inputs", "num_channels", "write_error_bin",
            "bin_path", "main", "FrescoHipError"]

@@ -514,6 +514,24 @@ int fresco_ebsynth_run(const uint8_t* src_style, const uint8_t* src_guide, const
                        const int* patchmatch_iters, const int* stop_threshold, int extra_pass_3x3, uint64_t seed,
                        int32_t* out_nnf, uint8_t* out_style, float* out_error, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* Batched form: n problems that share the channel counts, the source and target sizes, the weights and every
+ * per-level argument run through one launch sequence (the launches and copies of one fresco_ebsynth_run).  Every
+ * image and output is n images of the single call's layout, back to back (problem b of src_style starts at
+ * b * src_h * src_w * n_style bytes); seeds is a HOST array of n.  Problem b gives the same image, E and NNF, bit for
+ * bit, as fresco_ebsynth_run with its inputs and seeds[b]: the random stream does not depend on the batch position.
+ * 1 <= n <= FRESCO_EBSYNTH_MAX_BATCH (the seeds travel in kernel arguments): FRESCO_EINVAL below,
+ * FRESCO_EUNSUPPORTED above, FRESCO_EWORKSPACE under fresco_ebsynth_batch_workspace_bytes(n, ...) (0 outside the
+ * range), all before any launch.  fresco_ebsynth_run is n = 1 of this code; its workspace is the n = 1 size. */
+#define FRESCO_EBSYNTH_MAX_BATCH 64
+size_t fresco_ebsynth_batch_workspace_bytes(int n, int n_style, int n_guide, int src_w, int src_h, int tgt_w,
+                                            int tgt_h, int patch, int levels, int with_modulation);
+int fresco_ebsynth_run_batch(int n, const uint8_t* src_style, const uint8_t* src_guide, const uint8_t* tgt_guide,
+                             const uint8_t* tgt_modulation, const float* style_weights, const float* guide_weights,
+                             int n_style, int n_guide, int src_w, int src_h, int tgt_w, int tgt_h, float uniformity,
+                             int patch, int vote_mode, int levels, const int* search_vote_iters,
+                             const int* patchmatch_iters, const int* stop_threshold, int extra_pass_3x3,
+                             const uint64_t* seeds, int32_t* out_nnf, uint8_t* out_style, float* out_error,
+                             void* workspace, size_t workspace_bytes, void* stream);
 /* Single stages of the run, with the run's kernels, on channel-interleaved uint8 images (for tests):
  *   resample : bilinear downsample of an (ih, iw, nc <= 16) image to (oh, ow): sample point (x, y) * iw / ow, taps
  *              clamped, truncated to a byte;
@@ -556,6 +574,19 @@ int fresco_histogram_blend(const uint8_t* a, const uint8_t* b, const uint8_t* mi
 int fresco_poisson_fusion(const uint8_t* blend_bgr, const uint8_t* i1, const uint8_t* i2, const uint8_t* mask, int w,
                           int h, const float* grad_weight, uint8_t* out_bgr, uint8_t* out_lab, void* workspace,
                           size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (i)  Ebsynth guides -- the guide images video_blend.py builds (src/ebsynth/blender/guide.py), batched over n uint8
+ * images of (h, w, c), channel-interleaved, back to back.  DESIGN.md section 9.
+ *   fresco_edge_guide  : cv2.filter2D(img, -1, [[0,-1,0],[-1,4,-1],[0,-1,0]]), BORDER_REFLECT_101, saturated.
+ *   fresco_warp_nearest: flow_calc.warp(img, flow, 'nearest') -- grid_sample(nearest, zeros, align_corners=True) at
+ *                        pixel + flow through flow_utils' fp32 normalise / unnormalise, ties to even; flow is n fp32
+ *                        (2, h, w) planes, x first (what read_flow gives).
+ * 2 <= w, h; 1 <= c <= 16; 1 <= n <= 65535 (FRESCO_EUNSUPPORTED / FRESCO_EINVAL otherwise, before the launch); out must
+ * not be img.  One launch on `stream` each, no host synchronisation, exact (integer) results.
+ * ------------------------------------------------------------------------------------------ */
+int fresco_edge_guide(const uint8_t* img, uint8_t* out, int n, int w, int h, int c, void* stream);
+int fresco_warp_nearest(const uint8_t* img, const float* flow, uint8_t* out, int n, int w, int h, int c, void* stream);
 
 #ifdef __cplusplus
 }
