@@ -14,12 +14,18 @@ fused K|V rows (broadcast) and the other frames' selected rows (all-gather) for 
 pass runs trajectory-sharded between two all-to-alls (fresco_amd/dist.py); `collective_bytes_received_per_rank` in the
 JSON line states the fabric bytes.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel, attn_flash_kernel<40> on the
-up_blocks.3 cross-frame pass: algorithmic flop 4*B*HW*M*C per launch / mean HIP-event duration of those
-launches, measured in a second, instrumented replay of the same K steps (so `value` is not perturbed).
-`cpu_baseline` times the oracle (a CPU port of the reference algorithm) on rank 0's host cores on one
-call per (layer, mode) and weights them by the schedule; `torch_gpu_baseline` times the same port as plain
-PyTorch ops on the same GPU (the "reference PyTorch path" of the north star).
+Prints ONE JSON line (rank 0).  A plain run does only what the headline needs: setup, the W warm-up steps, the K timed
+steps, --dump-outputs if given, and the line (`value`, `ms_per_step`, `timing`, `config`, host issue time; on N > 1 GPUs
+the collective counts and bytes, which are arithmetic).  Its `roofline` and `cpu_baseline` are null.
+
+--full adds every other measurement and check, all of it AFTER the timed steps (so `value` is not perturbed):
+`roofline` is for the dominant kernel, attn_flash_kernel<40> on the up_blocks.3 cross-frame pass: algorithmic flop
+4*B*HW*M*C per launch / mean HIP-event duration of those launches, measured in a second, instrumented replay of the same
+K steps (`kernel_avg_us`: every kernel of that replay).  `cpu_baseline` times the oracle (a CPU port of the reference
+algorithm) on rank 0's host cores on one call per (layer, mode) and weights them by the schedule; `torch_gpu_baseline`
+times the same port as plain PyTorch ops on the same GPU (the "reference PyTorch path" of the north star).  Then the
+auxiliary legs (cfg2b, cfg2c, cfg3, f3_gmflow, full_step / latent_delta, cfg5) and, on N > 1 GPUs, the rank census, the
+sharded-vs-single-GPU check, the exchange timings and the opt-in p2p / hipGraph legs.
 """
 import argparse
 import ctypes
@@ -597,10 +603,16 @@ def main():
                          "(float32, a seeded sample of token rows where the full outputs exceed 64 MB; rank 0's frames)")
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--res", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement and check: the instrumented replay "
+                         "(roofline, per-kernel times), the CPU and PyTorch baselines, the auxiliary legs and, on N > 1 "
+                         "GPUs, the census / parity / exchange legs; off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU / PyTorch baselines and the legs built on them")
     ap.add_argument("--no-aux", action="store_true",
-                    help="skip the auxiliary legs (cfg2b, cfg2c): only the timed steps and their instrumented replay "
-                         "run, so that a rocprofv3 --stats average of the flash kernel is over the bench's own launches")
+                    help="with --full: skip the auxiliary legs (cfg2b, cfg2c, cfg5): only the timed steps and their "
+                         "instrumented replay run, so that a rocprofv3 --stats average of the flash kernel is over the "
+                         "bench's own launches")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -705,47 +717,11 @@ def main():
         dist.all_reduce(th, op=dist.ReduceOp.SUM)
         host_all = [float(v) for v in th.tolist()]
 
-    # instrumented replay of the same K steps: per-launch HIP-event durations of the dominant kernel
-    cap = args.steps * 64 + 64
-    lib.fresco_prof_enable(cap)
-    run_eager(0, args.steps)
-    torch.cuda.synchronize()
-    lib.fresco_prof_disable()
-    recs = read_prof(lib, cap)
     B_loc = 2 * n_loc
     HW3 = (R // 8) ** 2
     M3 = int(params[8][3].sum())
-    dom = [ms for tag, d, ms in recs if tag == 1 and d == (B_loc * 8, HW3, M3, 40)]
-    roofline = None
-    # (the committed PMC passes profile the single-GPU launch: no traffic figure for a frame shard's smaller launch)
-    pmc = pmc_traffic_bytes("attn_flash_kernelILi40") if world == 1 else None
-    if dom:
-        flop = 4.0 * B_loc * HW3 * M3 * 320
-        mean_s = sum(dom) / len(dom) * 1e-3
-        ach = flop / mean_s
-        roofline = dict(bound="mfma", kernel="attn_flash_kernel<40> (up_blocks.3 cross-frame pass)",
-                        achieved=round(ach / 1e12, 2), peak=PEAK_F16_DENSE / 1e12, unit="TFLOP/s",
-                        frac=round(ach / PEAK_F16_DENSE, 4),
-                        # HBM bytes per launch from the committed PMC passes (a number, or null without a profile)
-                        traffic=(pmc or {}).get("bytes"), traffic_source=(pmc or {}).get("source"),
-                        traffic_note=(pmc or {}).get("note"),
-                        algorithmic_bytes_per_launch=int(2 * B_loc * HW3 * 320 * 2 + 2 * 2 * M3 * 320 * 2),
-                        launches=len(dom),
-                        executed_flop_per_launch=flop * 1.4,
-                        note="achieved / frac count ALGORITHMIC flop against the 2.5 PFLOP/s dense fp16 spec peak; the kernel "
-                             "executes 1.40 x that (head dim 40 padded to 48 in QK^T and to 64 rows in PV), and its MFMA strand "
-                             "ALONE (28 MFMAs per 64 x 64 block back to back, nothing else) takes ~314 us on these boxes, i.e. "
-                             "the clock they sustain under matrix load caps this launch at ~0.45 (profiles/r03_attn_pipe.txt). "
-                             "INPUT REGIME: the bench's activations (random projections of N(0,1) hidden states) give logit "
-                             "bounds ~7 and a near-uniform softmax, the kernel's best case; `roofline_worst_regime` is the same "
-                             "launch on N(0,1) q, k",
-                        avg_launch_us=round(mean_s * 1e6, 2), algorithmic_flop_per_launch=flop)
-    by_tag = {}
-    for tag, d, ms in recs:
-        key = {1: "attn_flash", 2: "kv_pack", 3: "temporal", 10: "linear"}.get(tag, str(tag)) + str(list(d))
-        by_tag.setdefault(key, []).append(ms)
-    kernels_us = {k: round(1e3 * sum(v) / len(v), 2) for k, v in sorted(by_tag.items())}
-
+    # the headline line: every figure in it comes from the timed blocks above or from arithmetic on the workload
+    res = None
     if rank == 0:
         res = {
             "metric": "denoising-steps/sec (%d-frame batch, %d^2), FRESCO hot-path step" % (N, R),
@@ -779,8 +755,7 @@ def main():
                                 "of the exchange is timed beside it (`p2p_exchange`)" % world)
                                if world > 1 else "single GPU",
             },
-            "roofline": roofline,
-            "kernel_avg_us": kernels_us,
+            "roofline": None,
             "launch_mode": launch_mode,
             "ms_per_step_by_mode": {"eager": round(1e3 * dt / args.steps, 4)},
             # what every rank's HOST needed to issue one step (median block, before the closing synchronize): when it nears
@@ -801,6 +776,56 @@ def main():
                           for n_ in ("L2", "L3"))
             res["collectives_per_step"] = dict(cross_frame=cf_coll, temporal_all_to_all=12,
                                                schedule_mean=round(cf_coll + 12 * 8.0 / 15.0, 1))
+        else:
+            res["cpu_baseline"] = None
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(res, separators=(",", ":")), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full only: the instrumented replay, the baselines and the auxiliary legs (the line is printed at the end)
+    # instrumented replay of the same K steps: per-launch HIP-event durations of the dominant kernel
+    cap = args.steps * 64 + 64
+    lib.fresco_prof_enable(cap)
+    run_eager(0, args.steps)
+    torch.cuda.synchronize()
+    lib.fresco_prof_disable()
+    recs = read_prof(lib, cap)
+    dom = [ms for tag, d, ms in recs if tag == 1 and d == (B_loc * 8, HW3, M3, 40)]
+    roofline = None
+    # (the committed PMC passes profile the single-GPU launch: no traffic figure for a frame shard's smaller launch)
+    pmc = pmc_traffic_bytes("attn_flash_kernelILi40") if world == 1 else None
+    if dom:
+        flop = 4.0 * B_loc * HW3 * M3 * 320
+        mean_s = sum(dom) / len(dom) * 1e-3
+        ach = flop / mean_s
+        roofline = dict(bound="mfma", kernel="attn_flash_kernel<40> (up_blocks.3 cross-frame pass)",
+                        achieved=round(ach / 1e12, 2), peak=PEAK_F16_DENSE / 1e12, unit="TFLOP/s",
+                        frac=round(ach / PEAK_F16_DENSE, 4),
+                        # HBM bytes per launch from the committed PMC passes (a number, or null without a profile)
+                        traffic=(pmc or {}).get("bytes"), traffic_source=(pmc or {}).get("source"),
+                        traffic_note=(pmc or {}).get("note"),
+                        algorithmic_bytes_per_launch=int(2 * B_loc * HW3 * 320 * 2 + 2 * 2 * M3 * 320 * 2),
+                        launches=len(dom),
+                        executed_flop_per_launch=flop * 1.4,
+                        note="achieved / frac count ALGORITHMIC flop against the 2.5 PFLOP/s dense fp16 spec peak; the kernel "
+                             "executes 1.40 x that (head dim 40 padded to 48 in QK^T and to 64 rows in PV), and its MFMA strand "
+                             "ALONE (28 MFMAs per 64 x 64 block back to back, nothing else) takes ~314 us on these boxes, i.e. "
+                             "the clock they sustain under matrix load caps this launch at ~0.45 (profiles/r03_attn_pipe.txt). "
+                             "INPUT REGIME: the bench's activations (random projections of N(0,1) hidden states) give logit "
+                             "bounds ~7 and a near-uniform softmax, the kernel's best case; `roofline_worst_regime` is the same "
+                             "launch on N(0,1) q, k",
+                        avg_launch_us=round(mean_s * 1e6, 2), algorithmic_flop_per_launch=flop)
+    by_tag = {}
+    for tag, d, ms in recs:
+        key = {1: "attn_flash", 2: "kv_pack", 3: "temporal", 10: "linear"}.get(tag, str(tag)) + str(list(d))
+        by_tag.setdefault(key, []).append(ms)
+    kernels_us = {k: round(1e3 * sum(v) / len(v), 2) for k, v in sorted(by_tag.items())}
+    if rank == 0:
+        res["roofline"] = roofline
+        res["kernel_avg_us"] = kernels_us
         if world == 1 and not args.no_aux:
             res["cfg2b"] = cfg2b_large_mask(layers, N, R, device, lib)
             rows3 = params[8][3].reshape(-1).nonzero().squeeze(1).to(torch.int32).to(device)
@@ -889,8 +914,6 @@ def main():
                                             vs_lean_port=res["speedup_vs_torch_gpu_lean_port"],
                                             note="the reference's op sequence includes its two torch.cuda.empty_cache() calls "
                                                  "per layer call; the lean port drops them and the redundant clones")
-        elif world == 1:
-            res["cpu_baseline"] = None
     # ---- watchdog for everything below (started BEFORE the cfg5 leg: a rank that throws inside it would otherwise leave its
     # peers in a collective with nobody watching).  A hang prints the line as far as it got and exits; the watchdog's line
     # and the normal one are mutually exclusive.

@@ -47,3 +47,16 @@ def test_bench_py_parses_and_keeps_its_flags():
     for flag in ("--gpus", "--steps", "--warmup"):
         assert flag in src
     assert "dist.barrier()" in src and "torch.cuda.synchronize()" in src and "ReduceOp.MAX" in src
+
+
+def test_bench_py_full_is_an_opt_in_switch():
+    """everything beyond the headline (roofline replay, baselines, auxiliary legs) sits behind --full, off by default"""
+    tree = ast.parse(open(os.path.join(ROOT, "bench.py")).read())
+    opts = {}
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Call) and getattr(node.func, "attr", None) == "add_argument" and node.args:
+            if isinstance(node.args[0], ast.Constant):
+                opts[node.args[0].value] = {k.arg: k.value for k in node.keywords}
+    assert "--full" in opts
+    action = opts["--full"].get("action")
+    assert isinstance(action, ast.Constant) and action.value == "store_true" and "default" not in opts["--full"]
