@@ -15,6 +15,7 @@ from .mapping import cross_frame_masks, get_mapping_ind, get_single_mapping_ind
 from .step import predict_x0, step
 from .ebsynth import ebsynth_run, ebsynth_run_batch
 from . import blend
+from .flowcalc import FlowCalc, patch_flow_calc
 from .paras import (correlation_matrices, forward_backward_consistency_check, get_flow_and_interframe_paras,
                     get_intraframe_paras, interframe_paras_from_flows)
 
@@ -24,5 +25,5 @@ __all__ = [
     "disable_FRESCO_opt", "patch_reference", "get_mapping_ind", "get_single_mapping_ind", "cross_frame_masks",
     "step", "predict_x0", "get_flow_and_interframe_paras", "get_intraframe_paras", "interframe_paras_from_flows",
     "forward_backward_consistency_check", "correlation_matrices",
-    "ebsynth_run", "ebsynth_run_batch", "blend", "FrescoHipError", "LIB_PATH",
+    "ebsynth_run", "ebsynth_run_batch", "blend", "FlowCalc", "patch_flow_calc", "FrescoHipError", "LIB_PATH",
 ]

@@ -103,6 +103,8 @@ SIGNATURES = {
     "fresco_lab_to_bgr_u8": (_i, [_vp, _vp, _i, _vp]),
     "fresco_histogram_blend": (_i, [_vp] * 3 + [_i, _i, _d, _d, _vp, _vp, _vp, _sz, _vp]),
     "fresco_poisson_fusion": (_i, [_vp] * 4 + [_i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "fresco_flowcalc_input": (_i, [_vp] * 4 + [_i] * 4 + [_vp]),
+    "fresco_flowcalc_output": (_i, [_vp] * 5 + [_i, _i, _i, _f, _f, _vp]),
 }
 
 _lib = None

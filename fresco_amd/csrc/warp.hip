@@ -10,46 +10,9 @@
 // consecutive lanes read consecutive pixels of one channel plane (coalesced; the 4-tap gathers of
 // a smooth flow stay within a few cache lines of the plane).
 #include "common.h"
+#include "flow_consistency.h"
 
 namespace fresco {
-
-struct Taps {
-    int i00, i01, i10, i11;
-    float w00, w01, w10, w11;
-};
-
-// geometry.py:50-55,65-72: grid = pixel + flow, normalised 2*x/(w-1)-1, grid_sample(align_corners=True)
-// maps back with ((g+1)/2)*(size-1); zeros padding -> out-of-range taps get weight 0.
-__device__ __forceinline__ Taps make_taps(float fx, float fy, int x, int y, int h, int w) {
-    const float gx = 2.f * ((float)x + fx) / (float)(w - 1) - 1.f;
-    const float gy = 2.f * ((float)y + fy) / (float)(h - 1) - 1.f;
-    const float ix = ((gx + 1.f) / 2.f) * (float)(w - 1);
-    const float iy = ((gy + 1.f) / 2.f) * (float)(h - 1);
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    const float tx = ix - x0f, ty = iy - y0f;
-    // clamp before the int conversion so that huge / non-finite coordinates stay defined
-    const float x0c = fminf(fmaxf(x0f, -2.f), (float)w + 1.f);
-    const float y0c = fminf(fmaxf(y0f, -2.f), (float)h + 1.f);
-    const int x0 = (int)x0c, y0 = (int)y0c, x1 = x0 + 1, y1 = y0 + 1;
-    const bool vx0 = x0 >= 0 && x0 < w && x0f == x0c, vx1 = x1 >= 0 && x1 < w && x0f == x0c;
-    const bool vy0 = y0 >= 0 && y0 < h && y0f == y0c, vy1 = y1 >= 0 && y1 < h && y0f == y0c;
-    const int cx0 = min(max(x0, 0), w - 1), cx1 = min(max(x1, 0), w - 1);
-    const int cy0 = min(max(y0, 0), h - 1), cy1 = min(max(y1, 0), h - 1);
-    Taps t;
-    t.i00 = cy0 * w + cx0;
-    t.i01 = cy0 * w + cx1;
-    t.i10 = cy1 * w + cx0;
-    t.i11 = cy1 * w + cx1;
-    t.w00 = (vx0 && vy0) ? (1.f - tx) * (1.f - ty) : 0.f;
-    t.w01 = (vx1 && vy0) ? tx * (1.f - ty) : 0.f;
-    t.w10 = (vx0 && vy1) ? (1.f - tx) * ty : 0.f;
-    t.w11 = (vx1 && vy1) ? tx * ty : 0.f;
-    return t;
-}
-
-__device__ __forceinline__ float sample(const float* __restrict__ plane, const Taps& t) {
-    return plane[t.i00] * t.w00 + plane[t.i01] * t.w01 + plane[t.i10] * t.w10 + plane[t.i11] * t.w11;
-}
 
 constexpr int CPT = 8;  // channels per thread
 
@@ -210,7 +173,8 @@ __global__ __launch_bounds__(256) void chan_mean_std_kernel(const T* __restrict_
 }
 
 // forward_backward_consistency_check (geometry.py:75-96) + the colour-difference refinement of
-// get_flow_and_interframe_paras (diffusion_hacked.py:919-926), one thread per (pair, pixel):
+// get_flow_and_interframe_paras (diffusion_hacked.py:919-926), one thread per (pair, pixel); the check itself is
+// flow_consistency.h's fb_check, shared with fresco_flowcalc_output:
 //   occ_f = |fwd + warp(bwd, fwd)| > alpha (|fwd| + |bwd|) + beta   [OR  mean_c |img_n - warp(img_n+1, fwd)| > thr]
 //   occ_b = |bwd + warp(fwd, bwd)| > ...                            [OR  mean_c |img_n+1 - warp(img_n, bwd)| > thr]
 // Pair n couples frame n with frame (n+1) mod N.  The two tap sets are shared by the flow and the colour
@@ -226,17 +190,9 @@ __global__ __launch_bounds__(256) void flow_occlusion_kernel(const float* __rest
     const int n = blockIdx.y;
     if (p >= hw) return;
     const int y = p / w, x = p - y * w;
-    const float* f = fwd + (int64_t)n * 2 * hw;
-    const float* b = bwd + (int64_t)n * 2 * hw;
-    const float fx = f[p], fy = f[hw + p], bx = b[p], by = b[hw + p];
-    const float mag = sqrtf(fx * fx + fy * fy) + sqrtf(bx * bx + by * by);
-    const float thr = alpha * mag + beta;
-    const Taps tf = make_taps(fx, fy, x, y, h, w);
-    const Taps tb = make_taps(bx, by, x, y, h, w);
-    const float dfx = fx + sample(b, tf), dfy = fy + sample(b + hw, tf);
-    const float dbx = bx + sample(f, tb), dby = by + sample(f + hw, tb);
-    bool of = sqrtf(dfx * dfx + dfy * dfy) > thr;
-    bool ob = sqrtf(dbx * dbx + dby * dby) > thr;
+    const FbCheck fb = fb_check(fwd + (int64_t)n * 2 * hw, bwd + (int64_t)n * 2 * hw, hw, w, x, y, h, w, alpha, beta);
+    const Taps &tf = fb.tf, &tb = fb.tb;
+    bool of = fb.occ_f, ob = fb.occ_b;
     if (images) {
         const float* cur = images + (int64_t)n * C * hw;
         const float* nxt = images + (int64_t)((n + 1) % N) * C * hw;

@@ -519,6 +519,13 @@ class GMFlow(nn.Module):
         mean = torch.tensor([0.485, 0.456, 0.406], device=dev).view(1, 3, 1, 1)
         std = torch.tensor([0.229, 0.224, 0.225], device=dev).view(1, 3, 1, 1)
         x = torch.cat((img0, img1), 0).float()
+        return self.forward_normalised((x / 255.0 - mean) / std, splits, pred_bidir_flow)
+
+    @torch.no_grad()
+    def forward_normalised(self, x, splits=2, pred_bidir_flow=True):
+        """forward() from the network's own input: x (2b, 3, H, W) fp32, images 0 then images 1, already normalised
+        ((img / 255.0 - mean) / std) -- what fresco_amd.flowcalc builds from uint8 frames on the device."""
+        dev = x.device
         if x.is_cuda and os.environ.get("FRESCO_GMFLOW_LIBRARY_OPS", "0") != "1":
             # the dense layers' operands live as fp16 planes of x * 2^6 (weights: w * 2^10): an activation beyond +-1015 or a
             # weight beyond +-63 would saturate there -- finite, wrong, and these flows feed occlusion thresholds and pixel
@@ -526,14 +533,14 @@ class GMFlow(nn.Module):
             # forward is recomputed with library ops (exact fp32 range) when it is set.
             self._wts.out_of_range = False
             with ops.fn_range_guard(x.device) as guard:
-                flow = self._forward_native((x / 255.0 - mean) / std, splits, pred_bidir_flow)
+                flow = self._forward_native(x, splits, pred_bidir_flow)
             if not (guard.tripped() or self._wts.out_of_range):
                 return {"flow_preds": [flow]}
             import warnings
             warnings.warn("fresco_amd.GMFlow: an activation or weight left the range of the split-fp16 dense layers "
                           "(|activation| < 1015, |weight| < 63); this forward is recomputed with library ops",
-                          RuntimeWarning, stacklevel=2)
-        feats = self.backbone((x / 255.0 - mean) / std)
+                          RuntimeWarning, stacklevel=3)
+        feats = self.backbone(x)
         f0, f1 = feats.chunk(2, 0)
         b, c, h, w = f0.shape
         if h % splits or w % splits:

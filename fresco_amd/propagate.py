@@ -4,8 +4,9 @@ The reference's ``run_ebsynth`` starts one Ebsynth process per in-between frame 
 through ``subprocess.run``).  ``patch_run_ebsynth(vb)`` rebinds a loaded ``video_blend`` module's ``run_ebsynth`` to
 ``run_ebsynth`` here, which writes the same files:
 
-* flows through the module's own ``flow_calc.get_flow`` (same arguments and save paths), read back through the
-  ``read_flow`` / ``read_mask`` that ``blender.guide`` uses;
+* flows through the module's own ``flow_calc.get_flow`` (same arguments and save paths), or in one batched
+  ``flow_calc.get_flows`` call over every chain's pairs when it has one (``fresco_amd.flowcalc.FlowCalc``, recipe E),
+  read back through the ``read_flow`` / ``read_mask`` that ``blender.guide`` uses;
 * the edge, positional and temporal guides and ``output_seq[0]`` through the module's own ``cv2`` (``imread``,
   ``imwrite``, ``inpaint(..., 30, INPAINT_TELEA)``); the edge filter and the nearest warps run on the GPU
   (``fresco_amd.ebsynth.edge_guide`` / ``warp_nearest``), inpainting stays on the host;
@@ -205,14 +206,31 @@ def run_ebsynth(vb, video_sequence, *, max_batch=None, synth=None, threads=8, st
     chains = [Chain(video_sequence, i, fwd) for i in range(video_sequence.n_seq) for fwd in (True, False)]
     pool = ThreadPoolExecutor(max_workers=max(1, min(int(threads), MAX_THREADS)))
     try:
-        # flows, exactly as process_one_sequence computes them
+        # flows, exactly as process_one_sequence computes them; a batched flow_calc (fresco_amd.flowcalc.FlowCalc) takes
+        # every chain's pairs in one call, each input frame read once
         def flows_of(c):
             for j in range(c.interval - 1):
                 i1 = cv2.imread(c.inputs[j])
                 i2 = cv2.imread(c.inputs[j + 1])
                 vb.flow_calc.get_flow(i1, i2, c.flows[j])
 
-        timed("flows", lambda: [flows_of(c) for c in chains])
+        def batched_flows():
+            paths, slot, pairs, saves = [], {}, [], []
+            for c in chains:
+                for j in range(c.interval - 1):
+                    for p in c.inputs[j:j + 2]:
+                        if p not in slot:
+                            slot[p] = len(paths)
+                            paths.append(p)
+                    pairs.append((slot[c.inputs[j]], slot[c.inputs[j + 1]]))
+                    saves.append(c.flows[j])
+            if pairs:
+                vb.flow_calc.get_flows(list(pool.map(cv2.imread, paths)), pairs, saves, return_flows=False)
+
+        if hasattr(vb.flow_calc, "get_flows"):
+            timed("flows", batched_flows)
+        else:
+            timed("flows", lambda: [flows_of(c) for c in chains])
 
         def read_chain(c):
             c.flow = [gm.read_flow(f) for f in c.flows]

@@ -588,6 +588,26 @@ int fresco_poisson_fusion(const uint8_t* blend_bgr, const uint8_t* i1, const uin
 int fresco_edge_guide(const uint8_t* img, uint8_t* out, int n, int w, int h, int c, void* stream);
 int fresco_warp_nearest(const uint8_t* img, const float* flow, uint8_t* out, int n, int w, int h, int c, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * (j)  FlowCalc glue -- what FRESCO's FlowCalc.get_flow (src/ebsynth/flow/flow_utils.py) runs around GMFlow, batched
+ * over P frame pairs of n distinct frames.  DESIGN.md section 9.2.  Padding: InputPadder(mode='sintel',
+ * padding_factor=8): H' = H + ph, ph = ((H / 8 + 1) * 8 - H) % 8, ph / 2 rows on top and ph - ph / 2 below; W' alike.
+ *   fresco_flowcalc_input : frames (n, H, W, 3) uint8 (cv2.imread's BGR order, fed as is); first / second (P) int32
+ *                           frame indices in [0, n) on the device.  out (2P, 3, H', W') fp32: first images, then second
+ *                           images, replicate-padded and normalised as GMFlow.forward does it on the device,
+ *                           (x * fp32(1 / 255) - mean) / std, not contracted -- bit-identical to torch.
+ *   fresco_flowcalc_output: flows (2P, 2, H', W') fp32, GMFlow's bidirectional output (pair p's forward field at p, its
+ *                           backward field at P + p).  Per pair: InputPadder.unpad, then forward_backward_consistency_check
+ *                           on the unpadded fields (the arithmetic of fresco_flow_occlusion, same bits).  Writes bwd_flow
+ *                           (P, 2, H, W) fp32 and bwd_occ (P, H, W) uint8 0 / 255; fwd_flow / fwd_occ (both or neither)
+ *                           receive the forward field and fwd_occ -- what the swapped pair would write.
+ * 2 <= H, W; 2P <= 65535 (input) / P <= 65535 (output).  One launch on `stream` each, no host synchronisation.
+ * ------------------------------------------------------------------------------------------ */
+int fresco_flowcalc_input(const uint8_t* frames, const int* first, const int* second, float* out, int n, int P, int H,
+                          int W, void* stream);
+int fresco_flowcalc_output(const float* flows, float* bwd_flow, uint8_t* bwd_occ, float* fwd_flow, uint8_t* fwd_occ,
+                           int P, int H, int W, float alpha, float beta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
