@@ -12,7 +12,8 @@
 // Without gradient blending the frame is the first three of these (rhs writes the histogram blend's BGR).
 //
 // Colour conversions and the mask warp are fp64 / non-contracted fp32 (this file builds with -ffp-contract=off) so they
-// follow the numpy restatement of tests/blend_model.py operation by operation; the GEMMs use explicit fmaf.
+// follow the numpy restatement of tests/blend_model.py operation by operation; the GEMMs use explicit fmaf inside a
+// k-step and sum the k-steps in fp64.
 #include <cmath>
 
 #include "common.h"
@@ -318,7 +319,11 @@ struct GemmArgs {
 };
 
 // 64 x 64 output tile per 256-thread workgroup, 4 x 4 per thread, k-steps of 16 staged in LDS (8.5 KB).  Tiles are
-// zero-filled past the matrix edges, so any M, N, K work.  Each output is one k-ordered fmaf chain: deterministic.
+// zero-filled past the matrix edges, so any M, N, K work.  Each output is a k-ordered fmaf chain per k-step and a
+// k-ordered fp64 sum of the steps: deterministic.  The fp64 sum is what keeps the solve's error far below kTruncGuard
+// at large sides: one fp32 chain over K = 4096 rounds every add at the size of the running sum, which the DC term
+// (up to 127 sqrt(K) forward, 127 from the first step on backward) dominates, and on high-contrast frames that error
+// passed the guard from 2048^2 up.
 template <int EPI>
 __global__ __launch_bounds__(256) void blend_gemm(GemmArgs g) {
     __shared__ float As[kGemmK][kGemmTile + 4];  // transposed: As[k][m]
@@ -329,11 +334,11 @@ __global__ __launch_bounds__(256) void blend_gemm(GemmArgs g) {
     const int M = g.M, N = g.N, K = g.K;
     const int m0 = blockIdx.y * kGemmTile, n0 = blockIdx.x * kGemmTile;
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    float acc[4][4];
+    double acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
     const int ar = t >> 2, ac = (t & 3) * 4;   // A tile: row ar, columns ac .. ac + 3
     const int br = t >> 4, bc = (t & 15) * 4;  // B tile: row br, columns bc .. bc + 3
     for (int k0 = 0; k0 < K; k0 += kGemmK) {
@@ -354,6 +359,11 @@ __global__ __launch_bounds__(256) void blend_gemm(GemmArgs g) {
             }
         }
         __syncthreads();
+        float part[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) part[i][j] = 0.f;
 #pragma unroll
         for (int k = 0; k < kGemmK; ++k) {
             float a[4], b[4];
@@ -364,8 +374,12 @@ __global__ __launch_bounds__(256) void blend_gemm(GemmArgs g) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(a[i], b[j], acc[i][j]);
+                for (int j = 0; j < 4; ++j) part[i][j] = fmaf(a[i], b[j], part[i][j]);
         }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] += double(part[i][j]);
         __syncthreads();
     }
 #pragma unroll
@@ -377,7 +391,7 @@ __global__ __launch_bounds__(256) void blend_gemm(GemmArgs g) {
             const int gn = n0 + tx * 4 + j;
             if (gn >= N) continue;
             const size_t o = size_t(gm) * N + gn;
-            float v = acc[i][j];
+            float v = float(acc[i][j]);
             if (EPI == kEpiScale) v = v / (1.0f + g.gw2[z] * (g.lam_m[gm] + g.lam_n[gn]));
             if (EPI == kEpiLab) {
                 // poisson_fusion: clip(x + mean, 0, 255).astype(uint8) truncates; kTruncGuard keeps an exactly

@@ -103,22 +103,49 @@ def min_error_image(a, b, mask):
 # ---------------------------------------------------------------------------------------------------------------------
 # histogram blend
 # ---------------------------------------------------------------------------------------------------------------------
-def _transform(img, means, stds, target_means, target_stds):
+def constant_channels(lab):
+    """bool (3,): the channels of a uint8 (h, w, 3) image that hold one value everywhere (std exactly 0)"""
+    flat = np.asarray(lab).reshape(-1, 3)
+    return flat.min(axis=0) == flat.max(axis=0)
+
+
+def _transform(img, means, stds, target_means, target_stds, const=None):
+    """(img - mean) * target_std / std + target_mean per channel.  The zero-std rule, stated
+    here once: a channel flagged in ``const`` (std 0, where the reference divides by zero) becomes the target mean.
+    Channels that are not flagged are computed exactly as without the argument."""
     x = img.astype(np.float32)
-    return (x - means.reshape(1, 1, 3)) * target_stds.reshape(1, 1, 3) / stds.reshape(1, 1, 3) + \
+    if const is None or not const.any():
+        return (x - means.reshape(1, 1, 3)) * target_stds.reshape(1, 1, 3) / stds.reshape(1, 1, 3) + \
+            target_means.reshape(1, 1, 3)
+    out = (x - means.reshape(1, 1, 3)) * target_stds.reshape(1, 1, 3) / np.where(const, 1, stds).reshape(1, 1, 3) + \
         target_means.reshape(1, 1, 3)
+    out[..., const] = np.asarray(target_means, out.dtype)[const]
+    return out
 
 
 def histogram_blend_lab(a, b, min_error, weight1=0.5, weight2=0.5):
     """histogram_blend.blend up to (and including) the rounded uint8 Lab result"""
+    return np.clip(np.round(histogram_blend_values(a, b, min_error, weight1, weight2)), 0, 255).astype(np.uint8)
+
+
+def histogram_blend_values(a, b, min_error, weight1=0.5, weight2=0.5):
+    """histogram_blend.blend's Lab values before the rounding and the clip to uint8: float (h, w, 3).
+
+    Zero-std rule: a constant channel of a or of b transfers to the target mean (128), and so does the blend ab onto
+    the min-error image's mean where ab is constant.  "Constant" is decided from the inputs, never from a threshold on
+    a floating-point std: a and b by their Lab bytes (min == max), ab where each of a and b is constant or carries
+    weight 0.  (ab.std() of such a channel is 0 only up to float32 rounding.)  An ab that is constant only because the
+    two transfers cancel (correlation -1 at equal weights) is not covered: that input is ill-conditioned here and in
+    the kernel alike.  With no constant channel the result is bit-identical to the plain formula."""
     a, b, m = bgr_to_lab(a), bgr_to_lab(b), bgr_to_lab(min_error)
     t_mean = np.ones([3], np.float32) * T_MEAN
     t_std = np.ones([3], np.float32) * T_STD
-    A = _transform(a, a.mean(axis=(0, 1)), a.std(axis=(0, 1)), t_mean, t_std)
-    B = _transform(b, b.mean(axis=(0, 1)), b.std(axis=(0, 1)), t_mean, t_std)
+    ca, cb = constant_channels(a), constant_channels(b)
+    cab = (ca | (weight1 == 0)) & (cb | (weight2 == 0))
+    A = _transform(a, a.mean(axis=(0, 1)), a.std(axis=(0, 1)), t_mean, t_std, ca)
+    B = _transform(b, b.mean(axis=(0, 1)), b.std(axis=(0, 1)), t_mean, t_std, cb)
     ab = (A * weight1 + B * weight2 - T_MEAN) / 0.5 + T_MEAN
-    ab = _transform(ab, ab.mean(axis=(0, 1)), ab.std(axis=(0, 1)), m.mean(axis=(0, 1)), m.std(axis=(0, 1)))
-    return np.clip(np.round(ab), 0, 255).astype(np.uint8)
+    return _transform(ab, ab.mean(axis=(0, 1)), ab.std(axis=(0, 1)), m.mean(axis=(0, 1)), m.std(axis=(0, 1)), cab)
 
 
 def histogram_blend(a, b, min_error, weight1=0.5, weight2=0.5):

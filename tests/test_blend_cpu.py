@@ -55,6 +55,78 @@ def test_model_reproduces_golden():
         assert np.array_equal(res["hist_lab"], g["hist_lab"]), name
 
 
+def _plain_histogram_blend_lab(a, b, min_error, weight1, weight2):
+    """histogram_blend.blend as the model stated it before the zero-std rule: no constant channel is looked for"""
+    a, b, m = M.bgr_to_lab(a), M.bgr_to_lab(b), M.bgr_to_lab(min_error)
+    t_mean = np.ones([3], np.float32) * M.T_MEAN
+    t_std = np.ones([3], np.float32) * M.T_STD
+
+    def tr(img, means, stds, tm, ts):
+        return (img.astype(np.float32) - means.reshape(1, 1, 3)) * ts.reshape(1, 1, 3) / stds.reshape(1, 1, 3) + \
+            tm.reshape(1, 1, 3)
+
+    A = tr(a, a.mean(axis=(0, 1)), a.std(axis=(0, 1)), t_mean, t_std)
+    B_ = tr(b, b.mean(axis=(0, 1)), b.std(axis=(0, 1)), t_mean, t_std)
+    ab = (A * weight1 + B_ * weight2 - M.T_MEAN) / 0.5 + M.T_MEAN
+    return tr(ab, ab.mean(axis=(0, 1)), ab.std(axis=(0, 1)), m.mean(axis=(0, 1)), m.std(axis=(0, 1)))
+
+
+def test_zero_std_rule_leaves_other_inputs_bit_identical():
+    """no golden case has a constant channel, and there the model's values equal the plain formula's in every bit"""
+    for name, case, g, res in golden_frames():
+        me = M.min_error_image(case["oa"], case["ob"], res["mask"])
+        for w in ((1 - case["weight1"], case["weight1"]), (0.7, 0.6)):
+            if 0.0 in w:
+                continue  # a weight of 0 with no constant channel: covered below, ab varies through the other image
+            got = M.histogram_blend_values(case["oa"], case["ob"], me, *w)
+            want = _plain_histogram_blend_lab(case["oa"], case["ob"], me, *w)
+            assert got.dtype == want.dtype and np.array_equal(got, want), (name, w)
+    case = G.cases()["odd"]
+    me = M.min_error_image(case["oa"], case["ob"], case["prev_mask"])
+    for w in ((1.0, 0.0), (0.0, 1.0)):
+        assert np.array_equal(M.histogram_blend_values(case["oa"], case["ob"], me, *w),
+                              _plain_histogram_blend_lab(case["oa"], case["ob"], me, *w)), w
+
+
+def test_zero_std_rule_on_constant_channels():
+    """a channel with std 0 transfers to the target mean, without a division by zero (numpy warnings are errors here)"""
+    import warnings
+    case = G.cases()["odd"]
+    oa, ob, mask = case["oa"], case["ob"], case["prev_mask"]
+    g_a, g_b = np.repeat(oa[..., 1:2], 3, -1), np.repeat(ob[..., 1:2], 3, -1)
+    flat = np.ascontiguousarray(np.broadcast_to(np.asarray((40, 120, 200), np.uint8), oa.shape))
+    assert M.constant_channels(M.bgr_to_lab(g_a)).tolist() == [False, True, True]
+    assert M.constant_channels(M.bgr_to_lab(flat)).tolist() == [True, True, True]
+    assert not M.constant_channels(M.bgr_to_lab(oa)).any()
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        # grey + grey: a and b of the blend are the min-error image's mean, 128; L is what the plain formula gives
+        me = M.min_error_image(g_a, g_b, mask)
+        lab = M.histogram_blend_lab(g_a, g_b, me, 0.6, 0.4)
+        assert (lab[..., 1:] == 128).all()
+        with np.errstate(all="ignore"):
+            plain = _plain_histogram_blend_lab(g_a, g_b, me, 0.6, 0.4)
+        assert np.array_equal(M.histogram_blend_values(g_a, g_b, me, 0.6, 0.4)[..., 0], plain[..., 0])
+        # grey + colour: a's a / b channels sit at 128 after the first transfer, so the blend follows b alone and equals
+        # the transfer of b onto the min-error statistics
+        me = M.min_error_image(g_a, ob, mask)
+        got = M.histogram_blend_values(g_a, ob, me, 0.6, 0.4)
+        only_b = M.histogram_blend_values(ob, ob, me, 0.0, 1.0)
+        assert np.abs(got[..., 1:] - only_b[..., 1:]).max() < 1e-3
+        # flat + texture: weight 0 on the texture leaves a constant blend -> the min-error mean in every value
+        me = M.min_error_image(flat, ob, mask)
+        lab_me = M.bgr_to_lab(me)
+        v = M.histogram_blend_values(flat, ob, me, 1.0, 0.0)
+        assert np.array_equal(v, np.broadcast_to(lab_me.mean(axis=(0, 1)), v.shape))
+        # weight on the texture: the blend follows it in all three channels
+        v = M.histogram_blend_values(flat, ob, me, 0.6, 0.4)
+        assert np.abs(v - M.histogram_blend_values(ob, ob, me, 0.0, 1.0)).max() < 1e-3
+        # equal images: correlation 1, the blend returns Lab(oa)
+        assert np.array_equal(M.histogram_blend_lab(oa, oa, oa, 0.6, 0.4), M.bgr_to_lab(oa))
+        res = M.blend_frame(g_a, g_b, case["d1"], case["d2"], 0.4, mask, case["flow"])
+        assert (res["poisson_lab"][..., 1:] == 128).all() and np.isfinite(res["image"].astype(float)).all()
+
+
 def test_dct_solve_equals_lsqr_on_golden():
     """The exact DCT solve against the reference-shaped lsqr (the golden) within the Poisson bars; before truncation
     the two agree to far below a grey level."""
