@@ -30,7 +30,8 @@
 //     (global_load_lds_dwordx4, linear 1 KiB copies) into a 4-slot LDS ring, three steps ahead, behind counted
 //     vmcnt waits and that ONE barrier per step;
 //   * K fragments are read under the PV MFMAs, V^T fragments under the softmax: no MFMA waits on LDS;
-//   * two query blocks per wave at D <= 48: every fragment read feeds two MFMAs;
+//   * two query blocks per wave at D <= 48, and at D = 80 with the loop in half tiles (flash_body_halves): every
+//     fragment read feeds two MFMAs;
 //   * the common case (no diagonal bias, scale folded, >= 3 tiles ahead) is an instantiation of its own without
 //     the scalar branches of the rare passes (a taken branch costs an instruction-fetch bubble).
 // The softmax bookkeeping rides in the MFMAs wherever the head dim leaves room: a ones ROW in V^T makes the
@@ -352,26 +353,73 @@ __device__ __forceinline__ void ring_wait_barrier() {
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
+// ---- epilogue: normalise, store O[q][h*D + d]  (row0 = b * Lq; l_run is read only where V^T has no ones row)
 template <int D, int QB>
-__global__ __launch_bounds__(512, 2) void attn_flash_kernel(const half_t* __restrict__ q,
-                                                          const char* __restrict__ img,
-                                                          const float* __restrict__ ktmax,
-                                                          half_t* __restrict__ out, int B, int H, int Lq,
-                                                          int M, int nT, int batch_per_group,
-                                                          float scale_log2, float diag_bias_log2, int64_t q_ld) {
+__device__ __forceinline__ void flash_store(const floatx16 (&o)[QB][AttnCfg<D>::NDB], const float (&l_run)[QB],
+                                            half_t* __restrict__ out, int64_t row0, int Lq, int C, int h, int qrow0,
+                                            int l31, int hi) {
+    using Cfg = AttnCfg<D>;
+#pragma unroll
+    for (int j = 0; j < QB; ++j) {
+        float l_tot;
+        if (Cfg::ONES) {
+            // O^T row D: C-tile row rr = D % 32 lives in register (rr&3) + 4*(rr>>3) of lanes with hi = (rr>>2)&1
+            constexpr int rr = D % 32;
+            l_tot = __shfl(o[j][D / 32][(rr & 3) + 4 * (rr >> 3)], l31 + 32 * ((rr >> 2) & 1), 64);
+        } else {
+            l_tot = l_run[j] + __shfl_xor(l_run[j], 32, 64);
+        }
+        const float inv = 1.f / l_tot;
+        const int qr = qrow0 + 32 * j;
+        // A row's 8-column groups sit split over the two half-waves (lane l31: columns 8k .. 8k+3, lane
+        // l31 + 32: 8k+4 .. 8k+7).  One v_permlane32_swap per dword of a PAIR of groups leaves lanes 0-31 with the 16
+        // contiguous bytes of group k and lanes 32-63 with those of group k+1: one 16-byte store per pair instead of
+        // two 8-byte ones (the store tail of a row-per-lane epilogue is bound by store instructions, not bytes).
+        {
+            half_t* op = out + (row0 + (qr < Lq ? qr : 0)) * C + h * D;
+#pragma unroll
+            for (int db = 0; db < Cfg::NDB; ++db)
+#pragma unroll
+                for (int gp = 0; gp < 2; ++gp) {
+                    const int dA = db * 32 + gp * 16;  // first column of the pair
+                    if (dA >= D) continue;
+                    half4_t wa, wb;
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        wa[jj] = (half_t)(o[j][db][(2 * gp) * 4 + jj] * inv);
+                        wb[jj] = (half_t)(o[j][db][(2 * gp + 1) * 4 + jj] * inv);
+                    }
+                    if (dA + 8 < D) {
+                        const u32x2 a = __builtin_bit_cast(u32x2, wa), bb = __builtin_bit_cast(u32x2, wb);
+                        const auto s0 = __builtin_amdgcn_permlane32_swap(a[0], bb[0], false, false);
+                        const auto s1 = __builtin_amdgcn_permlane32_swap(a[1], bb[1], false, false);
+                        u32x4 st;
+                        st[0] = s0[0]; st[1] = s1[0]; st[2] = s0[1]; st[3] = s1[1];
+                        if (qr < Lq) *reinterpret_cast<u32x4*>(op + dA + hi * 8) = st;
+                    } else if (qr < Lq) {  // a lone 8-column group (D % 16 == 8): the two 8-byte halves as before
+                        *reinterpret_cast<half4_t*>(op + dA + hi * 4) = wa;
+                    }
+                }
+        }
+    }
+}
+
+// <D, QB> pairs that run flash_body_halves (below) instead of flash_body
+template <int D, int QB>
+struct FlashHalves : std::integral_constant<bool, D == 80 && QB == 2> {};
+
+// The body of one workgroup: head h, batch row b, query rows [qblk * 256 QB, (qblk + 1) * 256 QB).
+template <int D, int QB>
+__device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const char* __restrict__ img,
+                                           const float* __restrict__ ktmax, half_t* __restrict__ out, int H, int Lq,
+                                           int M, int nT, int batch_per_group, float scale_log2,
+                                           float diag_bias_log2, int64_t q_ld, int h, int qblk, int b, int tid) {
     using Cfg = AttnCfg<D>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int ROWS = 256 * QB;  // query rows per workgroup
-
-    const int nQblk = (Lq + ROWS - 1) / ROWS;
-    const unsigned blk = blockIdx.x;
-    const int h = blk % H;
-    const int qblk = (blk / H) % nQblk;
-    const int b = blk / (H * nQblk);
     const int g = b / batch_per_group;
     const int C = H * D;
 
-    const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hi = lane >> 5;
     const int qrow0 = qblk * ROWS + wave * 32 * QB + l31;  // row of query block 0; block j: + 32*j
@@ -718,50 +766,412 @@ __global__ __launch_bounds__(512, 2) void attn_flash_kernel(const half_t* __rest
         step(u, yes, no);
     }
 
-    // ---- epilogue: normalise, store O[q][h*D + d] -------------------------------------------------
+    flash_store<D, QB>(o, l_run, out, (int64_t)b * Lq, Lq, C, h, qrow0, l31, hi);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Two query blocks per wave where a whole tile's fragments no longer fit beside them (D = 80: O alone is 96 registers).
+// flash_body holds a 64-key tile per step: S 32 QB, P 16 QB, V^T 48, K 40 -- at QB = 2 that is past 256.  Here the
+// loop runs in HALF tiles of 32 keys with the same phase structure and the same ping-pong:
+//     phase (u, f):  [V^T fragments of keys 32 f .. 32 f + 31 of tile u | exp, pack S -> P]  barrier (group A; B has it in front)
+//                    [K fragments of the NEXT 32 keys | O^T += V^T P^T (2 k-steps), S^T of the next 32 keys]
+// so S is 32 registers, P 16 (packed into S's), the fragments of a phase 24 + 20, every fragment feeds two MFMAs, and a
+// 512-row workgroup makes the up_blocks.2 launch one round of 256.  With O 96, Q 40 and the two -m_run splats that hipcc
+// keeps as the C operands of the QK chains (32: no v_mov per tile) the kernel is at 251 registers, nothing in scratch.  Key order and k-step order of both products are flash_body's: per output
+// element the accumulation order is the same, and on operands that take this path the result is bit-equal to <D, 1>'s.
+//
+// Ring: packs are the same (K(p) || V^T(p - 1)).  Phase (u, 0) reads K of tile u's second half from pack u, one pack
+// behind the one the step reads, so pack u's slot is refilled (pack u + 4) after barrier (u, 1) instead of barrier u:
+// by then both groups are through the MFMA block of phase (u, 0).  Barrier (u, 0) keeps the counted wait (pack u + 2
+// landed), 2.5 steps ahead of its first reader.
+//
+// Only the common case lives here: scale folded, no max search after tile 0, no diagonal bias, two tiles or more.  The
+// rare passes would need `negm` (32 registers) and their branches in this body, so the WORKGROUP votes after tile 0's
+// scores: all eight waves common-case -> this body; otherwise flash_body<D, 1> runs once per 256-row half over the same
+// ring (a workgroup-level choice: all waves share one staging protocol).  The last tile (padded keys, and the max
+// looked at again as flash_body does) is handled as a whole tile: Q is dead by then and S of both halves fits.
+// ---------------------------------------------------------------------------------------------
+// Cross-lane reads without a lane-index register (__shfl_xor keeps one per distance; flash_body_halves has none to
+// spare and would share them with the flash_body it falls back to): the value of lane (l ^ X), X < 32, by ds_swizzle,
+// and that of lane (l ^ 32) by v_permlane32_swap (both_halves).
+template <int X>
+__device__ __forceinline__ float lane_xor(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (X << 10) | 0x1f));
+}
+// a, b = this lane's value and lane (l ^ 32)'s, in either order
+__device__ __forceinline__ void both_halves(float v, float& a, float& b) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    a = __builtin_bit_cast(float, (unsigned)sw[0]);
+    b = __builtin_bit_cast(float, (unsigned)sw[1]);
+}
+
+template <int D>
+__device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, const char* __restrict__ img,
+                                                  const float* __restrict__ ktmax, half_t* __restrict__ out, int H,
+                                                  int Lq, int M, int nT, int batch_per_group, float scale_log2,
+                                                  float diag_bias_log2, int64_t q_ld, int h, int qblk, int b) {
+    using Cfg = AttnCfg<D>;
+    static_assert(!Cfg::MCOL && Cfg::ONES, "head dims with a spare V^T row and no spare K column (D = 80)");
+    constexpr int NKS = Cfg::NKS, NDB = Cfg::NDB;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int g = b / batch_per_group;
+    const int C = H * D;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int l31 = lane & 31, hi = lane >> 5;
+    const int qrow0 = qblk * 512 + wave * 64 + l31;  // row of query block 0; block 1: + 32
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);
+    const int grpB = wave_s >= 4 ? 1 : 0;
+
+    // Q fragments, scaled as if folded (a wave that may not fold sends the workgroup to flash_body, which reloads them)
+    half8_t qf[2][NKS];
+    float q2[2];
 #pragma unroll
-    for (int j = 0; j < QB; ++j) {
-        float l_tot;
-        if (Cfg::ONES) {
-            // O^T row D: C-tile row rr = D % 32 lives in register (rr&3) + 4*(rr>>3) of lanes with hi = (rr>>2)&1
-            constexpr int rr = D % 32;
-            l_tot = __shfl(o[j][D / 32][(rr & 3) + 4 * (rr >> 3)], l31 + 32 * ((rr >> 2) & 1), 64);
-        } else {
-            l_tot = l_run[j] + __shfl_xor(l_run[j], 32, 64);
-        }
-        const float inv = 1.f / l_tot;
+    for (int j = 0; j < 2; ++j) {
         const int qr = qrow0 + 32 * j;
-        // A row's 8-column groups sit split over the two half-waves (lane l31: columns 8k .. 8k+3, lane
-        // l31 + 32: 8k+4 .. 8k+7).  One v_permlane32_swap per dword of a PAIR of groups leaves lanes 0-31 with the 16
-        // contiguous bytes of group k and lanes 32-63 with those of group k+1: one 16-byte store per pair instead of
-        // two 8-byte ones (the store tail of a row-per-lane epilogue is bound by store instructions, not bytes).
-        {
-            half_t* op = out + ((int64_t)b * Lq + (qr < Lq ? qr : 0)) * C + h * D;
+        const half_t* qp = q + ((int64_t)b * Lq + (qr < Lq ? qr : Lq - 1)) * q_ld + h * D;
+        q2[j] = 0.f;
 #pragma unroll
-            for (int db = 0; db < Cfg::NDB; ++db)
+        for (int ks = 0; ks < NKS; ++ks) {
+            const half8_t t = *reinterpret_cast<const half8_t*>(qp + ks * 16 + hi * 8);
 #pragma unroll
-                for (int gp = 0; gp < 2; ++gp) {
-                    const int dA = db * 32 + gp * 16;  // first column of the pair
-                    if (dA >= D) continue;
-                    half4_t wa, wb;
+            for (int e = 0; e < 8; ++e) q2[j] = fmaf((float)t[e], (float)t[e], q2[j]);
 #pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        wa[jj] = (half_t)(o[j][db][(2 * gp) * 4 + jj] * inv);
-                        wb[jj] = (half_t)(o[j][db][(2 * gp + 1) * 4 + jj] * inv);
-                    }
-                    if (dA + 8 < D) {
-                        const u32x2 a = __builtin_bit_cast(u32x2, wa), bb = __builtin_bit_cast(u32x2, wb);
-                        const auto s0 = __builtin_amdgcn_permlane32_swap(a[0], bb[0], false, false);
-                        const auto s1 = __builtin_amdgcn_permlane32_swap(a[1], bb[1], false, false);
-                        u32x4 st;
-                        st[0] = s0[0]; st[1] = s1[0]; st[2] = s0[1]; st[3] = s1[1];
-                        if (qr < Lq) *reinterpret_cast<u32x4*>(op + dA + hi * 8) = st;
-                    } else if (qr < Lq) {  // a lone 8-column group (D % 16 == 8): the two 8-byte halves as before
-                        *reinterpret_cast<half4_t*>(op + dA + hi * 4) = wa;
-                    }
-                }
+            for (int e = 0; e < 8; ++e) qf[j][ks][e] = (half_t)((float)t[e] * scale_log2);
+        }
+        float qa, qb;
+        both_halves(q2[j], qa, qb);
+        q2[j] = qa + qb;
+    }
+    float kmax;
+    {
+        const float* km = ktmax + (int64_t)(g * H + h) * nT;
+        float k2 = 0.f;
+        for (int i = lane; i < nT; i += 64) k2 = fmaxf(k2, km[i]);
+        k2 = fmaxf(k2, lane_xor<16>(k2));
+        k2 = fmaxf(k2, lane_xor<8>(k2));
+        k2 = fmaxf(k2, lane_xor<4>(k2));
+        k2 = fmaxf(k2, lane_xor<2>(k2));
+        k2 = fmaxf(k2, lane_xor<1>(k2));
+        float ka, kb;
+        both_halves(k2, ka, kb);
+        kmax = sqrtf(fmaxf(ka, kb));
+    }
+    bool common = diag_bias_log2 == 0.f && nT >= 2;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) common = common && (scale_log2 * sqrtf(q2[j]) * kmax <= FOLD_MAX);
+
+    // ---- staging (flash_body's: DMA pieces of 1 KiB, wave w issues pieces w, w + 8, ...)
+    constexpr int NPW_LO = Cfg::NP / 8, NPW_HI = (Cfg::NP + 7) / 8, NREM = Cfg::NP % 8;
+    const int many = wave_s < NREM ? 1 : 0;
+    const uint32_t lds0 =
+        __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
+    const char* src = img + (int64_t)(g * H + h) * (nT + 1) * Cfg::TILE;
+    const uint32_t lane_off = (wave * 64 + lane) * 16;
+    auto stage = [&](int p, int slot) __attribute__((always_inline)) {
+        const char* sp = src + (int64_t)p * Cfg::TILE;
+        const uint32_t dstb = lds0 + slot * Cfg::TILE + wave_s * 1024;
+#pragma unroll
+        for (int i = 0; i < NPW_HI; ++i) {
+            if (i < NPW_LO || many) {
+                const uint32_t m0v = dstb + i * 8192;
+                asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane_off), "s"(sp), "s"(m0v)
+                             : "memory");
+                sp += 8192;
+            }
+        }
+    };
+    auto wait_barrier = [&](int keep) __attribute__((always_inline)) {
+        if (keep == 0) {
+            ring_wait_barrier<0>();
+        } else if (many) {
+            if (keep == 1) ring_wait_barrier<NPW_HI>(); else ring_wait_barrier<2 * NPW_HI>();
+        } else {
+            if (keep == 1) ring_wait_barrier<NPW_LO>(); else ring_wait_barrier<2 * NPW_LO>();
+        }
+    };
+
+    const int koff = (hi * 64 + l31) * 16;
+    const int voff = Cfg::KTILE + (hi * Cfg::DPV + l31) * 16;
+    floatx16 s[2];  // S^T of the 32 keys whose softmax comes next
+    // S^T of keys 32 f .. 32 f + 31 of the tile whose K sits in `slot`; the chains start at c0 / c1
+    auto qk_half = [&](floatx16 (&acc)[2], int slot, int f, float c0, float c1) __attribute__((always_inline)) {
+        half8_t kf[NKS];
+        const char* kb_ = smem + slot * Cfg::TILE + koff + f * 512;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) kf[ks] = *reinterpret_cast<const half8_t*>(kb_ + ks * 2048);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            acc[0][r] = c0;
+            acc[1][r] = c1;
+        }
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[j][ks], acc[j], 0, 0, 0);
+    };
+
+    // ---- prologue: packs 0 .. 3 in flight, packs 0 and 1 landed; tile 0's row max (flash_body's anchor of m_run) from
+    // both halves of its scores, the first half's kept in `s`
+    stage(0, 3);
+    stage(1, 0);
+    if (nT > 1) stage(2, 1);
+    if (nT > 2) stage(3, 2);
+    wait_barrier(nT > 2 ? 2 : (nT > 1 ? 1 : 0));
+    float m_run[2];
+    {
+        floatx16 t[2];
+        qk_half(t, 3, 1, 0.f, 0.f);
+        qk_half(s, 3, 0, 0.f, 0.f);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float mt = fmaxf(s[j][0], t[j][0]);
+#pragma unroll
+            for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[j][r]), t[j][r]);
+            const unsigned mb = __builtin_bit_cast(unsigned, mt);
+            const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
+            m_run[j] = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
+            // flash_body's nomax test (folded: accumulator units are exponent units)
+            common = common && (scale_log2 * sqrtf(q2[j]) * kmax * 1.001f + 1e-3f - m_run[j] <= NOMAX_THR);
         }
     }
+    __builtin_amdgcn_sched_barrier(0);
+
+    // ---- the vote
+    {
+        int* votes = reinterpret_cast<int*>(smem + Cfg::LDS_BYTES);
+        const int mine = __builtin_amdgcn_readfirstlane((int)__all(common));
+        if (lane == 0) votes[wave] = mine;
+        __syncthreads();
+        int all = 1;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) all &= votes[w];
+        if (__builtin_amdgcn_readfirstlane(all) == 0) {
+#pragma nounroll
+            for (int half = 0; half < 2; ++half) {
+                ring_wait_barrier<0>();  // the ring is idle: every pack in flight has landed, nobody reads
+                // (thread and block indices go in through empty asm: otherwise hipcc shares flash_body's index arithmetic
+                // with the code above and carries it, in scratch, through the half-tile loop)
+                int tid_ = tid, h_ = h, qb_ = qblk * 2 + half, b_ = b;
+                asm volatile("" : "+v"(tid_), "+s"(h_), "+s"(qb_), "+s"(b_));
+                if (qb_ * 256 < Lq)
+                    flash_body<D, 1>(q, img, ktmax, out, H, Lq, M, nT, batch_per_group, scale_log2, diag_bias_log2, q_ld,
+                                     h_, qb_, b_, tid_);
+            }
+            return;
+        }
+    }
+
+    floatx16 o[2][NDB];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int db = 0; db < NDB; ++db)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[j][db][r] = 0.f;
+
+    // Phase (u, F).  FIRST = tile 0: its scores were accumulated from zero and the anchor is subtracted afterwards, as
+    // flash_body's search pass does on tile 0 (later tiles start their chains at -m_run).  FULL: (u + 3 < nT), the ring
+    // handling is unconditional.
+    auto phase = [&](int u, auto f_c, auto first_c, auto full_c) __attribute__((always_inline)) {
+        constexpr int F = decltype(f_c)::value;
+        constexpr bool FIRST = decltype(first_c)::value;
+        constexpr bool FULL = decltype(full_c)::value;
+        const int slot = u & 3;
+        auto ring_sync = [&]() __attribute__((always_inline)) {
+            if (F == 0) {  // pack u + 2 (step u + 1) has landed for everyone
+                if (FULL) ring_wait_barrier<NPW_LO>(); else wait_barrier(u + 2 < nT ? 1 : 0);
+            } else {       // everyone is through phase (u, 0): pack u's slot takes pack u + 4
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                if (FULL || u + 3 < nT) stage(u + 4, (u + 3) & 3);
+            }
+        };
+        if (grpB) ring_sync();
+        __builtin_amdgcn_sched_barrier(0);
+
+        // ---- V^T fragments of the phase's two k-steps, in flight under the softmax
+        half8_t vf[2][NDB];
+        {
+            const char* vb_ = smem + slot * Cfg::TILE + voff + F * (4 * Cfg::DPV * 16);
+#pragma unroll
+            for (int kc = 0; kc < 2; ++kc)
+#pragma unroll
+                for (int db = 0; db < NDB; ++db)
+                    vf[kc][db] = *reinterpret_cast<const half8_t*>(vb_ + (kc * 2 * Cfg::DPV + db * 32) * 16);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+
+        half8_t pf[2][2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (FIRST) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[j][r] -= m_run[j];
+            }
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const float p0 = __builtin_amdgcn_exp2f(s[j][r]);
+                const float p1 = __builtin_amdgcn_exp2f(s[j][r + 1]);
+                pf[j][r >> 3][r & 7] = (half_t)p0;
+                pf[j][r >> 3][(r & 7) + 1] = (half_t)p1;
+            }
+            // (pins the exponentials in front of group A's barrier, as in flash_body)
+#pragma unroll
+            for (int kc = 0; kc < 2; ++kc) asm volatile("" : "+v"(pf[j][kc]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+
+        if (!grpB) ring_sync();
+        __builtin_amdgcn_sched_barrier(0);
+
+        // ---- K fragments of the next 32 keys (second half of tile u: pack u; first half of tile u + 1: this pack)
+        half8_t kf[NKS];
+        {
+            const char* kb_ = smem + (F == 0 ? ((u + 3) & 3) * Cfg::TILE + 512 : slot * Cfg::TILE) + koff;
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) kf[ks] = *reinterpret_cast<const half8_t*>(kb_ + ks * 2048);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+
+        __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int kc = 0; kc < 2; ++kc)
+#pragma unroll
+            for (int db = 0; db < NDB; ++db)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    o[j][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[kc][db], pf[j][kc], o[j][db], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[j][r] = (FIRST && F == 0) ? 0.f : -m_run[j];
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                s[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[j][ks], s[j], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    const std::integral_constant<int, 0> f0;
+    const std::integral_constant<int, 1> f1;
+    const std::integral_constant<bool, true> yes;
+    const std::integral_constant<bool, false> no;
+    phase(0, f0, yes, no);
+    phase(0, f1, yes, no);
+    int u = 1;
+    for (; u + 3 < nT; ++u) {
+        phase(u, f0, no, yes);
+        phase(u, f1, no, yes);
+    }
+    for (; u < nT - 1; ++u) {
+        phase(u, f0, no, no);
+        phase(u, f1, no, no);
+    }
+
+    // ---- the last tile, whole: padded keys masked, the max looked at (flash_body's fix and search passes)
+    // (what only the last tile and the epilogue need of the lane's indices is derived again from here on, not carried in
+    // registers through the loop above, which has none to spare)
+    int tid2 = threadIdx.x;
+    asm volatile("" : "+v"(tid2));
+    const int l31e = tid2 & 31, hie = (tid2 >> 5) & 1;
+    {
+        const int slot = u & 3;
+        if (grpB) ring_wait_barrier<0>();
+        __builtin_amdgcn_sched_barrier(0);
+        floatx16 s1[2];  // the tile's second half (its K: pack u)
+        qk_half(s1, (u + 3) & 3, 1, -m_run[0], -m_run[1]);
+        __builtin_amdgcn_sched_barrier(0);
+        half8_t pf[2][4];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            int kbase = u * 64 + 4 * hie;
+            asm volatile("" : "+v"(kbase));
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key0 = kbase + (r & 3) + 8 * (r >> 2);
+                if (key0 >= M) s[j][r] = -1e30f;
+                if (key0 + 32 >= M) s1[j][r] = -1e30f;
+            }
+            float mt = fmaxf(s[j][0], s1[j][0]);
+#pragma unroll
+            for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[j][r]), s1[j][r]);
+            {
+                const unsigned mb = __builtin_bit_cast(unsigned, mt);
+                const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
+                mt = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
+            }
+            if (__builtin_amdgcn_readfirstlane((int)__any(mt > RESCALE_THR)) != 0) {
+                const float delta = fmaxf(mt, 0.f);
+                const float alpha = __builtin_amdgcn_exp2f(-delta);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    s[j][r] -= delta;
+                    s1[j][r] -= delta;
+                }
+#pragma unroll
+                for (int db = 0; db < NDB; ++db)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) o[j][db][r] *= alpha;
+            }
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const float p0 = __builtin_amdgcn_exp2f(s[j][r]);
+                const float p1 = __builtin_amdgcn_exp2f(s[j][r + 1]);
+                const float p2 = __builtin_amdgcn_exp2f(s1[j][r]);
+                const float p3 = __builtin_amdgcn_exp2f(s1[j][r + 1]);
+                pf[j][r >> 3][r & 7] = (half_t)p0;
+                pf[j][r >> 3][(r & 7) + 1] = (half_t)p1;
+                pf[j][2 + (r >> 3)][r & 7] = (half_t)p2;
+                pf[j][2 + (r >> 3)][(r & 7) + 1] = (half_t)p3;
+            }
+#pragma unroll
+            for (int kc = 0; kc < 4; ++kc) asm volatile("" : "+v"(pf[j][kc]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (!grpB) ring_wait_barrier<0>();
+        __builtin_amdgcn_sched_barrier(0);
+        const char* vb_ = smem + slot * Cfg::TILE + voff;
+#pragma unroll
+        for (int kc = 0; kc < 4; ++kc) {
+            half8_t vf[NDB];
+#pragma unroll
+            for (int db = 0; db < NDB; ++db)
+                vf[db] = *reinterpret_cast<const half8_t*>(vb_ + (kc * 2 * Cfg::DPV + db * 32) * 16);
+#pragma unroll
+            for (int db = 0; db < NDB; ++db)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    o[j][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[db], pf[j][kc], o[j][db], 0, 0, 0);
+        }
+    }
+
+    const float no_l[2] = {0.f, 0.f};  // (the row sum is O^T row D)
+    flash_store<D, 2>(o, no_l, out, (int64_t)b * Lq, Lq, C, h, qblk * 512 + (tid2 >> 6) * 64 + l31e, l31e, hie);
+}
+
+template <int D, int QB>
+__global__ __launch_bounds__(512, 2) void attn_flash_kernel(const half_t* __restrict__ q,
+                                                          const char* __restrict__ img,
+                                                          const float* __restrict__ ktmax,
+                                                          half_t* __restrict__ out, int B, int H, int Lq,
+                                                          int M, int nT, int batch_per_group,
+                                                          float scale_log2, float diag_bias_log2, int64_t q_ld) {
+    const int nQblk = (Lq + 256 * QB - 1) / (256 * QB);
+    const unsigned blk = blockIdx.x;
+    const int h = blk % H;
+    const int qblk = (blk / H) % nQblk;
+    const int b = blk / (H * nQblk);
+    if constexpr (FlashHalves<D, QB>::value)
+        flash_body_halves<D>(q, img, ktmax, out, H, Lq, M, nT, batch_per_group, scale_log2, diag_bias_log2, q_ld, h, qblk, b);
+    else
+        flash_body<D, QB>(q, img, ktmax, out, H, Lq, M, nT, batch_per_group, scale_log2, diag_bias_log2, q_ld, h, qblk, b,
+                          threadIdx.x);
 }
 
 template <int D, int QB>
@@ -769,14 +1179,36 @@ static int launch_flash(const half_t* q, const char* img, half_t* out, int B, in
                         int n_groups, float scale, float diag_bias, int64_t q_ld, const float* ktmax,
                         hipStream_t st) {
     using Cfg = AttnCfg<D>;
-    if (int rc = allow_dyn_lds(&attn_flash_kernel<D, QB>, Cfg::LDS_BYTES)) return rc;
+    constexpr int lds = Cfg::LDS_BYTES + (FlashHalves<D, QB>::value ? 64 : 0);  // + the eight waves' votes
+    if (int rc = allow_dyn_lds(&attn_flash_kernel<D, QB>, lds)) return rc;
     const int nQblk = (Lq + 256 * QB - 1) / (256 * QB);
     const float log2e = 1.4426950408889634f;
     ProfScope ps(FRESCO_PROF_ATTN_FLASH, B * H, Lq, M, D, st);
     const int grid = H * nQblk * B;
-    hipLaunchKernelGGL((attn_flash_kernel<D, QB>), dim3(grid), dim3(512), Cfg::LDS_BYTES, st, q, img,
+    hipLaunchKernelGGL((attn_flash_kernel<D, QB>), dim3(grid), dim3(512), lds, st, q, img,
                        ktmax, out, B, H, Lq, M, nT, B / n_groups, scale * log2e, diag_bias * log2e, q_ld);
     return check_launch();
+}
+
+// Two query blocks (64 rows) per wave while the accumulators leave room (two waves per SIMD = 256
+// registers each): every K / V^T fragment read from LDS then feeds two (four) MFMAs.  Exception: a launch whose
+// 512-row workgroups would leave CUs idle (a frame shard of a multi-GPU run: 2 batch rows x 8 heads x 8 query blocks
+// = 128 workgroups for 256 CUs) takes 256-row workgroups instead -- twice as many, each half as long.  D = 80 (the
+// half-tile body) follows the same rule, and keeps 256-row workgroups for launches of at most 256 queries.
+template <int D>
+static int launch_flash_auto(const half_t* q, const char* img, half_t* out, int B, int H, int Lq, int M, int nT,
+                             int n_groups, float scale, float diag_bias, int64_t q_ld, const float* ktmax,
+                             hipStream_t st) {
+    using Cfg = AttnCfg<D>;
+    if constexpr ((D <= 48 && Cfg::MCOL) || FlashHalves<D, 2>::value) {
+        const int grid2 = H * ((Lq + 511) / 512) * B;
+        const bool idle = grid2 < device_cus();
+        if (FlashHalves<D, 2>::value ? (idle || Lq <= 256) : (idle && Lq > 256))
+            return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
+        return launch_flash<D, 2>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
+    } else {
+        return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
+    }
 }
 
 template <int D>
@@ -794,18 +1226,7 @@ static int launch_attn(const half_t* q, const half_t* k, const half_t* v, const 
         hipLaunchKernelGGL((kv_pack_kernel<D>), pg, dim3(256), 0, st, k, v, kv_rows, img, ktmax, H, M, nT, group_rows,
                            kv_ld);
     }
-    // Two query blocks (64 rows) per wave while the accumulators leave room (two waves per SIMD = 256
-    // registers each): every K / V^T fragment read from LDS then feeds two (four) MFMAs.  Exception: a launch whose
-    // 512-row workgroups would leave CUs idle (a frame shard of a multi-GPU run: 2 batch rows x 8 heads x 8 query blocks
-    // = 128 workgroups for 256 CUs) takes 256-row workgroups instead -- twice as many, each half as long.
-    if constexpr (D <= 48 && Cfg::MCOL) {
-        const int grid2 = H * ((Lq + 511) / 512) * B;
-        if (Lq > 256 && grid2 < device_cus())
-            return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
-        return launch_flash<D, 2>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
-    } else {
-        return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
-    }
+    return launch_flash_auto<D>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
 }
 
 static size_t attn_ws_bytes(int n_groups, int H, int M, int D) {
@@ -875,14 +1296,7 @@ static int launch_kvproj_attn(const half_t* q, const half_t* x, int64_t x_ld, co
         hipLaunchKernelGGL((kvproj_pack_kernel<KIN, D>), dim3(nT, H * D / 160, n_groups), dim3(320), lds, st, x, x_ld, x_rows,
                            Wk, Wv, img, ktmax, H, M, nT);
     }
-    if constexpr (D <= 48 && Cfg::MCOL) {
-        const int grid2 = H * ((Lq + 511) / 512) * B;
-        if (Lq > 256 && grid2 < device_cus())
-            return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
-        return launch_flash<D, 2>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
-    } else {
-        return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
-    }
+    return launch_flash_auto<D>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
 }
 }  // namespace fresco
 
