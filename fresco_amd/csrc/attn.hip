@@ -27,7 +27,7 @@
 //     barrier therefore releases A's matrix block together with B's softmax block and vice versa, and keeps
 //     them half a step apart for the whole key loop (s_setprio raises the matrix block);
 //   * key packs (K of tile u+1 next to V^T of tile u: exactly what one loop body reads) arrive by DMA
-//     (global_load_lds_dwordx4, linear 1 KiB copies) into a 4-slot LDS ring, three steps ahead, behind counted
+//     (lds_dma.h: linear 1 KiB copies) into a 4-slot LDS ring, three steps ahead, behind counted
 //     vmcnt waits and that ONE barrier per step;
 //   * K fragments are read under the PV MFMAs, V^T fragments under the softmax: no MFMA waits on LDS;
 //   * two query blocks per wave at D <= 48, and at D = 80 with the loop in half tiles (flash_body_halves): every
@@ -43,6 +43,7 @@
 // MFMA 32x32x16 f16 operand layout (gfx950): lane l supplies 8 consecutive k for row/col (l & 31), k-chunk
 // (l >> 5); C/D: col = l & 31, row = (r & 3) + 8*(r >> 2) + 4*(l >> 5), r = 0..15.
 #include "attn_cfg.h"
+#include "lds_dma.h"
 #include <type_traits>
 
 namespace fresco {
@@ -348,10 +349,51 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
 // its own pieces of the pack after next (counted vmcnt) before the barrier, so every fragment read finds its
 // data landed one barrier earlier and no MFMA waits on global memory.
 // ---------------------------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void ring_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
+// a, b = this lane's value and lane (l ^ 32)'s, in either order: v_permlane32_swap (VALU) instead of a ds_bpermute
+// through the LDS pipe (the builtin inserts the wait state the swap needs)
+__device__ __forceinline__ void both_halves(float v, float& a, float& b) {
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    a = __builtin_bit_cast(float, (unsigned)sw[0]);
+    b = __builtin_bit_cast(float, (unsigned)sw[1]);
 }
+// a row maximum over both half-waves: each holds 32 of the query's 64 keys of a tile
+__device__ __forceinline__ float max_both_halves(float v) {
+    float a, b;
+    both_halves(v, a, b);
+    return fmaxf(a, b);
+}
+
+// The pack ring of a workgroup (head h of key group g): a pack IS its LDS image, so it is NP linear 1 KiB copies
+// (lds_dma.h); wave w issues pieces w, w + 8, ... (destination = wave-uniform base + lane * 16, source = scalar base + one
+// per-lane offset).  Ordering is by the counted waits + barrier of the bodies' `ring_sync`.
+template <int D>
+struct PackRing {
+    using Cfg = AttnCfg<D>;
+    static constexpr int NPW_LO = Cfg::NP / 8, NPW_HI = (Cfg::NP + 7) / 8, NREM = Cfg::NP % 8;
+    const int wave_s;
+    const int many;  // this wave issues NPW_HI pieces per pack (else NPW_LO)
+    const uint32_t lds0;
+    const char* const src;
+    const uint32_t lane_off;
+    __device__ __forceinline__ PackRing(const char* img, int g, int H, int h, int nT, const char* smem, int wave_s_,
+                                        int tid)
+        : wave_s(wave_s_), many(wave_s_ < NREM ? 1 : 0), lds0(lds_addr(smem)),
+          src(img + (int64_t)(g * H + h) * (nT + 1) * Cfg::TILE), lane_off(tid * 16) {}
+    __device__ __forceinline__ void stage(int p, int slot) const {  // pack p -> ring slot
+        const char* sp = src + (int64_t)p * Cfg::TILE;
+        const uint32_t dstb = lds0 + slot * Cfg::TILE + wave_s * 1024;
+#pragma unroll
+        for (int i = 0; i < NPW_HI; ++i) {
+            if (i < NPW_LO || many) {
+                lds_dma16(lane_off, sp, dstb + i * 8192);
+                sp += 8192;
+            }
+        }
+    }
+    // wait until at most `keep` of this wave's newest packs are still in flight, then the workgroup barrier
+    __device__ __forceinline__ void wait_barrier(int keep) const { dma_wait_barrier_keep<NPW_LO, NPW_HI>(keep, many); }
+};
 
 // ---- epilogue: normalise, store O[q][h*D + d]  (row0 = b * Lq; l_run is read only where V^T has no ones row)
 template <int D, int QB>
@@ -488,40 +530,8 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
     const float resc_thr = RESCALE_THR / cmul;  // thresholds and the diagonal bias in accumulator units
     const float diag_u = diag_bias_log2 / cmul;
 
-    // ---- staging: global -> LDS by DMA (global_load_lds_dwordx4), no register round trip ---------
-    // A pack IS its LDS image, so it is NP linear 1 KiB copies; wave w issues pieces w, w+8, ...
-    // (destination = wave-uniform M0 base + lane*16, source = scalar base + one per-lane offset).  The DMA
-    // is inline asm on purpose: the compiler must not see these LDS writes, or it would drain vmcnt to zero
-    // in front of every fragment read; ordering is by the counted s_waitcnt + s_barrier of `ring_sync`.
-    constexpr int NPW_LO = Cfg::NP / 8, NPW_HI = (Cfg::NP + 7) / 8, NREM = Cfg::NP % 8;
-    const int many = wave_s < NREM ? 1 : 0;  // this wave issues NPW_HI pieces per pack (else NPW_LO)
-    const uint32_t lds0 =
-        __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
-    const char* src = img + (int64_t)(g * H + h) * (nT + 1) * Cfg::TILE;
-    const uint32_t lane_off = (wave * 64 + lane) * 16;
-    auto stage = [&](int p, int slot) __attribute__((always_inline)) {  // pack p -> ring slot
-        const char* sp = src + (int64_t)p * Cfg::TILE;
-        const uint32_t dstb = lds0 + slot * Cfg::TILE + wave_s * 1024;
-#pragma unroll
-        for (int i = 0; i < NPW_HI; ++i) {
-            if (i < NPW_LO || many) {
-                const uint32_t m0v = dstb + i * 8192;
-                asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane_off), "s"(sp), "s"(m0v)
-                             : "memory");
-                sp += 8192;
-            }
-        }
-    };
-    // wait until at most `keep` of this wave's newest tiles are still in flight, then the workgroup barrier
-    auto wait_barrier = [&](int keep) __attribute__((always_inline)) {
-        if (keep == 0) {
-            ring_wait_barrier<0>();
-        } else if (many) {
-            if (keep == 1) ring_wait_barrier<NPW_HI>(); else ring_wait_barrier<2 * NPW_HI>();
-        } else {
-            if (keep == 1) ring_wait_barrier<NPW_LO>(); else ring_wait_barrier<2 * NPW_LO>();
-        }
-    };
+    // ---- staging: global -> LDS by DMA, no register round trip
+    const PackRing<D> ring(img, g, H, h, nT, smem, wave_s, tid);
 
     floatx16 o[QB][Cfg::NDB];
     // The accumulators must come out as  c*s - m_run  (no per-score subtraction).  MCOL: -m_run rides in Q's
@@ -576,11 +586,11 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
 
     // ---- prologue: packs 0 .. 3 in flight (pack p = step p-1, slot (p+3) & 3), packs 0 and 1 landed,
     // S^T of tile 0 computed
-    stage(0, 3);
-    stage(1, 0);
-    if (nT > 1) stage(2, 1);
-    if (nT > 2) stage(3, 2);
-    wait_barrier(nT > 2 ? 2 : (nT > 1 ? 1 : 0));
+    ring.stage(0, 3);
+    ring.stage(1, 0);
+    if (nT > 1) ring.stage(2, 1);
+    if (nT > 2) ring.stage(3, 2);
+    ring.wait_barrier(nT > 2 ? 2 : (nT > 1 ? 1 : 0));
     {
         half8_t kf[2][Cfg::NKS];
         read_k(kf, 3);
@@ -612,11 +622,11 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
         // barrier u: pack u+2 (step u+1) has landed for everyone; its predecessor's slot takes pack u+4
         auto ring_sync = [&]() __attribute__((always_inline)) {
             if (FAST) {
-                ring_wait_barrier<NPW_LO>();  // (waves with an extra piece per pack wait for one piece more)
-                stage(u + 4, (u + 3) & 3);
+                dma_wait_barrier<PackRing<D>::NPW_LO>();  // (waves with an extra piece per pack wait for one piece more)
+                ring.stage(u + 4, (u + 3) & 3);
             } else {
-                wait_barrier(u + 2 < nT ? 1 : 0);
-                if (u + 3 < nT) stage(u + 4, (u + 3) & 3);
+                ring.wait_barrier(u + 2 < nT ? 1 : 0);
+                if (u + 3 < nT) ring.stage(u + 4, (u + 3) & 3);
             }
         };
         if (grpB) ring_sync();
@@ -658,12 +668,7 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
                 float mt = fmaxf(s[j][0][0], s[j][1][0]);
 #pragma unroll
                 for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[j][0][r]), s[j][1][r]);  // v_max3_f32
-                {   // the other half of the wave holds the query's other 32 keys of the tile: v_permlane32_swap (VALU) instead
-                    // of a ds_bpermute through the LDS pipe (the builtin inserts the wait state the swap needs)
-                    const unsigned mb = __builtin_bit_cast(unsigned, mt);
-                    const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-                    mt = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
-                }
+                mt = max_both_halves(mt);  // the other half of the wave holds the query's other 32 keys of the tile
                 if (u == 0 || __builtin_amdgcn_readfirstlane((int)__any(mt > resc_thr)) != 0) {
                     float delta = (u == 0) ? mt : fmaxf(mt, 0.f);
                     if (Cfg::MCOL) {
@@ -793,17 +798,10 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
 // ---------------------------------------------------------------------------------------------
 // Cross-lane reads without a lane-index register (__shfl_xor keeps one per distance; flash_body_halves has none to
 // spare and would share them with the flash_body it falls back to): the value of lane (l ^ X), X < 32, by ds_swizzle,
-// and that of lane (l ^ 32) by v_permlane32_swap (both_halves).
+// and that of lane (l ^ 32) by v_permlane32_swap (both_halves, above).
 template <int X>
 __device__ __forceinline__ float lane_xor(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (X << 10) | 0x1f));
-}
-// a, b = this lane's value and lane (l ^ 32)'s, in either order
-__device__ __forceinline__ void both_halves(float v, float& a, float& b) {
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    const auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    a = __builtin_bit_cast(float, (unsigned)sw[0]);
-    b = __builtin_bit_cast(float, (unsigned)sw[1]);
 }
 
 template <int D>
@@ -855,43 +853,14 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
         k2 = fmaxf(k2, lane_xor<4>(k2));
         k2 = fmaxf(k2, lane_xor<2>(k2));
         k2 = fmaxf(k2, lane_xor<1>(k2));
-        float ka, kb;
-        both_halves(k2, ka, kb);
-        kmax = sqrtf(fmaxf(ka, kb));
+        kmax = sqrtf(max_both_halves(k2));
     }
     bool common = diag_bias_log2 == 0.f && nT >= 2;
 #pragma unroll
     for (int j = 0; j < 2; ++j) common = common && (scale_log2 * sqrtf(q2[j]) * kmax <= FOLD_MAX);
 
-    // ---- staging (flash_body's: DMA pieces of 1 KiB, wave w issues pieces w, w + 8, ...)
-    constexpr int NPW_LO = Cfg::NP / 8, NPW_HI = (Cfg::NP + 7) / 8, NREM = Cfg::NP % 8;
-    const int many = wave_s < NREM ? 1 : 0;
-    const uint32_t lds0 =
-        __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
-    const char* src = img + (int64_t)(g * H + h) * (nT + 1) * Cfg::TILE;
-    const uint32_t lane_off = (wave * 64 + lane) * 16;
-    auto stage = [&](int p, int slot) __attribute__((always_inline)) {
-        const char* sp = src + (int64_t)p * Cfg::TILE;
-        const uint32_t dstb = lds0 + slot * Cfg::TILE + wave_s * 1024;
-#pragma unroll
-        for (int i = 0; i < NPW_HI; ++i) {
-            if (i < NPW_LO || many) {
-                const uint32_t m0v = dstb + i * 8192;
-                asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(lane_off), "s"(sp), "s"(m0v)
-                             : "memory");
-                sp += 8192;
-            }
-        }
-    };
-    auto wait_barrier = [&](int keep) __attribute__((always_inline)) {
-        if (keep == 0) {
-            ring_wait_barrier<0>();
-        } else if (many) {
-            if (keep == 1) ring_wait_barrier<NPW_HI>(); else ring_wait_barrier<2 * NPW_HI>();
-        } else {
-            if (keep == 1) ring_wait_barrier<NPW_LO>(); else ring_wait_barrier<2 * NPW_LO>();
-        }
-    };
+    // ---- staging (flash_body's; the fallback below constructs its own ring over the same slots)
+    const PackRing<D> ring(img, g, H, h, nT, smem, wave_s, tid);
 
     const int koff = (hi * 64 + l31) * 16;
     const int voff = Cfg::KTILE + (hi * Cfg::DPV + l31) * 16;
@@ -916,11 +885,11 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
 
     // ---- prologue: packs 0 .. 3 in flight, packs 0 and 1 landed; tile 0's row max (flash_body's anchor of m_run) from
     // both halves of its scores, the first half's kept in `s`
-    stage(0, 3);
-    stage(1, 0);
-    if (nT > 1) stage(2, 1);
-    if (nT > 2) stage(3, 2);
-    wait_barrier(nT > 2 ? 2 : (nT > 1 ? 1 : 0));
+    ring.stage(0, 3);
+    ring.stage(1, 0);
+    if (nT > 1) ring.stage(2, 1);
+    if (nT > 2) ring.stage(3, 2);
+    ring.wait_barrier(nT > 2 ? 2 : (nT > 1 ? 1 : 0));
     float m_run[2];
     {
         floatx16 t[2];
@@ -931,9 +900,7 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
             float mt = fmaxf(s[j][0], t[j][0]);
 #pragma unroll
             for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[j][r]), t[j][r]);
-            const unsigned mb = __builtin_bit_cast(unsigned, mt);
-            const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-            m_run[j] = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
+            m_run[j] = max_both_halves(mt);
             // flash_body's nomax test (folded: accumulator units are exponent units)
             common = common && (scale_log2 * sqrtf(q2[j]) * kmax * 1.001f + 1e-3f - m_run[j] <= NOMAX_THR);
         }
@@ -952,7 +919,7 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
         if (__builtin_amdgcn_readfirstlane(all) == 0) {
 #pragma nounroll
             for (int half = 0; half < 2; ++half) {
-                ring_wait_barrier<0>();  // the ring is idle: every pack in flight has landed, nobody reads
+                dma_wait_barrier<0>();  // the ring is idle: every pack in flight has landed, nobody reads
                 // (thread and block indices go in through empty asm: otherwise hipcc shares flash_body's index arithmetic
                 // with the code above and carries it, in scratch, through the half-tile loop)
                 int tid_ = tid, h_ = h, qb_ = qblk * 2 + half, b_ = b;
@@ -983,10 +950,10 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
         const int slot = u & 3;
         auto ring_sync = [&]() __attribute__((always_inline)) {
             if (F == 0) {  // pack u + 2 (step u + 1) has landed for everyone
-                if (FULL) ring_wait_barrier<NPW_LO>(); else wait_barrier(u + 2 < nT ? 1 : 0);
+                if (FULL) dma_wait_barrier<PackRing<D>::NPW_LO>(); else ring.wait_barrier(u + 2 < nT ? 1 : 0);
             } else {       // everyone is through phase (u, 0): pack u's slot takes pack u + 4
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                if (FULL || u + 3 < nT) stage(u + 4, (u + 3) & 3);
+                if (FULL || u + 3 < nT) ring.stage(u + 4, (u + 3) & 3);
             }
         };
         if (grpB) ring_sync();
@@ -1082,7 +1049,7 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
     const int l31e = tid2 & 31, hie = (tid2 >> 5) & 1;
     {
         const int slot = u & 3;
-        if (grpB) ring_wait_barrier<0>();
+        if (grpB) dma_wait_barrier<0>();
         __builtin_amdgcn_sched_barrier(0);
         floatx16 s1[2];  // the tile's second half (its K: pack u)
         qk_half(s1, (u + 3) & 3, 1, -m_run[0], -m_run[1]);
@@ -1101,11 +1068,7 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
             float mt = fmaxf(s[j][0], s1[j][0]);
 #pragma unroll
             for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[j][r]), s1[j][r]);
-            {
-                const unsigned mb = __builtin_bit_cast(unsigned, mt);
-                const auto sw = __builtin_amdgcn_permlane32_swap(mb, mb, false, false);
-                mt = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
-            }
+            mt = max_both_halves(mt);
             if (__builtin_amdgcn_readfirstlane((int)__any(mt > RESCALE_THR)) != 0) {
                 const float delta = fmaxf(mt, 0.f);
                 const float alpha = __builtin_amdgcn_exp2f(-delta);
@@ -1134,7 +1097,7 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
             for (int kc = 0; kc < 4; ++kc) asm volatile("" : "+v"(pf[j][kc]));
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (!grpB) ring_wait_barrier<0>();
+        if (!grpB) dma_wait_barrier<0>();
         __builtin_amdgcn_sched_barrier(0);
         const char* vb_ = smem + slot * Cfg::TILE + voff;
 #pragma unroll

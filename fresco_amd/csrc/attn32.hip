@@ -16,6 +16,7 @@
 //
 // q (B, Lq, D), k (B, Lk, D), v (B, Lk, DV), out (B, Lq, DV), all fp32 row-major.  grid (ceil(Lq/128), B).
 #include "common.h"
+#include "lds_dma.h"
 
 namespace fresco {
 
@@ -409,11 +410,6 @@ __global__ __launch_bounds__(256) void kv_split_kernel(const float* __restrict__
     if (flag && __any(bad) && (tid & 63) == 0) atomicOr(flag, 1);
 }
 
-template <int N_>
-__device__ __forceinline__ void a32_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N_) : "memory");
-}
-
 // Round 6: TWO tile buffers and NW = 4 or 8 waves (128 or 256 queries) per workgroup.  The single-buffer form of rounds 4-5
 // could only request K(t + 1) once every wave was done with K(t), i.e. half a tile ahead: with the image coming from HBM /
 // MALL (a 1024-token window has 8 query blocks to share a tile, and they run in lockstep: the first to ask pays the miss and
@@ -453,17 +449,14 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_f32p_kernel(con
     const float* qp = q + ((int64_t)b * Lq + (qrow < Lq ? qrow : Lq - 1)) * D + hi * 8;
     const int nT = (Lk + 31) / 32;
     const char* ib = img + (int64_t)b * nT * I::TILE;
-    const uint32_t lds0 =
-        __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)tbuf);
+    const uint32_t lds0 = lds_addr(tbuf);
     const uint32_t voff = (uint32_t)lane * 16;
     auto stage = [&](int t) __attribute__((always_inline)) {  // wave w copies KiB w, w + NW, ... of tile t's image
         const char* src = ib + (int64_t)t * I::TILE + wave * 1024;
         const uint32_t dst = lds0 + (uint32_t)((t & 1) * I::TILE + wave * 1024);
 #pragma unroll
         for (int i = 0; i < PPW; ++i)
-            asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src + i * (NW * 1024)),
-                         "s"(dst + (uint32_t)(i * (NW * 1024)))
-                         : "memory");
+            lds_dma16(voff, src + i * (NW * 1024), dst + (uint32_t)(i * (NW * 1024)));
     };
     stage(0);
 
@@ -499,7 +492,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_f32p_kernel(con
 
     for (int t = 0; t < nT; ++t) {
         // tile t has landed for everyone, and everyone is done with tile t - 1: its buffer takes tile t + 1
-        a32_wait_barrier<0>();
+        dma_wait_barrier<0>();
         if (t + 1 < nT) stage(t + 1);
         const char* kh_s = tbuf + (t & 1) * I::TILE;
         const char* kl_s = kh_s + 32 * KROW;

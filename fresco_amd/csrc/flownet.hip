@@ -21,6 +21,7 @@
 //   fn_layernorm_kernel  LayerNorm over 128 channels (+ residual), one wave per row
 //   fn_conv7_rgb_kernel  the 7 x 7 / stride 2 stem on 3 input channels: direct fp32 FMAs (K = 147 is no MFMA shape)
 #include "common.h"
+#include "lds_dma.h"
 
 namespace fresco {
 
@@ -62,17 +63,8 @@ __device__ __forceinline__ int fn_row_of(const FnConv& cv, int blk, int r) {
     return (img * cv.OH + ty * 16 + (r >> 4)) * cv.OW + tx * 16 + (r & 15);
 }
 
-// one LDS-DMA piece: 64 lanes x 16 bytes, lane l's bytes land at lds_dst + 16 l (M0 is written in the statement that uses it)
-__device__ __forceinline__ void fn_dma16(const void* gsrc, uint32_t lds_dst) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_dst) : "memory");  // (m0 cannot be listed as a clobber: hipcc rejects it as a reserved register; it does not keep values in m0 across statements on gfx9+)
-}
-template <int N_>
-__device__ __forceinline__ void fn_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N_) : "memory");
-}
-
 // 256 x BN x 32 tiles, 8 waves as 4 x 2 (wave tiles 64 x BN/2), one workgroup per CU.  Operands arrive by LDS-DMA
-// (global_load_lds_dwordx4: no staging registers, no ds_write) into a ring of three slots, chunks two steps ahead, behind
+// (lds_dma.h: no staging registers, no ds_write) into a ring of three slots, chunks two steps ahead, behind
 // counted vmcnt waits and ONE barrier per chunk (the protocol of opt_fast.hip's Gram / S V kernels).  A slot holds the four
 // planes [A hi | A lo | W hi | W lo] as unpadded 64-byte rows (32 halfs): the DMA writes lane-linear, so the bank swizzle is on
 // the SOURCE side -- the lane that owns LDS position q of row R fetches 16-byte piece q ^ ((R >> 2) & 3) of that row -- and
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(512, 1) void fn_gemm_kernel(const half_t* __restric
         }
     }
     const int n0 = by * BN;
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
+    const uint32_t lds0 = lds_addr(smem);
 
     const int q = lane & 3;
     // W: BN = 128: piece `wave` of both W planes; BN = 64: waves 0-3 piece `wave` of W hi, waves 4-7 piece wave - 4 of W lo
@@ -209,15 +201,15 @@ __global__ __launch_bounds__(512, 1) void fn_gemm_kernel(const half_t* __restric
                 }
                 const void* ph = ok ? static_cast<const void*>(a_hi + off) : zeros;
                 const void* pl = ok ? static_cast<const void*>(a_lo + off) : zeros;
-                fn_dma16(ph, sb + (uint32_t)((2 * wave + i) * 1024));
-                fn_dma16(pl, sb + (uint32_t)(A_PL + (2 * wave + i) * 1024));
+                lds_dma16(ph, sb + (uint32_t)((2 * wave + i) * 1024));
+                lds_dma16(pl, sb + (uint32_t)(A_PL + (2 * wave + i) * 1024));
             }
             if (BN == 128) {
-                fn_dma16(w_ok ? static_cast<const void*>(w_hi + w_off + k0) : zeros, sb + (uint32_t)(2 * A_PL + wave * 1024));
-                fn_dma16(w_ok ? static_cast<const void*>(w_lo + w_off + k0) : zeros, sb + (uint32_t)(2 * A_PL + W_PL + wave * 1024));
+                lds_dma16(w_ok ? static_cast<const void*>(w_hi + w_off + k0) : zeros, sb + (uint32_t)(2 * A_PL + wave * 1024));
+                lds_dma16(w_ok ? static_cast<const void*>(w_lo + w_off + k0) : zeros, sb + (uint32_t)(2 * A_PL + W_PL + wave * 1024));
             } else {
                 const half_t* wp = wave < 4 ? w_hi : w_lo;
-                fn_dma16(w_ok ? static_cast<const void*>(wp + w_off + k0) : zeros,
+                lds_dma16(w_ok ? static_cast<const void*>(wp + w_off + k0) : zeros,
                          sb + (uint32_t)(2 * A_PL + (wave < 4 ? 0 : W_PL) + (wave & 3) * 1024));
             }
         };
@@ -233,9 +225,9 @@ __global__ __launch_bounds__(512, 1) void fn_gemm_kernel(const half_t* __restric
             // own pieces of chunk kc have landed (what may still fly: chunk kc + 1's), then everyone's, and every wave is done
             // with chunk kc - 1: its slot takes chunk kc + 2
             if (kc + 1 < nk)
-                fn_wait_barrier<NPW>();
+                dma_wait_barrier<NPW, false>();
             else
-                fn_wait_barrier<0>();
+                dma_wait_barrier<0, false>();
             if (kc + 2 < nk) stage(kc + 2, slot >= 1 ? slot - 1 : NS - 1);
             const char* s = smem + slot * SLOT;
             const char* sa = s + (wm * 64 + l31) * 64;
@@ -290,18 +282,18 @@ __global__ __launch_bounds__(512, 1) void fn_gemm_kernel(const half_t* __restric
     do {                                                                                                                    \
         const int64_t po_ = p_off[(N_) % 3];                                                                                \
         const half_t* pl_ = (N_) < 3 ? a_hi : a_lo;                                                                         \
-        fn_dma16(po_ >= 0 ? static_cast<const void*>(pl_ + po_ + (C_) * 32) : zeros,                                        \
+        lds_dma16(po_ >= 0 ? static_cast<const void*>(pl_ + po_ + (C_) * 32) : zeros,                                        \
                  lds0 + (uint32_t)((((C_) & 1) * P_SLOT) + ((N_) / 3) * P_PL + (wave + 8 * ((N_) % 3)) * 1024));            \
     } while (0)
 #define FN_PATCH_WSTAGE(K0_, SLOT_)                                                                                         \
     do {                                                                                                                    \
         const uint32_t sb_ = lds0 + (uint32_t)(2 * P_SLOT + (SLOT_) * W_SLOT);                                              \
         if (BN == 128) {                                                                                                    \
-            fn_dma16(w_ok ? static_cast<const void*>(w_hi + w_off + (K0_)) : zeros, sb_ + (uint32_t)(wave * 1024));         \
-            fn_dma16(w_ok ? static_cast<const void*>(w_lo + w_off + (K0_)) : zeros, sb_ + (uint32_t)(W_PL + wave * 1024));  \
+            lds_dma16(w_ok ? static_cast<const void*>(w_hi + w_off + (K0_)) : zeros, sb_ + (uint32_t)(wave * 1024));         \
+            lds_dma16(w_ok ? static_cast<const void*>(w_lo + w_off + (K0_)) : zeros, sb_ + (uint32_t)(W_PL + wave * 1024));  \
         } else {                                                                                                            \
             const half_t* wp_ = wave < 4 ? w_hi : w_lo;                                                                     \
-            fn_dma16(w_ok ? static_cast<const void*>(wp_ + w_off + (K0_)) : zeros,                                          \
+            lds_dma16(w_ok ? static_cast<const void*>(wp_ + w_off + (K0_)) : zeros,                                          \
                      sb_ + (uint32_t)((wave < 4 ? 0 : W_PL) + (wave & 3) * 1024));                                          \
         }                                                                                                                   \
     } while (0)
@@ -313,11 +305,11 @@ __global__ __launch_bounds__(512, 1) void fn_gemm_kernel(const half_t* __restric
         constexpr int older_ = (((T_) >= 1 && (T_) <= 6) ? 1 : 0) + (((T_) >= 2 && (T_) <= 7) ? 1 : 0);                     \
         const int s_ = c * 9 + (T_);                                                                                        \
         if (s_ + 1 >= total)                                                                                                \
-            fn_wait_barrier<0>();                                                                                           \
+            dma_wait_barrier<0, false>();                                                                                           \
         else if (nxt)                                                                                                       \
-            fn_wait_barrier<NW + older_>();                                                                                 \
+            dma_wait_barrier<NW + older_, false>();                                                                                 \
         else                                                                                                                \
-            fn_wait_barrier<NW>();                                                                                          \
+            dma_wait_barrier<NW, false>();                                                                                          \
         if (s_ + 2 < total) {                                                                                               \
             const int t2_ = (T_) + 2 >= 9 ? (T_) + 2 - 9 : (T_) + 2, c2_ = (T_) + 2 >= 9 ? c + 1 : c;                       \
             FN_PATCH_WSTAGE(t2_ * cv.cin + c2_ * 32, slot >= 1 ? slot - 1 : NS - 1);                                        \

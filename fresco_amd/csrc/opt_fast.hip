@@ -24,6 +24,7 @@
 //
 // All reductions have a fixed order: results are bit-reproducible run to run.
 #include "opt_shared.h"
+#include "lds_dma.h"
 #include <stdlib.h>
 
 namespace fresco {
@@ -821,11 +822,6 @@ __device__ __forceinline__ void gx_tile(int idx, int hw, int& ti, int& tj) {
     }
 }
 
-template <int N_>
-__device__ __forceinline__ void gx_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N_) : "memory");
-}
-
 // ------------------------------------------------------------------------------------------------
 // Epilogue of the 256 x 128 / 128 x 128 Gram kernels for one wave's 64 x 64 sub-tile (rows wm * 64 .., columns wn * 64 ..
 // of the workgroup tile): G - T -> sign bytes, stored from registers in both positions -- no LDS, no barrier.
@@ -968,21 +964,15 @@ __global__ __launch_bounds__(512, 4) void gram16y_kernel(const half_t* __restric
     const char* src0 = baseH + oA;
     const char* src1 = baseL + oA;
     const char* src2 = (wq ? baseL : baseH) + oB;
-    const uint32_t lds0 =
-        __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)gy_smem);
+    const uint32_t lds0 = lds_addr(gy_smem);
     const uint32_t voff = (uint32_t)lane * 16;
     const uint32_t pw = (uint32_t)(wq * GY_BLK + (wave & 3) * 1024);
     auto stage = [&](int kc, int slot) __attribute__((always_inline)) {
         const int64_t ko = (int64_t)kc * GY_BLK;
         const uint32_t m0b = lds0 + (uint32_t)(slot * GY_SLOT) + pw;
-#define GY_PIECE(I, SRC)                                                                                         \
-    asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"((SRC) + ko),             \
-                 "s"(m0b + (uint32_t)((I)*2 * GY_BLK))                                                             \
-                 : "memory")
-        GY_PIECE(0, src0);
-        GY_PIECE(1, src1);
-        GY_PIECE(2, src2);
-#undef GY_PIECE
+        lds_dma16(voff, src0 + ko, m0b);
+        lds_dma16(voff, src1 + ko, m0b + (uint32_t)(2 * GY_BLK));
+        lds_dma16(voff, src2 + ko, m0b + (uint32_t)(4 * GY_BLK));
     };
 
     floatx16 acc[2][2];
@@ -1000,9 +990,9 @@ __global__ __launch_bounds__(512, 4) void gram16y_kernel(const half_t* __restric
     stage(0, 0);
     if (nk > 1) {
         stage(1, 1);
-        gx_wait_barrier<3>();
+        dma_wait_barrier<3>();
     } else {
-        gx_wait_barrier<0>();
+        dma_wait_barrier<0>();
     }
     int slot = 0;
     for (int kc = 0; kc < nk; ++kc) {
@@ -1028,9 +1018,9 @@ __global__ __launch_bounds__(512, 4) void gram16y_kernel(const half_t* __restric
         }
         if (kc + 1 < nk) {
             if (kc + 2 < nk)
-                gx_wait_barrier<3>();
+                dma_wait_barrier<3>();
             else
-                gx_wait_barrier<0>();
+                dma_wait_barrier<0>();
         }
         slot = slot == GY_NS - 1 ? 0 : slot + 1;
     }
@@ -1098,21 +1088,15 @@ __global__ __launch_bounds__(256, 3) void gram16z_kernel(const half_t* __restric
     // wave w copies KiB w of each of the four blocks
     const int64_t oA = ((int64_t)ti * nk) * GY_BLK + wave * 1024;
     const int64_t oB = ((int64_t)tj * nk) * GY_BLK + wave * 1024;
-    const uint32_t lds0 =
-        __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)gy_smem);
+    const uint32_t lds0 = lds_addr(gy_smem);
     const uint32_t voff = (uint32_t)lane * 16;
     auto stage = [&](int kc, int slot) __attribute__((always_inline)) {
         const int64_t ko = (int64_t)kc * GY_BLK;
         const uint32_t m0b = lds0 + (uint32_t)(slot * GZ_SLOT + wave * 1024);
-#define GZ_PIECE(I, SRC)                                                                                         \
-    asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"((SRC) + ko),             \
-                 "s"(m0b + (uint32_t)((I)*GY_BLK))                                                                 \
-                 : "memory")
-        GZ_PIECE(0, baseH + oA);
-        GZ_PIECE(1, baseL + oA);
-        GZ_PIECE(2, baseH + oB);
-        GZ_PIECE(3, baseL + oB);
-#undef GZ_PIECE
+        lds_dma16(voff, baseH + oA + ko, m0b);
+        lds_dma16(voff, baseL + oA + ko, m0b + (uint32_t)GY_BLK);
+        lds_dma16(voff, baseH + oB + ko, m0b + (uint32_t)(2 * GY_BLK));
+        lds_dma16(voff, baseL + oB + ko, m0b + (uint32_t)(3 * GY_BLK));
     };
 
     floatx16 acc[2][2];
@@ -1130,9 +1114,9 @@ __global__ __launch_bounds__(256, 3) void gram16z_kernel(const half_t* __restric
     stage(0, 0);
     if (nk > 1) {
         stage(1, 1);
-        gx_wait_barrier<4>();
+        dma_wait_barrier<4>();
     } else {
-        gx_wait_barrier<0>();
+        dma_wait_barrier<0>();
     }
     int slot = 0;
     for (int kc = 0; kc < nk; ++kc) {
@@ -1156,9 +1140,9 @@ __global__ __launch_bounds__(256, 3) void gram16z_kernel(const half_t* __restric
         if (kc + 2 < nk) stage(kc + 2, slot >= 1 ? slot - 1 : GZ_NS - 1);  // the slot chunk kc - 1 was read from
         if (kc + 1 < nk) {
             if (kc + 2 < nk)
-                gx_wait_barrier<4>();
+                dma_wait_barrier<4>();
             else
-                gx_wait_barrier<0>();
+                dma_wait_barrier<0>();
         }
         slot = slot == GZ_NS - 1 ? 0 : slot + 1;
     }
@@ -1342,7 +1326,7 @@ __global__ __launch_bounds__(256) void sv16_kernel(const half_t* __restrict__ vh
 // 64 x 64, two workgroups per CU.  Ablation of sv16_kernel (profiles/r02_attn_experiments.txt section 5): 45 % of its
 // time is the staging work itself -- each thread pays 5 global loads + 6 ds_write_b128 (with the sign expansion) per 16
 // MFMAs, and two chunks of register look-ahead do not help.  Here
-//   * operands arrive by LDS-DMA (global_load_lds_dwordx4: no staging registers, no VALU) into a ring of slots behind
+//   * operands arrive by LDS-DMA (lds_dma.h: no staging registers, no VALU) into a ring of slots behind
 //     counted vmcnt waits and one barrier per chunk (the protocol of proj.hip / attn.hip); with the registers that
 //     frees (108) two workgroups share a CU, so a 2-slot ring (one chunk ahead) is enough: while one workgroup waits
 //     for its chunk the other multiplies;
@@ -1357,10 +1341,6 @@ __global__ __launch_bounds__(256) void sv16_kernel(const half_t* __restrict__ vh
 constexpr int SB_TC = 128, SB_K = 32;
 constexpr int SB_VROW = SB_K * 2, SB_SROW = SB_K;
 constexpr int SB_NSLOT = 3;
-template <int N_>
-__device__ __forceinline__ void sb_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N_) : "memory");
-}
 
 // CT = channel rows per workgroup: 128 (8 waves as 2 x 4, wave tiles 64 x 64) for the full rounds of a launch, 64 (8 waves
 // as 1 x 8, wave tiles 64 x 32) for the tiles of the last, partly filled round: 1280 tiles on 512 workgroup slots are
@@ -1398,8 +1378,7 @@ __global__ __launch_bounds__(512, 4) void sv16b_kernel(const half_t* __restrict_
     const char* vhb = reinterpret_cast<const char*>(vh + ((int64_t)b * nct + c0 / 128) * hw * 128);
     const char* vlb = reinterpret_cast<const char*>(vl + ((int64_t)b * nct + c0 / 128) * hw * 128);
     const char* sbp = reinterpret_cast<const char*>(sgn_in + ((int64_t)b * npt + p0 / 256) * hw * 256);
-    const uint32_t lds0 =
-        __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)sb_smem);
+    const uint32_t lds0 = lds_addr(sb_smem);
 
     // DMA, 1 KiB pieces: CT = 128: wave w copies KiB w of Vh, of Vl and of S (3 pieces); CT = 64: waves 0-3 KiB w of the Vh
     // half, waves 4-7 KiB w - 4 of the Vl half, every wave KiB w of S (2 pieces)
@@ -1411,19 +1390,15 @@ __global__ __launch_bounds__(512, 4) void sv16b_kernel(const half_t* __restrict_
     const uint32_t o_a = CT == 128 ? (uint32_t)(wave * 1024) : (uint32_t)((wave < 4 ? 0 : VARR) + (wave & 3) * 1024);
     auto stage = [&](int kc, int slot) __attribute__((always_inline)) {
         const uint32_t m0b = lds0 + (uint32_t)(slot * SLOT);
-#define SB_PIECE(OFF, SRC)                                                                                        \
-    asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(SRC), "s"(m0b + (uint32_t)(OFF)) \
-                 : "memory")
-        SB_PIECE(o_a, s_a + (int64_t)kc * (SB_TC * SB_VROW));
-        if (CT == 128) SB_PIECE(VARR + wave * 1024, s_l + (int64_t)kc * (SB_TC * SB_VROW));
-        SB_PIECE(2 * VARR + wave * 1024, s_s + (int64_t)kc * SARR);
-#undef SB_PIECE
+        lds_dma16(voff, s_a + (int64_t)kc * (SB_TC * SB_VROW), m0b + o_a);
+        if (CT == 128) lds_dma16(voff, s_l + (int64_t)kc * (SB_TC * SB_VROW), m0b + (uint32_t)(VARR + wave * 1024));
+        lds_dma16(voff, s_s + (int64_t)kc * SARR, m0b + (uint32_t)(2 * VARR + wave * 1024));
     };
     auto wait_barrier = [&](int keep) __attribute__((always_inline)) {  // keep = newer slots that may stay in flight
         if (keep == 0)
-            sb_wait_barrier<0>();
+            dma_wait_barrier<0>();
         else
-            sb_wait_barrier<NPW>();
+            dma_wait_barrier<NPW>();
     };
 
     floatx16 acc[2][NJ];
@@ -1519,11 +1494,9 @@ __global__ __launch_bounds__(512, 4) void sv16b_kernel(const half_t* __restrict_
 #pragma unroll
                     for (int pc = 0; pc < 2; ++pc) {
                         const char* src = (ar ? vlb : vhb) + ((int64_t)(ch0 + ni) * 128 + rl0) * SB_VROW + pc * 1024;
-                        asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src),
-                                     "s"(mybase + (uint32_t)(ni * 4096 + ar * 2048 + pc * 1024))
-                                     : "memory");
+                        lds_dma16(voff, src, mybase + (uint32_t)(ni * 4096 + ar * 2048 + pc * 1024));
                     }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            dma_wait<0>();
 #pragma unroll
             for (int ni = 0; ni < NJ; ++ni)
 #pragma unroll

@@ -6,8 +6,8 @@
 // 2.3 TB/s, 360 TFLOP/s).  Here x is read ONCE: a wave keeps its 32 rows of x resident in registers as
 // MFMA B fragments (K/16 fragments of 8 halfs) and streams slabs of 64 weight rows x 160 k through LDS -- the
 // same swapped orientation as the flash kernel (out^T = W_tile x^T: one lane owns one row of x and ends up
-// with 4 x 8 consecutive output features of a 64-feature tile).  Weight slabs are DMA'd global -> LDS (global_load_lds_dwordx4, issued as inline asm so that
-// the compiler does not drain vmcnt in front of the fragment reads) into a 3-slot ring, TWO steps ahead, behind
+// with 4 x 8 consecutive output features of a 64-feature tile).  Weight slabs are DMA'd global -> LDS (lds_dma.h: hidden from the compiler so that
+// it does not drain vmcnt in front of the fragment reads) into a 3-slot ring, TWO steps ahead, behind
 // a counted s_waitcnt and one barrier per step; rows padded to an odd multiple of 16 B (conflict-free
 // ds_read_b128); the weights (<= 2.4 MB) stay L2-resident.
 //
@@ -33,6 +33,7 @@
 // MFMA order: bit-identical outputs.  (16384, 640): single projection 29.9 -> 25.2 us, q,k,v 54.6 -> 49.8; (65536, 320),
 // HBM-bound in that phase: 59.0 -> 58.8 (profiles/r06_ab_proj_x_staging.txt; the old form is in the commit history).
 #include "common.h"
+#include "lds_dma.h"
 
 namespace fresco {
 
@@ -63,11 +64,6 @@ struct ProjCfg {
     static_assert(XST >= OSCR && (32 * (KC / 8)) % 64 == 0, "staging region");
     static constexpr int BIAS_OFF = RING_BYTES + NWV * XST;  // [nw][N] halfs follow
 };
-
-template <int N_>
-__device__ __forceinline__ void proj_wait_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N_) : "memory");
-}
 
 template <int K, int NWV>
 __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
@@ -103,8 +99,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
         dma_off[i] = (r < Cfg::TF && dc < Cfg::CPR - 1) ? (uint32_t)(r * K * 2 + dc * 16) : 0u;
     }
     const int many = wave_s < Cfg::NREM || Cfg::NREM == 0 ? 1 : 0;  // this wave issues NPW_HI pieces per slab
-    const uint32_t lds0 =
-        __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
+    const uint32_t lds0 = lds_addr(smem);
     // feature tile ft belongs to projection ft / tiles_per_out: every projection keeps its own (live) weight
     // matrix, nothing is stacked or cached on the host side.  The slab address is scalar arithmetic.
     const int tiles_per_out = N / Cfg::TF;
@@ -121,26 +116,13 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
         const uint32_t dstb = lds0 + slot * Cfg::SLOT + wave_s * 1024;
 #pragma unroll
         for (int i = 0; i < Cfg::NPW_HI; ++i) {
-            if (i < Cfg::NPW_LO || many) {
-                const uint32_t m0v = dstb + i * NWV * 1024;
-                asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(dma_off[i]), "s"(src), "s"(m0v)
-                             : "memory");
-            }
+            if (i < Cfg::NPW_LO || many) lds_dma16(dma_off[i], src, dstb + i * NWV * 1024);
         }
     };
     // the slab of step s+1 has landed for everyone (own pieces: counted vmcnt, at most the newest slab's still in
     // flight -- output stores only make the wait stricter), and every wave is done with the slab of step s-1
     auto wait_barrier = [&](int keep) __attribute__((always_inline)) {  // keep = newer slabs that may stay in flight
-        if (keep == 0)
-            proj_wait_barrier<0>();
-        else if (keep == 1 && many)
-            proj_wait_barrier<Cfg::NPW_HI>();
-        else if (keep == 1)
-            proj_wait_barrier<Cfg::NPW_LO>();
-        else if (many)
-            proj_wait_barrier<2 * Cfg::NPW_HI>();
-        else
-            proj_wait_barrier<2 * Cfg::NPW_LO>();
+        dma_wait_barrier_keep<Cfg::NPW_LO, Cfg::NPW_HI>(keep, many);
     };
     constexpr int AHEAD = Cfg::NBUF - 1;
 

@@ -20,6 +20,7 @@
 // the same kernel runs on those rows without a row table ("packed" form), and the way back mirrors it
 // (all-to-all, fresco_temporal_unpack).
 #include "common.h"
+#include "lds_dma.h"
 
 namespace fresco {
 
@@ -33,7 +34,7 @@ typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 // N <= 32 frames: the per-pixel N x N attention on the matrix pipe.
 //
 // A block owns PB consecutive trajectories of one CFG half: R = PB*N rows each of Q, K and V.  The rows arrive by
-// LDS-DMA (global_load_lds_dwordx4: one instruction per gathered row and 64 chunks, every load of the block in
+// LDS-DMA (lds_dma.h: one instruction per gathered row and 64 chunks, every load of the block in
 // flight at once, no staging registers) into LDS rows of RS = 16 * (C/8 | 1) bytes: an odd number of 16-byte
 // chunks, so that the 16 rows of an MFMA operand tile start in 16 different bank quads (ds_read_b128 of one
 // chunk per row: conflict-free) and rows 4 apart sit 16 banks apart (the 2-byte reads of the V operand).
@@ -98,8 +99,7 @@ __global__ __launch_bounds__(512) void temporal_mfma_kernel(
     // ---- stage Q, K, V rows by DMA: wave w takes rows w, w + nwaves, ...; lane = 16-byte chunk of the row ------
     const int ppr = (CC + 63) >> 6;  // DMA instructions per row
     {
-        const uint32_t lds0 =
-            __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem);
+        const uint32_t lds0 = lds_addr(smem);
         for (int r = wave; r < R; r += nwaves) {
             int ro = __builtin_amdgcn_readfirstlane(rows[r]);
             if (ro < 0) ro = 0;  // rows without a trajectory: load something valid, never stored
@@ -110,16 +110,11 @@ __global__ __launch_bounds__(512) void temporal_mfma_kernel(
                 for (int part = 0; part < ppr; ++part) {
                     const int cc = part * 64 + lane;
                     const uint32_t m0v = lds0 + (uint32_t)((t * R + r) * RS + part * 1024);
-                    if (cc < CC) {
-                        const uint32_t voff = (uint32_t)cc * 16u;
-                        asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src[t]),
-                                     "s"(m0v)
-                                     : "memory");
-                    }
+                    if (cc < CC) lds_dma16((uint32_t)cc * 16u, src[t], m0v);
                 }
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        dma_wait<0>();
     }
     __syncthreads();
 

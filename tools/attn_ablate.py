@@ -20,9 +20,9 @@ def rep(s, old, new, count=1):
 
 def edits(name, s):
     if "nodma" in name or "nobar" in name:
-        s = rep(s, "                ring_wait_barrier<NPW_LO>();  // (waves with an extra piece per pack wait for one piece more)\n"
-                   "                stage(u + 4, (u + 3) & 3);",
-                "                ring_wait_barrier<NPW_LO>();" if "nobar" not in name else
+        s = rep(s, "                dma_wait_barrier<PackRing<D>::NPW_LO>();  // (waves with an extra piece per pack wait for one piece more)\n"
+                   "                ring.stage(u + 4, (u + 3) & 3);",
+                "                dma_wait_barrier<PackRing<D>::NPW_LO>();" if "nobar" not in name else
                 "                asm volatile(\"s_waitcnt vmcnt(0) lgkmcnt(0)\" ::: \"memory\");")
     if "noreads" in name:
         s = rep(s, "vf[kc][db] = *reinterpret_cast<const half8_t*>(vb_ + (kc * 2 * Cfg::DPV + db * 32) * 16);",
@@ -45,7 +45,8 @@ def main():
     for v in sys.argv[1:] or ["base", "nodma", "nobar", "noreads", "novalu", "nodma_noreads", "nobar_noreads_novalu"]:
         s = edits(v, src) if v != "base" else src
         cpp = os.path.join(OUT, "attn_%s.hip" % v)
-        open(cpp, "w").write(s.replace('#include "attn_cfg.h"', '#include "../../fresco_amd/csrc/attn_cfg.h"'))
+        open(cpp, "w").write(s.replace('#include "attn_cfg.h"', '#include "../../fresco_amd/csrc/attn_cfg.h"')
+                             .replace('#include "lds_dma.h"', '#include "../../fresco_amd/csrc/lds_dma.h"'))
         obj = os.path.join(OUT, "attn_%s.o" % v)
         subprocess.check_call([HIPCC] + FLAGS + ["-c", cpp, "-o", obj])
         subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + [obj, "-o",

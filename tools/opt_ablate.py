@@ -37,21 +37,25 @@ def edits(name, s):
         s = rep(s, "            tnext[r] = wgt ? __builtin_nontemporal_load(tgt + (int64_t)(i * 32 + (r & 3) + 8 * (r >> 2)) * hw + jj * 32) : 0.f;",
                 "            tnext[r] = 0.25f;")
     if "g_nodma" in v:
-        s = rep(s, "        GY_PIECE(0, src0);\n        GY_PIECE(1, src1);\n        GY_PIECE(2, src2);", "        (void)m0b; (void)ko;")
+        s = rep(s, "        lds_dma16(voff, src0 + ko, m0b);\n        lds_dma16(voff, src1 + ko, m0b + (uint32_t)(2 * GY_BLK));\n        lds_dma16(voff, src2 + ko, m0b + (uint32_t)(4 * GY_BLK));",
+                "        (void)m0b; (void)ko;")
     if "g_nomfma" in v:
         old = ("                    acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[jj], acc[i][jj], 0, 0, 0);\n"
                "                    acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[jj], acc[i][jj], 0, 0, 0);\n"
                "                    acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[jj], acc[i][jj], 0, 0, 0);")
         s = rep(s, old, "                    asm volatile(\"\" ::\"v\"(ah[i]), \"v\"(al[i]), \"v\"(bh[jj]), \"v\"(bl[jj]));")
     if "g_nobar" in v:
-        s = rep(s, 'asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\\n\\ts_barrier" ::"n"(N_) : "memory");\n}\n\n// ------------------------------------------------------------------------------------------------\n// Epilogue of the 256',
-                'asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N_) : "memory");\n}\n\n// ------------------------------------------------------------------------------------------------\n// Epilogue of the 256')
+        # the Gram kernels' counted waits lose their barrier (the S V kernel, further down, keeps its own)
+        i, j = s.index("void gram16y_kernel"), s.index("constexpr int SB_TC")
+        s = (s[:i].replace("namespace fresco {\n", "namespace fresco {\ntemplate <int N_>\n__device__ __forceinline__ void gx_wait() {\n"
+                           "    asm volatile(\"s_waitcnt vmcnt(%0) lgkmcnt(0)\" ::\"n\"(N_) : \"memory\");\n}\n", 1) +
+             s[i:j].replace("dma_wait_barrier<", "gx_wait<") + s[j:])
     if "s_nodot" in v:
         s = rep(s, "    if (dotp) {\n        __syncthreads();  // the ring is free\n        const uint32_t mybase", "    if (dotp && alpha == 12345.f) {\n        __syncthreads();\n        const uint32_t mybase")
     if "s_nostore" in v:
         s = rep(s, "                dvt[((int64_t)b * C + c0 + rl) * hw + col] = acc[mi][ni][r];", "                if (acc[mi][ni][r] == 12345.f) dvt[((int64_t)b * C + c0 + rl) * hw + col] = acc[mi][ni][r];")
     if "s_nodma" in v:
-        s = rep(s, "        SB_PIECE(o_a, s_a + (int64_t)kc * (SB_TC * SB_VROW));\n        if (CT == 128) SB_PIECE(VARR + wave * 1024, s_l + (int64_t)kc * (SB_TC * SB_VROW));\n        SB_PIECE(2 * VARR + wave * 1024, s_s + (int64_t)kc * SARR);",
+        s = rep(s, "        lds_dma16(voff, s_a + (int64_t)kc * (SB_TC * SB_VROW), m0b + o_a);\n        if (CT == 128) lds_dma16(voff, s_l + (int64_t)kc * (SB_TC * SB_VROW), m0b + (uint32_t)(VARR + wave * 1024));\n        lds_dma16(voff, s_s + (int64_t)kc * SARR, m0b + (uint32_t)(2 * VARR + wave * 1024));",
                 "        (void)m0b;")
     if "s_nomfma" in v:
         s = rep(s, "                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][0], fb[j], acc[i][j], 0, 0, 0);\n                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i][1], fb[j], acc[i][j], 0, 0, 0);\n                }\n        }\n        if (kc + 1 < nk) wait_barrier(kc + 2 < nk ? 1 : 0);",
@@ -84,7 +88,8 @@ def main():
     for v in sys.argv[1:]:
         s = edits(v, src) if v != "base" else src
         cpp = os.path.join(OUT, "opt_fast_%s.hip" % v)
-        open(cpp, "w").write(s.replace('#include "opt_shared.h"', '#include "../../fresco_amd/csrc/opt_shared.h"'))
+        open(cpp, "w").write(s.replace('#include "opt_shared.h"', '#include "../../fresco_amd/csrc/opt_shared.h"')
+                             .replace('#include "lds_dma.h"', '#include "../../fresco_amd/csrc/lds_dma.h"'))
         obj = os.path.join(OUT, "opt_fast_%s.o" % v)
         subprocess.check_call([HIPCC] + FLAGS + ["-c", cpp, "-o", obj])
         subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + [obj, "-o",
