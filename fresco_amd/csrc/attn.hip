@@ -140,193 +140,280 @@ __global__ __launch_bounds__(256) void kv_pack_kernel(const half_t* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
-// kvproj_pack (round 6): the K | V projection of the SELECTED rows and the pack in ONE launch, for layer calls whose only
-// reader of K and V is the cross-frame pass (cross-frame-only steps: 7 of the 15 of the schedule).  Before: fresco_linear_rows
-// (K | V of the 2 x M gathered hidden rows -> HBM, 15 - 18 us) then kv_pack_kernel (gather again, transpose, pad -> image,
-// 9 - 13 us), two latency-bound launches in front of the flash kernel.  Here a workgroup owns one 64-key tile of one CFG
-// half and 160 output features of K and of V (4 heads at D = 40, 2 at D = 80): the 64 gathered hidden rows are staged in
-// LDS once (odd 16-byte row stride: conflict-free fragment reads), each of the 5 waves streams its 32 weight rows of W_k
-// and of W_v straight from L2 into MFMA fragments (no LDS: nothing is shared between waves), and the accumulators ARE the
-// image's pieces -- K as C[feature][key] (A = W_k, B = x: a lane's 4 consecutive features of a key are 8 bytes of the
-// key's chunk), V^T as C[key][feature] (A = x, B = W_v: a lane's registers 8 kc' .. 8 kc' + 7 are the 8 keys of one
-// 16-byte V^T chunk, in the C-tile key order the flash kernel's PV product consumes).  The constant parts of the image
-// (ones column of K, ones row / zero rows of V^T) and max |k|^2 per (head, tile) are written alongside (partial sums per
-// 4 features in LDS, added in a fixed order: run-to-run identical).  K and V never exist in HBM.
-// Numerics: one fp32 accumulation chain per output in natural k order (linear_kernel: two chains, permuted k) -- the fp16
-// K / V values can differ from the two-launch path's in the last place; parity is against the oracle, as everywhere.
-// grid (nT, H*D/160, G), 320 threads.
+// kvproj_pack: the K | V projection of the SELECTED rows and the pack in ONE launch, for layer calls whose K and V are
+// read through the cross-frame pass's key image (V by nothing else).  The two-launch form is fresco_linear_rows (K | V of
+// the 2 x M gathered hidden rows -> HBM) then kv_pack_kernel (gather again, transpose, pad -> image), two latency-bound
+// launches in front of the flash kernel.  K and V never exist in HBM here.
+//
+// A workgroup (5 waves) owns one CFG half, 160 output features of K OR of V (4 heads at D = 40, 2 at D = 80) and a
+// contiguous range of TILES 64-key tiles:
+//   * weights ONCE: a wave's 32 weight rows (all of K_in) are its MFMA fragments for the whole range and stay in registers
+//     (80 VGPRs at K_in = 320, 160 at 640).  They arrive coalesced -- consecutive lanes copy consecutive 16-byte pieces of
+//     a row by LDS-DMA into a wave-private staging slot (rows of 320 k at an odd 16-byte stride; two rounds at 640) and are
+//     read from there in fragment order.  (The first form had every lane walk its own row straight from L2: 16 bytes of
+//     64 different lines per instruction, which a CU serves at ~9 B/clk, and every one of the 264 / 136 single-tile
+//     workgroups paid that for both matrices -- 10 us of its 22.)
+//   * hidden rows: the 64 (K_in = 320) or 32 (640: half tiles) gathered rows of a block are copied by LDS-DMA into one of two
+//     buffers, one block ahead: the gather of block u + 1 is in flight under block u's products and stores, ONE barrier per
+//     block.  A DMA piece is 64 consecutive 16-byte chunks of the buffer, so the pad chunk of a row is written too (with a
+//     copy of its neighbour; never read), and rows past M are copied from a valid row and zeroed on the way out.
+//   * the accumulators ARE the image's pieces -- K as C[feature][key] (A = W_k, B = x: a lane's 4 consecutive features of a
+//     key are 8 bytes of the key's chunk), V^T as C[key][feature] (A = x, B = W_v: a lane's registers 8 kc' .. 8 kc' + 7
+//     are the 8 keys of one 16-byte V^T chunk, in the C-tile key order the flash kernel's PV product consumes).  The
+//     constant parts of the image (ones column of K, ones row / zero rows of V^T) and max |k|^2 per (head, tile) are
+//     written alongside (partial sums per 4 features in LDS, added in a fixed order: run-to-run identical).
+// LDS: buffer 0 | staging slots (later: buffer 1, the |k|^2 parts of two tiles) | row table = 150 KB, one workgroup per CU.
+// Numerics: one fp32 accumulation chain per output; MFMA step (st, i) contracts k = 64 st + 8 i + {0..7, 32..39} (the order
+// of the single-tile form this replaces: same image, bit for bit).  linear_kernel uses two chains and another order, so the
+// fp16 K / V values can differ from the two-launch path's in the last place; parity is against the oracle, as everywhere.
+// grid (ceil(nT / TILES), 2 * H*D/160, G), 320 threads; blockIdx.y = 2 * feature group + (0: K, 1: V).
 // ---------------------------------------------------------------------------------------------
 template <int KIN, int D>
 struct KvProjCfg {
-    static constexpr int ROWB = KIN * 2 + 16;  // LDS bytes per staged hidden row: an odd number of 16-byte chunks
-    static constexpr int HPW = 160 / D;        // heads per workgroup
-    static constexpr int NPART = D / 4;        // partial sums of |k|^2 per key and head (one per 4 features)
-    static constexpr int XS_BYTES = 64 * ROWB;
-    static constexpr int LDS_BYTES = XS_BYTES + HPW * NPART * 64 * 4 + 64 * 4;
+    // key tiles per workgroup, chosen from the sweep in EXPERIMENTS.md section 7 (3 at up_blocks.3: 23 ranges x 4 x 2 = 184
+    // workgroups, one round on 256 CUs; 2 would be 272.  2 at up_blocks.2: 144 workgroups; 1 would be 272)
+    static constexpr int TILES = KIN == 320 ? 3 : 2;
+    static constexpr int XR = 64 * 320 / KIN;    // hidden rows per block (a whole tile, or half of one)
+    static constexpr int BPT = 64 / XR;          // blocks per tile
+    static constexpr int NB = XR / 32;           // 32-key MFMA blocks per block
+    static constexpr int CPR = KIN / 8;          // 16-byte chunks per hidden row
+    static constexpr int ROWB = KIN * 2 + 16;    // LDS bytes per staged hidden row: an odd number of 16-byte chunks
+    static constexpr int XPIECES = (XR * (CPR + 1) + 63) / 64;  // 1 KiB DMA pieces per buffer
+    static constexpr int XBUF = XPIECES * 1024;
+    static constexpr int WK = 320;               // k per weight round
+    static constexpr int WROWB = WK * 2 + 16;    // LDS bytes per staged weight row: odd too
+    static constexpr int WPIECES = (32 * (WK / 8 + 1) + 63) / 64;
+    static constexpr int WSLOT = WPIECES * 1024;  // one wave's staging slot
+    static constexpr int NWR = KIN / WK;         // weight rounds
+    static constexpr int HPW = 160 / D;          // heads per workgroup
+    static constexpr int NPART = D / 4;          // partial sums of |k|^2 per key and head (one per 4 features)
+    static constexpr int N2P = HPW * NPART * 64; // floats per tile
+    static constexpr int STAGE_BYTES = 5 * WSLOT;
+    static constexpr int LDS_BYTES = XBUF + STAGE_BYTES + TILES * 64 * 4;
+    static_assert(XBUF + 2 * N2P * 4 <= STAGE_BYTES, "buffer 1 and the |k|^2 parts live in the staging area");
+    static_assert(KIN % WK == 0 && 64 % XR == 0 && XR % 32 == 0 && 160 % D == 0 && D % 8 == 0 && TILES >= 1, "shapes");
 };
 
+// __launch_bounds__' second argument is used as a REGISTER CAP here, not as an occupancy: by its LDS one workgroup fits a CU at
+// either width (5 waves on 4 SIMDs: at most 2 per SIMD).  "3" at K_in = 320 means <= 168 registers, the budget
+// tests/test_kernel_resources.py pins for this instantiation, and the build sits exactly on it (80 weight + 32 accumulator
+// + 32 hidden-row fragment registers + addresses; the lane coordinates of the epilogue are laundered to keep its addresses
+// out of the loop-invariant set): an edit that adds live registers will spill -- that test says so.  "2" at 640: <= 256 (228).
 template <int KIN, int D>
 __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(const half_t* __restrict__ x, int64_t x_ld,
-                                                           const int32_t* __restrict__ x_rows,
-                                                           const half_t* __restrict__ Wk,
-                                                           const half_t* __restrict__ Wv, char* __restrict__ img,
-                                                           float* __restrict__ ktmax, int H, int M, int nT) {
+                                                             const int32_t* __restrict__ x_rows,
+                                                             const half_t* __restrict__ Wk,
+                                                             const half_t* __restrict__ Wv, char* __restrict__ img,
+                                                             float* __restrict__ ktmax, int H, int M, int nT) {
     using Cfg = AttnCfg<D>;
     using PC = KvProjCfg<KIN, D>;
-    constexpr int ROWB = PC::ROWB, HPW = PC::HPW, NPART = PC::NPART;
-    constexpr int NKS = KIN / 16;         // MFMA k-steps
-    // k-steps per pipeline stage = one 128-byte line of every weight row: a lane (row, hi) takes the 64-byte half line
-    // [64 hi, 64 hi + 64) of the line as its fragments of the stage's four k-steps (the contraction order is free as long as
-    // the hidden-row fragments follow it) -- four back-to-back loads of one line, of which three hit in L1; with the natural
-    // order (16 bytes of every other 32) a line is touched by four instructions one pipeline step apart and has left the
-    // 32 KB L1 in between: weight loads 10 us of this launch's 24 (profiles/r06_kvproj_ablation.txt)
-    constexpr int SK = 4;
-    constexpr int NST = NKS / SK;
-    constexpr int CPR = KIN / 8;          // 16-byte chunks per hidden row
-    constexpr int NXL = 64 * CPR / 320;   // staging loads per thread
-    static_assert(NKS % SK == 0 && (64 * CPR) % 320 == 0 && 160 % D == 0 && D % 8 == 0, "shapes");
+    constexpr int ROWB = PC::ROWB, HPW = PC::HPW, NPART = PC::NPART, CPR = PC::CPR, XR = PC::XR, NB = PC::NB, BPT = PC::BPT;
+    constexpr int NKS = KIN / 16;  // MFMA k-steps
+    constexpr int SK = 4;          // k-steps per 64-k stage: lane (row, hi) holds k = 64 st + 32 hi + 8 i + (0..7) for step (st, i)
+    constexpr int WST = PC::WK / 64;  // stages per weight round
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* xs = smem;
-    float* n2p = reinterpret_cast<float*>(smem + PC::XS_BYTES);
-    int32_t* rows = reinterpret_cast<int32_t*>(n2p + HPW * NPART * 64);
-    const int tile = blockIdx.x, fg = blockIdx.y, g = blockIdx.z;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    char* stage = smem + PC::XBUF;
+    float* n2p = reinterpret_cast<float*>(stage + PC::XBUF);
+    int32_t* rows = reinterpret_cast<int32_t*>(stage + PC::STAGE_BYTES);
+    const int tile0 = blockIdx.x * PC::TILES, fg = blockIdx.y >> 1, g = blockIdx.z;
+    const bool kv = blockIdx.y & 1;  // 0: this workgroup makes K pieces, 1: V^T pieces
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
+    const int nt = min(PC::TILES, nT - tile0);  // tiles of this range
+    const int nblk = nt * BPT;
+    const uint32_t lds0 = lds_addr(smem);
+    const int ft = fg * 5 + wave;  // this wave's 32-feature tile
+    const half_t* wsrc = (kv ? Wv : Wk) + (int64_t)ft * 32 * KIN;
 
-    if (tid < 64) {
-        const int m = tile * 64 + tid;
-        rows[tid] = m < M ? x_rows[(int64_t)g * M + m] : -1;
-    }
-    const int ft = fg * 5 + wave;  // this wave's 32-feature tile of K and of V
-    const half_t* wkp = Wk + (int64_t)(ft * 32 + l31) * KIN + hi * 32;
-    const half_t* wvp = Wv + (int64_t)(ft * 32 + l31) * KIN + hi * 32;
-    // Software pipeline, one stage ahead: the weight fragments of stage s + 1 are requested before the products of stage s
-    // (hipcc on its own sinks every load to its use: load -> wait -> MFMA, one L2 round trip per k-step -- 28 us for this
-    // launch; the sched_barriers pin the batches).  Stage 0 is requested before the hidden rows are gathered.
-    half8_t fk[2][SK], fv[2][SK];
-    auto fetch = [&](int st, int buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < SK; ++i) {
-            fk[buf][i] = *reinterpret_cast<const half8_t*>(wkp + st * 64 + i * 8);
-            fv[buf][i] = *reinterpret_cast<const half8_t*>(wvp + st * 64 + i * 8);
+    // one round of this wave's weight rows -> its staging slot, consecutive lanes on consecutive chunks of a row
+    auto weight_dma = [&](int round) __attribute__((always_inline)) {
+#pragma unroll 1  // (unrolled, hipcc keeps all 21 addresses live at once)
+        for (int j = 0; j < PC::WPIECES; ++j) {
+            const int c = j * 64 + lane;
+            const int row = min(c / (PC::WK / 8 + 1), 31), dc = min(c % (PC::WK / 8 + 1), PC::WK / 8 - 1);
+            lds_dma16(wsrc + (int64_t)row * KIN + round * PC::WK + dc * 8, lds0 + PC::XBUF + wave * PC::WSLOT + j * 1024);
         }
     };
-    fetch(0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    __syncthreads();  // rows[]
-    {   // gather the 64 hidden rows into LDS: all of a thread's loads in flight, then its writes
-        uint4 xv[NXL];
+    half8_t fw[NKS];
+    auto weight_frags = [&](int round) __attribute__((always_inline)) {
+        const char* slot = stage + wave * PC::WSLOT + l31 * PC::WROWB + hi * 64;
 #pragma unroll
-        for (int i = 0; i < NXL; ++i) {
-            const int c = tid + i * 320;
-            const int row = c / CPR, dc = c % CPR;
-            const int32_t r = rows[row];
-            xv[i] = make_uint4(0, 0, 0, 0);
-            if (r >= 0) xv[i] = *reinterpret_cast<const uint4*>(x + (int64_t)r * x_ld + dc * 8);
+        for (int s = 0; s < WST; ++s)
+#pragma unroll
+            for (int i = 0; i < SK; ++i)
+                fw[(round * WST + s) * SK + i] = *reinterpret_cast<const half8_t*>(slot + s * 128 + i * 16);
+    };
+    // the gathered hidden rows of block u -> buffer u & 1 (buffer 1 is the head of the staging area)
+    auto gather_dma = [&](int u) __attribute__((always_inline)) {
+        const uint32_t dst = lds0 + (u & 1) * PC::XBUF;
+#pragma unroll 1
+        for (int j = wave; j < PC::XPIECES; j += 5) {
+            const int c = j * 64 + lane;
+            const int row = min(c / (CPR + 1), XR - 1), dc = min(c % (CPR + 1), CPR - 1);
+            const int32_t r = max(rows[u * XR + row], 0);
+            lds_dma16(x + (int64_t)r * x_ld + dc * 8, dst + j * 1024);
         }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < NXL; ++i) {
-            const int c = tid + i * 320;
-            *reinterpret_cast<uint4*>(xs + (c / CPR) * ROWB + (c % CPR) * 16) = xv[i];
-        }
-    }
-    floatx16 ak[2], av[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ak[b][r] = av[b][r] = 0.f;
-    __syncthreads();
-#pragma unroll
-    for (int st = 0; st < NST; ++st) {
-        const int buf = st & 1;
-        if (st + 1 < NST) fetch(st + 1, buf ^ 1);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < SK; ++i) {
-            const int kb = (st * 64 + hi * 32 + i * 8) * 2;  // byte offset inside a staged row (same k order as the weights)
-            const half8_t x0 = *reinterpret_cast<const half8_t*>(xs + l31 * ROWB + kb);
-            const half8_t x1 = *reinterpret_cast<const half8_t*>(xs + (32 + l31) * ROWB + kb);
-            ak[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fk[buf][i], x0, ak[0], 0, 0, 0);
-            ak[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fk[buf][i], x1, ak[1], 0, 0, 0);
-            av[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x0, fv[buf][i], av[0], 0, 0, 0);
-            av[1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(x1, fv[buf][i], av[1], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    // ---- K pieces: lane (key l31 of block b, hi), registers 4j .. 4j+3 = features 32 ft + 8 j + 4 hi + (0..3)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int key = b * 32 + l31;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int f0 = ft * 32 + 8 * j + 4 * hi;
-            const int head = f0 / D, dd = f0 - head * D;
-            half4_t w;
+    };
+    // max |k|^2 of local tile tl per head: parts added in a fixed order, maximum over the 64 keys
+    auto reduce_ktmax = [&](int tl) __attribute__((always_inline)) {
+        if (!kv && wave < HPW) {
+            const float* part = n2p + (tl & 1) * PC::N2P + wave * NPART * 64 + lane;
             float n2 = 0.f;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                w[e] = (half_t)ak[b][4 * j + e];
-                n2 = fmaf((float)w[e], (float)w[e], n2);
-            }
-            char* dst = img + ((int64_t)(g * H + head) * (nT + 1) + tile) * Cfg::TILE;
-            *reinterpret_cast<half4_t*>(dst + ((dd >> 3) * 64 + key) * 16 + (dd & 7) * 2) = w;
-            n2p[((head - fg * HPW) * NPART + (dd >> 2)) * 64 + key] = n2;
+            for (int p_ = 0; p_ < NPART; ++p_) n2 += part[p_ * 64];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) n2 = fmaxf(n2, __shfl_xor(n2, off, 64));
+            if (lane == 0) ktmax[(int64_t)(g * H + fg * HPW + wave) * nT + tile0 + tl] = n2;
         }
+    };
+
+    weight_dma(0);
+    for (int i = tid; i < nt * 64; i += 320) {
+        const int m = tile0 * 64 + i;
+        rows[i] = m < M ? x_rows[(int64_t)g * M + m] : -1;
     }
-    // ---- V^T pieces: lane (feature 32 ft + l31, hi), registers 8 kc' .. 8 kc' + 7 = keys of chunk (kc = 2 b + kc', cc = hi)
-    {
-        const int f = ft * 32 + l31;
-        const int head = f / D, d = f - head * D;
-        char* dst = img + ((int64_t)(g * H + head) * (nT + 1) + tile + 1) * Cfg::TILE + Cfg::KTILE;
+    dma_wait_barrier<0>();  // rows[]; this wave's weight round 0 has landed
+    gather_dma(0);
+    weight_frags(0);
 #pragma unroll
-        for (int b = 0; b < 2; ++b)
+    for (int round = 1; round < PC::NWR; ++round) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot has been read
+        weight_dma(round);
+        dma_wait<0>();
+        weight_frags(round);
+    }
+
+    // the block loop, once per role (a compile-time role: with a run-time one hipcc hoists the two branches' common fragment
+    // reads, all 20 k-steps of them, in front of the branch and spills)
+    auto blocks = [&](auto role) __attribute__((always_inline)) {
+        constexpr bool KV = decltype(role)::value;
+        for (int u = 0; u < nblk; ++u) {
+            // block u's rows have landed (every wave waited for its own pieces); everyone is done with the other buffer -- and,
+            // at u = 0, with the staging slots under it.  The wait is counted: the NST image stores of block u - 1 are this
+            // wave's only vector-memory operations younger than its pieces of block u, and stay in flight
+            // NST MUST equal the number of global store instructions the epilogue below issues per block (K: NB x 4 half4
+            // stores, V: NB x 2 half8 stores) and nothing else may touch vector memory after gather_dma: with fewer stores
+            // than NST the wait returns before the rows have landed.  Check the listing's vmcnt against its stores after any
+            // edit of the epilogue.
+            constexpr int K_STORES = NB * 4, V_STORES = NB * 2;
+            constexpr int NST = KV ? V_STORES : K_STORES;
+            if (u == 0) dma_wait_barrier<0>(); else dma_wait_barrier<NST>();
+            if (u > 0 && u % BPT == 0) reduce_ktmax(u / BPT - 1);  // (its store: in front of the next pieces, not behind)
+            if (u + 1 < nblk) gather_dma(u + 1);
+            const char* xs = smem + (u & 1) * PC::XBUF + l31 * ROWB + hi * 64;
+            const int tl = u / BPT, kbase = (u % BPT) * XR;
+            const int32_t* trow = rows + tl * 64;
+            floatx16 acc[NB];
 #pragma unroll
-            for (int kq = 0; kq < 2; ++kq) {
-                half8_t w;
+            for (int b = 0; b < NB; ++b)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) w[e] = (half_t)av[b][8 * kq + e];
-                *reinterpret_cast<half8_t*>(dst + (((2 * b + kq) * 2 + hi) * Cfg::DPV + d) * 16) = w;
+                for (int r = 0; r < 16; ++r) acc[b][r] = 0.f;
+            // the products, hidden-row fragments one group of four ahead of their MFMAs (left alone, hipcc issues
+            // read -> wait -> MFMA: an LDS round trip per step)
+            constexpr int GS = 4 / NB, NG = NKS / GS;  // k-steps per group, groups
+            half8_t xq[2][4];
+            auto xfetch = [&](int q) __attribute__((always_inline)) {
+#pragma unroll
+                for (int i = 0; i < GS; ++i)
+#pragma unroll
+                    for (int b = 0; b < NB; ++b) {
+                        const int s = q * GS + i;
+                        xq[q & 1][i * NB + b] = *reinterpret_cast<const half8_t*>(xs + b * 32 * ROWB + (s / SK) * 128 + (s % SK) * 16);
+                    }
+            };
+            xfetch(0);
+#pragma unroll
+            for (int q = 0; q < NG; ++q) {
+                if (q + 1 < NG) xfetch(q + 1);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < GS; ++i)
+#pragma unroll
+                    for (int b = 0; b < NB; ++b) {
+                        const half8_t xb = xq[q & 1][i * NB + b], wf = fw[q * GS + i];
+                        acc[b] = KV ? __builtin_amdgcn_mfma_f32_32x32x16_f16(xb, wf, acc[b], 0, 0, 0)
+                                    : __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, xb, acc[b], 0, 0, 0);
+                    }
+                __builtin_amdgcn_sched_barrier(0);
             }
-    }
-    // ---- constant parts of the image for this workgroup's heads
+            // (the image addresses below are loop-invariant per lane; hoisted out of the block loop they cost more registers
+            // than the K_in = 320 budget has left.  Laundering the lane coordinates keeps them inside the iteration.)
+            int l31e = l31, hie = hi;
+            asm volatile("" : "+v"(l31e), "+v"(hie));
+            if (!KV) {
+                // ---- K pieces: lane (key l31 of block b, hi), registers 4j .. 4j+3 = features 32 ft + 8 j + 4 hi + (0..3)
+#pragma unroll
+                for (int b = 0; b < NB; ++b) {
+                    const int key = kbase + b * 32 + l31e;
+                    const bool real = trow[key] >= 0;
+#pragma unroll
+                    for (int j = 0; j < K_STORES / NB; ++j) {  // one store each: K_STORES per block
+                        const int f0 = ft * 32 + 8 * j + 4 * hie;
+                        const int head = f0 / D, dd = f0 - head * D;
+                        half4_t w;
+                        float n2 = 0.f;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            w[e] = real ? (half_t)acc[b][4 * j + e] : (half_t)0;
+                            n2 = fmaf((float)w[e], (float)w[e], n2);
+                        }
+                        char* dst = img + ((int64_t)(g * H + head) * (nT + 1) + tile0 + tl) * Cfg::TILE;
+                        *reinterpret_cast<half4_t*>(dst + ((dd >> 3) * 64 + key) * 16 + (dd & 7) * 2) = w;
+                        n2p[(tl & 1) * PC::N2P + ((head - fg * HPW) * NPART + (dd >> 2)) * 64 + key] = n2;
+                    }
+                }
+            } else {
+                // ---- V^T pieces: lane (feature 32 ft + l31, hi), registers 8 kq .. 8 kq + 7 = keys of chunk (kc, cc = hi)
+                const int f = ft * 32 + l31e;
+                const int head = f / D, d = f - head * D;
+                char* dst = img + ((int64_t)(g * H + head) * (nT + 1) + tile0 + tl + 1) * Cfg::TILE + Cfg::KTILE;
+#pragma unroll
+                for (int b = 0; b < NB; ++b)
+#pragma unroll
+                    for (int kq = 0; kq < V_STORES / NB; ++kq) {  // one store each: V_STORES per block
+                        const int kc = kbase / 16 + 2 * b + kq;
+                        half8_t w;
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) {
+                            const int key = kc * 16 + (e & 3) + 8 * (e >> 2) + 4 * hie;
+                            w[e] = trow[key] >= 0 ? (half_t)acc[b][8 * kq + e] : (half_t)0;
+                        }
+                        *reinterpret_cast<half8_t*>(dst + ((kc * 2 + hie) * Cfg::DPV + d) * 16) = w;
+                    }
+            }
+        }
+    };
+    if (kv) blocks(std::true_type{}); else blocks(std::false_type{});
+    // ---- constant parts of the image for this workgroup's heads and tiles: the K pads by the K workgroup, V^T's by V's
     {
         constexpr int KPAD = (Cfg::DPK - D) / 8;         // pad chunks of K per key (the first one carries the ones column)
         constexpr int VPAD = Cfg::DPV - D;               // pad rows of V^T (the first one is all ones)
-        constexpr int PER_HEAD = KPAD * 64 + VPAD * 8;
-        for (int i = tid; i < HPW * PER_HEAD; i += 320) {
-            const int hl = i / PER_HEAD, c = i % PER_HEAD;
+        const int per_head = kv ? VPAD * 8 : KPAD * 64;
+        for (int i = tid; per_head > 0 && i < nt * HPW * per_head; i += 320) {
+            const int c = i % per_head, hl = (i / per_head) % HPW, tl = i / (per_head * HPW);
             const int head = fg * HPW + hl;
-            char* base = img + ((int64_t)(g * H + head) * (nT + 1) + tile) * Cfg::TILE;
-            if (c < KPAD * 64) {
+            const int32_t* trow = rows + tl * 64;
+            char* base = img + ((int64_t)(g * H + head) * (nT + 1) + tile0 + tl) * Cfg::TILE;
+            if (!kv) {
                 const int pc = c / 64, key = c % 64;
                 uint4 val = make_uint4(0, 0, 0, 0);
-                if (Cfg::MCOL && pc == 0 && rows[key] >= 0) val.x = 0x3C00u;  // K[key][D] = 1.0 (running max rides in the QK MFMA)
+                if (Cfg::MCOL && pc == 0 && trow[key] >= 0) val.x = 0x3C00u;  // K[key][D] = 1.0 (running max rides in the QK MFMA)
                 *reinterpret_cast<uint4*>(base + ((D / 8 + pc) * 64 + key) * 16) = val;
             } else {
-                const int c2 = c - KPAD * 64;
-                const int pr = c2 / 8, kcc = c2 % 8;     // pad row, (kc, cc) chunk
+                const int pr = c / 8, kcc = c % 8;       // pad row, (kc, cc) chunk
                 const int kc = kcc >> 1, cc = kcc & 1;
                 half8_t o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int key = kc * 16 + (e & 3) + 8 * (e >> 2) + 4 * cc;
-                    o[e] = (Cfg::ONES && pr == 0 && rows[key] >= 0) ? (half_t)1 : (half_t)0;
+                    o[e] = (Cfg::ONES && pr == 0 && trow[key] >= 0) ? (half_t)1 : (half_t)0;
                 }
                 *reinterpret_cast<half8_t*>(base + Cfg::TILE + Cfg::KTILE + (kcc * Cfg::DPV + D + pr) * 16) = o;
             }
         }
     }
     __syncthreads();
-    // ---- max |k|^2 of the tile per head: parts added in a fixed order, maximum over the 64 keys
-    if (wave < HPW) {
-        float n2 = 0.f;
-#pragma unroll
-        for (int p_ = 0; p_ < NPART; ++p_) n2 += n2p[(wave * NPART + p_) * 64 + lane];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) n2 = fmaxf(n2, __shfl_xor(n2, off, 64));
-        if (lane == 0) ktmax[(int64_t)(g * H + fg * HPW + wave) * nT + tile] = n2;
-    }
+    reduce_ktmax(nt - 1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1256,8 +1343,9 @@ static int launch_kvproj_attn(const half_t* q, const half_t* x, int64_t x_ld, co
         ProfScope ps(FRESCO_PROF_KV_PACK, n_groups, H, M, -D, st);  // (d < 0: the fused projection + pack launch)
         constexpr int lds = KvProjCfg<KIN, D>::LDS_BYTES;
         if (int rc = allow_dyn_lds(&kvproj_pack_kernel<KIN, D>, lds)) return rc;
-        hipLaunchKernelGGL((kvproj_pack_kernel<KIN, D>), dim3(nT, H * D / 160, n_groups), dim3(320), lds, st, x, x_ld, x_rows,
-                           Wk, Wv, img, ktmax, H, M, nT);
+        constexpr int T = KvProjCfg<KIN, D>::TILES;
+        hipLaunchKernelGGL((kvproj_pack_kernel<KIN, D>), dim3((nT + T - 1) / T, 2 * (H * D / 160), n_groups), dim3(320), lds,
+                           st, x, x_ld, x_rows, Wk, Wv, img, ktmax, H, M, nT);
     }
     return launch_flash_auto<D>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
 }

@@ -39,8 +39,10 @@ class FRESCOAttnProcessor2_0:
         self.fuse_projections = True  # q/k/v (and to_out at C = 320) through fresco_linear when they are plain Linears
         # cross-frame-only calls (no temporal pass) read K and V of the selected tokens only: project just those
         self.sparse_kv_projection = True
-        # ... and (round 6) project them INSIDE the key pack: one launch instead of fresco_linear_rows + kv_pack, K and V
-        # never reach HBM (fresco_attn_fwd_kvproj; plain bias-free fp16 to_k / to_v of a supported width only)
+        # ... and project them INSIDE the key pack: one launch instead of fresco_linear_rows + kv_pack, the selected K and V
+        # never reach HBM (fresco_attn_fwd_kvproj; plain bias-free fp16 to_k / to_v of a supported width only).  Calls with
+        # the temporal pass take it too: that pass reads K of every row but V of none, so to_q | to_k are projected in full
+        # and V only inside the pack
         self.fuse_kv_pack = True
 
     # ---- fused projections ---------------------------------------------------------------------------
@@ -53,7 +55,7 @@ class FRESCOAttnProcessor2_0:
         if (self.fuse_projections and x.dtype == torch.float16 and x.is_cuda
                 and all(_plain_linear(m, False) for m in mods)
                 and len({(m.in_features, m.out_features) for m in mods}) == 1
-                and all(m.weight.is_contiguous() for m in mods)):
+                and all(m.weight.is_contiguous() and m.weight.data_ptr() % 16 == 0 for m in mods)):
             # (x_rows come from _sel_rows: positions of a mask's True entries, in range by construction)
             return ops.linear(x, [m.weight.detach() for m in mods], None, outs, x_rows=x_rows, x_rows_trusted=True)
         if x_rows is not None:  # (modules that keep their own forward: gather first)
@@ -204,36 +206,52 @@ class FRESCOAttnProcessor2_0:
                 if mask_bias is not None:
                     raise ValueError("fresco_amd: attention_mask is not supported in the frame-sharded FRESCO branch")
                 return self._sharded_self_attention(attn, hidden_states, residual, input_ndim)
-            sparse_kv = (self.sparse_kv_projection and bool(ctrl) and ctrl.use_cfattn and not ctrl.use_interattn
-                         and mask_bias is None and hidden_states.shape[0] % self.unet_chunk_size == 0)
-            if sparse_kv:
+            # cross-frame pass over a row table of the hidden states (frame 0 and the selected tokens of the other frames)
+            cf_rows = (self.sparse_kv_projection and bool(ctrl) and ctrl.use_cfattn
+                       and mask_bias is None and hidden_states.shape[0] % self.unet_chunk_size == 0)
+            if cf_rows:
                 # (the row table below is built from the mask's own (frame, pixel) grid and handed to the kernel
                 # unchecked: a mask of another batch size takes the general path, whose row table IS bounds-checked)
                 m_ = self._cf_mask(ctrl, hidden_states.shape[1])
-                sparse_kv = m_ is None or (m_.dim() == 2 and
-                                           m_.shape[0] == hidden_states.shape[0] // self.unet_chunk_size)
-            if sparse_kv:
-                # the only reader of K and V is the cross-frame pass, which gathers frame 0 and the selected tokens of
-                # the other frames (225-247): project exactly those rows, in the order the pass enumerates them
-                (query,) = self._project(attn, hidden_states, ("to_q",))
+                cf_rows = m_ is None or (m_.dim() == 2 and
+                                         m_.shape[0] == hidden_states.shape[0] // self.unet_chunk_size)
+            fuse_kv = False
+            if cf_rows:
                 chunk_, hw_ = self.unet_chunk_size, hidden_states.shape[1]
                 mask = self._cf_mask(ctrl, hw_)
                 nf = hidden_states.shape[0] // chunk_
                 rows_all = self._sel_rows(mask, chunk_, nf, hw_, hidden_states.device)  # flat rows of both CFG halves
-                if (self.fuse_kv_pack and self.fuse_projections and hidden_states.dtype == torch.float16
-                        and hidden_states.is_cuda and not ctrl.use_intraattn
-                        and _plain_linear(attn.to_k, False) and _plain_linear(attn.to_v, False)
-                        and attn.to_k.weight.is_contiguous() and attn.to_v.weight.is_contiguous()
-                        and attn.to_k.out_features == attn.to_v.out_features == query.shape[-1]
-                        and attn.to_k.out_features % attn.heads == 0
-                        and ops.attention_kvproj_supported(attn.heads, attn.to_k.out_features // attn.heads,
-                                                           attn.to_k.in_features)):
-                    # K | V of the selected rows are projected inside the key pack of the cross-frame pass below
-                    fused_kv = (rows_all, attn.to_k.weight.detach(), attn.to_v.weight.detach(), rows_all.numel() // chunk_)
-                    key = value = None
+                # (the spatial-guided pass in front changes nothing here: it only replaces the queries, and its use of the
+                # shared workspace is over, in stream order, before the pack writes the key image)
+                fuse_kv = (self.fuse_kv_pack and self.fuse_projections and hidden_states.dtype == torch.float16
+                           and hidden_states.is_cuda
+                           and _plain_linear(attn.to_k, False) and _plain_linear(attn.to_v, False)
+                           and attn.to_k.weight.is_contiguous() and attn.to_v.weight.is_contiguous()
+                           # the pack copies 16-byte pieces of the weights and of the hidden rows: a contiguous but misaligned
+                           # view (a slice of a flat parameter buffer) takes the unfused path
+                           and attn.to_k.weight.data_ptr() % 16 == 0 and attn.to_v.weight.data_ptr() % 16 == 0
+                           and hidden_states.data_ptr() % 16 == 0
+                           and attn.to_k.out_features == attn.to_v.out_features == getattr(attn.to_q, "out_features", None)
+                           and attn.to_k.out_features % attn.heads == 0
+                           and ops.attention_kvproj_supported(attn.heads, attn.to_k.out_features // attn.heads,
+                                                              attn.to_k.in_features))
+            # the only reader of V, and without the temporal pass of K, is the cross-frame pass, which gathers the rows of the
+            # table (225-247): project exactly those, in the order the pass enumerates them
+            sparse_kv = cf_rows and not ctrl.use_interattn
+            if cf_rows and fuse_kv:
+                # K | V of the selected rows are projected inside the key pack of the cross-frame pass below; the temporal
+                # pass, when on, reads K of every row
+                if ctrl.use_interattn:
+                    query, key = self._project(attn, hidden_states, ("to_q", "to_k"))
                 else:
-                    key, value = self._project(attn, hidden_states, ("to_k", "to_v"), x_rows=rows_all)
-                    key, value = key.view(chunk_, -1, key.shape[-1]), value.view(chunk_, -1, value.shape[-1])
+                    (query,) = self._project(attn, hidden_states, ("to_q",))
+                    key = None
+                value = None
+                fused_kv = (rows_all, attn.to_k.weight.detach(), attn.to_v.weight.detach(), rows_all.numel() // chunk_)
+            elif sparse_kv:
+                (query,) = self._project(attn, hidden_states, ("to_q",))
+                key, value = self._project(attn, hidden_states, ("to_k", "to_v"), x_rows=rows_all)
+                key, value = key.view(chunk_, -1, key.shape[-1]), value.view(chunk_, -1, value.shape[-1])
             else:
                 query, key, value = self._project(attn, hidden_states, ("to_q", "to_k", "to_v"))
         else:
@@ -287,7 +305,7 @@ class FRESCOAttnProcessor2_0:
                 hs = self._masked_attention(q_att, k0, v0, heads, sm_scale, mask_bias)
             else:
                 hs = self._masked_attention(q_att, key, value, heads, sm_scale, mask_bias)
-        elif fresco and ctrl.use_cfattn and sparse_kv and fused_kv is not None:
+        elif fresco and ctrl.use_cfattn and fused_kv is not None:
             hs = ops.attention_kvproj(q_att, hidden_states, fused_kv[0], fused_kv[1], fused_kv[2], heads, sm_scale,
                                       n_groups=chunk, M=fused_kv[3], workspace=self._ws)
         elif fresco and ctrl.use_cfattn and sparse_kv:
