@@ -18,7 +18,7 @@ ERRORS = {
     -3: "FRESCO_EWORKSPACE (workspace too small)",
     -4: "FRESCO_ELAUNCH (HIP launch failed)",
 }
-F16, F32 = 0, 1
+F16, F32, BF16 = 0, 1, 2
 
 
 class FrescoHipError(RuntimeError):
@@ -38,9 +38,11 @@ SIGNATURES = {
     "fresco_attn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fresco_attn_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i64, _f, _f, _vp]),
     "fresco_attn_fwd_ld": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i64, _f, _f, _i64, _i64, _vp]),
+    "fresco_attn_fwd_dt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i64, _f, _f, _i64, _i64, _i, _vp]),
     "fresco_attn_kvproj_supported": (_i, [_i, _i, _i]),
     "fresco_attn_fwd_kvproj": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _f, _i64, _vp]),
     "fresco_temporal_attn_ld": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i64, _i64, _i64, _vp]),
+    "fresco_temporal_attn_dt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i64, _i64, _i64, _i, _vp]),
     "fresco_temporal_attn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "fresco_temporal_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _vp]),
     "fresco_temporal_attn_packed": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
@@ -53,6 +55,10 @@ SIGNATURES = {
                            _vp]),
     "fresco_linear_rows": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i,
                                 _i, _vp]),
+    "fresco_linear_dt": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i,
+                              _i, _vp]),
+    "fresco_linear_rows_dt": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i,
+                                   _i, _i, _i, _vp]),
     "fresco_attn_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "fresco_attn_f32_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fresco_attn_f32_ws": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _f, _vp]),

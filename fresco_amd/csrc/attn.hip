@@ -1,4 +1,4 @@
-// Dense fp16 attention with shared key groups for FRESCO's spatial-guided and efficient
+// Dense fp16 / bf16 attention with shared key groups for FRESCO's spatial-guided and efficient
 // cross-frame passes (reference: src/diffusion_hacked.py:225-247, 250-254, 281-285, 303-305, 371).
 //
 // Two kernels:
@@ -52,18 +52,17 @@ namespace fresco {
 // pack: grid (nT, H, G), 256 threads.  Pack p of the image = K fragments of tile p || V^T fragments of tile p - 1: what
 // ONE loop step of attn_flash_kernel reads (PV(u) next to QK(u+1)); nT + 1 packs.
 // ---------------------------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void kv_pack_kernel(const half_t* __restrict__ k,
-                                                       const half_t* __restrict__ v,
-                                                       const int32_t* __restrict__ kv_rows,
-                                                       char* __restrict__ img, float* __restrict__ ktmax,
-                                                       int H, int M, int nT, int64_t group_rows,
-                                                       int64_t kv_ld) {
+template <typename T, int D>
+__device__ __forceinline__ void kv_pack_body(const T* __restrict__ k, const T* __restrict__ v,
+                                             const int32_t* __restrict__ kv_rows, char* __restrict__ img,
+                                             float* __restrict__ ktmax, int H, int M, int nT, int64_t group_rows,
+                                             int64_t kv_ld) {
     using Cfg = AttnCfg<D>;
+    typedef typename Elem<T>::x8 X8;
     const int tile = blockIdx.x, h = blockIdx.y, g = blockIdx.z;
     __shared__ int32_t rows[64];
-    __shared__ __attribute__((aligned(16))) half_t ks[64][D + 8];  // +8 halfs: 16-B aligned rows
-    __shared__ __attribute__((aligned(16))) half_t vs[64][D + 8];
+    __shared__ __attribute__((aligned(16))) T ks[64][D + 8];  // +8 halfs: 16-B aligned rows
+    __shared__ __attribute__((aligned(16))) T vs[64][D + 8];
 
     if (threadIdx.x < 64) {
         const int m = tile * 64 + threadIdx.x;
@@ -97,24 +96,24 @@ __global__ __launch_bounds__(256) void kv_pack_kernel(const half_t* __restrict__
         if (d0 < D)
             val = *reinterpret_cast<const uint4*>(&ks[key][d0]);
         else if (Cfg::MCOL && d0 == D && rows[key] >= 0)
-            val.x = 0x3C00u;  // K[key][D] = 1.0: with Q[query][D] = -m the QK MFMA delivers  q.k - m
+            val.x = Elem<T>::ONE_BITS;  // K[key][D] = 1.0: with Q[query][D] = -m the QK MFMA delivers  q.k - m
         *reinterpret_cast<uint4*>(dst + (int64_t)c * 16) = val;
     }
     // V^T chunks
     for (int c = threadIdx.x; c < 8 * Cfg::DPV; c += 256) {
         const int d = c % Cfg::DPV, cc = (c / Cfg::DPV) & 1, kc = c / (2 * Cfg::DPV);
-        half8_t o;
+        X8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int key = kc * 16 + (e & 3) + 8 * (e >> 2) + 4 * cc;
-            half_t val = (half_t)0;
+            T val = (T)0;
             if (d < D)
                 val = vs[key][d];
             else if (Cfg::ONES && d == D && rows[key] >= 0)
-                val = (half_t)1;  // ones row: only real keys count towards the softmax denominator
+                val = (T)1;  // ones row: only real keys count towards the softmax denominator
             o[e] = val;
         }
-        *reinterpret_cast<half8_t*>(dst + Cfg::TILE + Cfg::KTILE + (int64_t)c * 16) = o;
+        *reinterpret_cast<X8*>(dst + Cfg::TILE + Cfg::KTILE + (int64_t)c * 16) = o;
     }
     // largest squared key norm of the tile (four threads per key, fixed summation order): the flash kernel
     // bounds every logit of a query by |q| max|k| (Cauchy-Schwarz) and drops the running-max search when
@@ -123,7 +122,7 @@ __global__ __launch_bounds__(256) void kv_pack_kernel(const half_t* __restrict__
         const int row = threadIdx.x >> 2, part = threadIdx.x & 3;
         float n2 = 0.f;
         for (int dc = part; dc < D / 8; dc += 4) {
-            const half8_t kk = *reinterpret_cast<const half8_t*>(&ks[row][dc * 8]);
+            const X8 kk = *reinterpret_cast<const X8*>(&ks[row][dc * 8]);
 #pragma unroll
             for (int e = 0; e < 8; ++e) n2 = fmaf((float)kk[e], (float)kk[e], n2);
         }
@@ -138,6 +137,18 @@ __global__ __launch_bounds__(256) void kv_pack_kernel(const half_t* __restrict__
             ktmax[(int64_t)(g * H + h) * nT + tile] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
     }
 }
+
+#define FRESCO_KV_PACK_KERNEL(NAME, T)                                                                            \
+    template <int D>                                                                                              \
+    __global__ __launch_bounds__(256) void NAME(const T* __restrict__ k, const T* __restrict__ v,                  \
+                                                const int32_t* __restrict__ kv_rows, char* __restrict__ img,       \
+                                                float* __restrict__ ktmax, int H, int M, int nT,                   \
+                                                int64_t group_rows, int64_t kv_ld) {                               \
+        kv_pack_body<T, D>(k, v, kv_rows, img, ktmax, H, M, nT, group_rows, kv_ld);                                \
+    }
+FRESCO_KV_PACK_KERNEL(kv_pack_kernel, half_t)
+FRESCO_KV_PACK_KERNEL(kv_pack_bf16_kernel, bf16_t)
+#undef FRESCO_KV_PACK_KERNEL
 
 // ---------------------------------------------------------------------------------------------
 // kvproj_pack: the K | V projection of the SELECTED rows and the pack in ONE launch, for layer calls whose K and V are
@@ -483,11 +494,12 @@ struct PackRing {
 };
 
 // ---- epilogue: normalise, store O[q][h*D + d]  (row0 = b * Lq; l_run is read only where V^T has no ones row)
-template <int D, int QB>
+template <typename T, int D, int QB>
 __device__ __forceinline__ void flash_store(const floatx16 (&o)[QB][AttnCfg<D>::NDB], const float (&l_run)[QB],
-                                            half_t* __restrict__ out, int64_t row0, int Lq, int C, int h, int qrow0,
+                                            T* __restrict__ out, int64_t row0, int Lq, int C, int h, int qrow0,
                                             int l31, int hi) {
     using Cfg = AttnCfg<D>;
+    typedef typename Elem<T>::x4 X4;
 #pragma unroll
     for (int j = 0; j < QB; ++j) {
         float l_tot;
@@ -505,18 +517,18 @@ __device__ __forceinline__ void flash_store(const floatx16 (&o)[QB][AttnCfg<D>::
         // contiguous bytes of group k and lanes 32-63 with those of group k+1: one 16-byte store per pair instead of
         // two 8-byte ones (the store tail of a row-per-lane epilogue is bound by store instructions, not bytes).
         {
-            half_t* op = out + (row0 + (qr < Lq ? qr : 0)) * C + h * D;
+            T* op = out + (row0 + (qr < Lq ? qr : 0)) * C + h * D;
 #pragma unroll
             for (int db = 0; db < Cfg::NDB; ++db)
 #pragma unroll
                 for (int gp = 0; gp < 2; ++gp) {
                     const int dA = db * 32 + gp * 16;  // first column of the pair
                     if (dA >= D) continue;
-                    half4_t wa, wb;
+                    X4 wa, wb;
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) {
-                        wa[jj] = (half_t)(o[j][db][(2 * gp) * 4 + jj] * inv);
-                        wb[jj] = (half_t)(o[j][db][(2 * gp + 1) * 4 + jj] * inv);
+                        wa[jj] = (T)(o[j][db][(2 * gp) * 4 + jj] * inv);
+                        wb[jj] = (T)(o[j][db][(2 * gp + 1) * 4 + jj] * inv);
                     }
                     if (dA + 8 < D) {
                         const u32x2 a = __builtin_bit_cast(u32x2, wa), bb = __builtin_bit_cast(u32x2, wb);
@@ -526,7 +538,7 @@ __device__ __forceinline__ void flash_store(const floatx16 (&o)[QB][AttnCfg<D>::
                         st[0] = s0[0]; st[1] = s1[0]; st[2] = s0[1]; st[3] = s1[1];
                         if (qr < Lq) *reinterpret_cast<u32x4*>(op + dA + hi * 8) = st;
                     } else if (qr < Lq) {  // a lone 8-column group (D % 16 == 8): the two 8-byte halves as before
-                        *reinterpret_cast<half4_t*>(op + dA + hi * 4) = wa;
+                        *reinterpret_cast<X4*>(op + dA + hi * 4) = wa;
                     }
                 }
         }
@@ -538,12 +550,14 @@ template <int D, int QB>
 struct FlashHalves : std::integral_constant<bool, D == 80 && QB == 2> {};
 
 // The body of one workgroup: head h, batch row b, query rows [qblk * 256 QB, (qblk + 1) * 256 QB).
-template <int D, int QB>
-__device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const char* __restrict__ img,
-                                           const float* __restrict__ ktmax, half_t* __restrict__ out, int H, int Lq,
+template <typename T, int D, int QB>
+__device__ __forceinline__ void flash_body(const T* __restrict__ q, const char* __restrict__ img,
+                                           const float* __restrict__ ktmax, T* __restrict__ out, int H, int Lq,
                                            int M, int nT, int batch_per_group, float scale_log2,
                                            float diag_bias_log2, int64_t q_ld, int h, int qblk, int b, int tid) {
     using Cfg = AttnCfg<D>;
+    typedef typename Elem<T>::x8 X8;
+    constexpr bool FOLD = FoldCfg<T>::ENABLE;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int ROWS = 256 * QB;  // query rows per workgroup
     const int g = b / batch_per_group;
@@ -556,18 +570,18 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
     const int grpB = wave_s >= 4 ? 1 : 0;  // (flags are ints from scalar values: the branches on them stay scalar)
 
     // Q fragments (B operand of S^T = K Q^T), resident for the whole kernel
-    half8_t qf[QB][Cfg::NKS];
+    X8 qf[QB][Cfg::NKS];
     float q2[QB];  // |q|^2 of this lane's query
 #pragma unroll
     for (int j = 0; j < QB; ++j) {
         const int qr = qrow0 + 32 * j;
-        const half_t* qp = q + ((int64_t)b * Lq + (qr < Lq ? qr : Lq - 1)) * q_ld + h * D;
+        const T* qp = q + ((int64_t)b * Lq + (qr < Lq ? qr : Lq - 1)) * q_ld + h * D;
         q2[j] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < Cfg::NKS; ++ks) {
             const int d0 = ks * 16 + hi * 8;
-            half8_t t = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (d0 < D) t = *reinterpret_cast<const half8_t*>(qp + d0);
+            X8 t = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (d0 < D) t = *reinterpret_cast<const X8*>(qp + d0);
 #pragma unroll
             for (int e = 0; e < 8; ++e) q2[j] = fmaf((float)t[e], (float)t[e], q2[j]);
             qf[j][ks] = t;
@@ -600,7 +614,8 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
 #pragma unroll
     for (int j = 0; j < QB; ++j) fold_ok = fold_ok && (scale_log2 * sqrtf(q2[j]) * kmax <= FOLD_MAX);
     // (flags are ints read from scalar values: the branches on them stay scalar branches)
-    const int folded = __builtin_amdgcn_readfirstlane((int)__all(fold_ok));
+    // (bf16 never folds, FoldCfg in attn_cfg.h: the folded passes are compiled out and every score is scaled in fp32)
+    const int folded = FOLD ? __builtin_amdgcn_readfirstlane((int)__all(fold_ok)) : 0;
     const float qs = folded ? scale_log2 : 1.f;
     const float cmul = folded ? 1.f : scale_log2;
     float qbound[QB];  // bound on the accumulators (units u), with a margin for the roundings above
@@ -611,7 +626,7 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
 #pragma unroll
             for (int ks = 0; ks < Cfg::NKS; ++ks)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) qf[j][ks][e] = (half_t)((float)qf[j][ks][e] * scale_log2);
+                for (int e = 0; e < 8; ++e) qf[j][ks][e] = (T)((float)qf[j][ks][e] * scale_log2);
         }
     }
     const float resc_thr = RESCALE_THR / cmul;  // thresholds and the diagonal bias in accumulator units
@@ -643,17 +658,17 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
     // per-lane fragment offset inside a ring slot (K: + (ks*128 + kb*32)*16; V^T: + KTILE + (kc*2*DPV + db*32)*16)
     const int koff = (hi * 64 + l31) * 16;
     const int voff = Cfg::KTILE + (hi * Cfg::DPV + l31) * 16;
-    auto read_k = [&](half8_t (&kf)[2][Cfg::NKS], int slot) __attribute__((always_inline)) {
+    auto read_k = [&](X8 (&kf)[2][Cfg::NKS], int slot) __attribute__((always_inline)) {
         const char* kb_ = smem + slot * Cfg::TILE + koff;
 #pragma unroll
         for (int ks = 0; ks < Cfg::NKS; ++ks)
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
-                kf[kb][ks] = *reinterpret_cast<const half8_t*>(kb_ + (ks * 128 + kb * 32) * 16);
+                kf[kb][ks] = *reinterpret_cast<const X8*>(kb_ + (ks * 128 + kb * 32) * 16);
     };
 
     floatx16 s[QB][2];  // S^T of the tile whose softmax comes next
-    auto qk = [&](half8_t (&kf)[2][Cfg::NKS]) __attribute__((always_inline)) {
+    auto qk = [&](X8 (&kf)[2][Cfg::NKS]) __attribute__((always_inline)) {
 #pragma unroll
         for (int j = 0; j < QB; ++j)
 #pragma unroll
@@ -667,7 +682,7 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int j = 0; j < QB; ++j) {
-                    s[j][kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[kb][ks], qf[j][ks], s[j][kb], 0, 0, 0);
+                    s[j][kb] = Elem<T>::mfma32x32x16(kf[kb][ks], qf[j][ks], s[j][kb]);
                 }
     };
 
@@ -679,7 +694,7 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
     if (nT > 2) ring.stage(3, 2);
     ring.wait_barrier(nT > 2 ? 2 : (nT > 1 ? 1 : 0));
     {
-        half8_t kf[2][Cfg::NKS];
+        X8 kf[2][Cfg::NKS];
         read_k(kf, 3);
         qk(kf);
     }
@@ -720,19 +735,19 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
         __builtin_amdgcn_sched_barrier(0);
 
         // ---- V^T fragments of tile u -> registers (landed one barrier ago), in flight under the softmax
-        half8_t vf[4][Cfg::NDB];
+        X8 vf[4][Cfg::NDB];
         {
             const char* vb_ = smem + slot * Cfg::TILE + voff;
 #pragma unroll
             for (int kc = 0; kc < 4; ++kc)
 #pragma unroll
                 for (int db = 0; db < Cfg::NDB; ++db)
-                    vf[kc][db] = *reinterpret_cast<const half8_t*>(vb_ + (kc * 2 * Cfg::DPV + db * 32) * 16);
+                    vf[kc][db] = *reinterpret_cast<const X8*>(vb_ + (kc * 2 * Cfg::DPV + db * 32) * 16);
         }
         __builtin_amdgcn_sched_barrier(0);
 
         // ---- online softmax, one query per lane; the packed P registers are the PV B operands
-        half8_t pf[QB][4];
+        X8 pf[QB][4];
 #pragma unroll
         for (int j = 0; j < QB; ++j) {
             if (fix) {
@@ -759,11 +774,11 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
                 if (u == 0 || __builtin_amdgcn_readfirstlane((int)__any(mt > resc_thr)) != 0) {
                     float delta = (u == 0) ? mt : fmaxf(mt, 0.f);
                     if (Cfg::MCOL) {
-                        // stays fp16-representable (and finite: logits beyond +-6e4 log2 units saturate)
-                        const float m_new = (float)(half_t)fminf(fmaxf(m_run[j] + delta, -6.0e4f), 6.0e4f);
+                        // stays representable in T (and finite: logits beyond +-6e4 units saturate)
+                        const float m_new = (float)(T)fminf(fmaxf(m_run[j] + delta, -6.0e4f), 6.0e4f);
                         delta = m_new - m_run[j];
                         m_run[j] = m_new;
-                        const half_t nm = (half_t)(-m_new);
+                        const T nm = (T)(-m_new);
                         qf[j][MKS][ME] = (hi == MHI) ? nm : qf[j][MKS][ME];
                     } else {
                         m_run[j] += delta;
@@ -797,8 +812,8 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
                     const float p0 = __builtin_amdgcn_exp2f(s[j][kb][r]);
                     const float p1 = __builtin_amdgcn_exp2f(s[j][kb][r + 1]);
                     if (!Cfg::ONES) psum += p0 + p1;
-                    pf[j][kb * 2 + (r >> 3)][r & 7] = (half_t)p0;
-                    pf[j][kb * 2 + (r >> 3)][(r & 7) + 1] = (half_t)p1;
+                    pf[j][kb * 2 + (r >> 3)][r & 7] = (T)p0;
+                    pf[j][kb * 2 + (r >> 3)][(r & 7) + 1] = (T)p1;
                 }
             if (!Cfg::ONES) l_run[j] += psum;
             // (pins the exponentials in front of group A's barrier below: being free of side effects they would
@@ -812,7 +827,7 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
         __builtin_amdgcn_sched_barrier(0);
 
         // ---- K fragments of tile u+1 (same pack), in flight under the PV MFMAs
-        half8_t kf[2][Cfg::NKS];
+        X8 kf[2][Cfg::NKS];
         if (!LAST) read_k(kf, slot);
         __builtin_amdgcn_sched_barrier(0);
 
@@ -827,7 +842,7 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
             for (int db = 0; db < Cfg::NDB; ++db)
 #pragma unroll
                 for (int j = 0; j < QB; ++j) {
-                    o[j][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[kc][db], pf[j][kc], o[j][db], 0, 0, 0);
+                    o[j][db] = Elem<T>::mfma32x32x16(vf[kc][db], pf[j][kc], o[j][db]);
                 }
         __builtin_amdgcn_sched_barrier(0);
         // ---- S^T of tile u+1
@@ -858,7 +873,7 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
         step(u, yes, no);
     }
 
-    flash_store<D, QB>(o, l_run, out, (int64_t)b * Lq, Lq, C, h, qrow0, l31, hi);
+    flash_store<T, D, QB>(o, l_run, out, (int64_t)b * Lq, Lq, C, h, qrow0, l31, hi);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -882,6 +897,8 @@ __device__ __forceinline__ void flash_body(const half_t* __restrict__ q, const c
 // scores: all eight waves common-case -> this body; otherwise flash_body<D, 1> runs once per 256-row half over the same
 // ring (a workgroup-level choice: all waves share one staging protocol).  The last tile (padded keys, and the max
 // looked at again as flash_body does) is handled as a whole tile: Q is dead by then and S of both halves fits.
+// bf16 (FoldCfg: no fold at all) runs the same body with Q exact and every score multiplied by c in fp32 in front of its
+// exponential; "common case" then means no max search after tile 0, no diagonal bias, two tiles or more.
 // ---------------------------------------------------------------------------------------------
 // Cross-lane reads without a lane-index register (__shfl_xor keeps one per distance; flash_body_halves has none to
 // spare and would share them with the flash_body it falls back to): the value of lane (l ^ X), X < 32, by ds_swizzle,
@@ -891,12 +908,14 @@ __device__ __forceinline__ float lane_xor(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (X << 10) | 0x1f));
 }
 
-template <int D>
-__device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, const char* __restrict__ img,
-                                                  const float* __restrict__ ktmax, half_t* __restrict__ out, int H,
+template <typename T, int D>
+__device__ __forceinline__ void flash_body_halves(const T* __restrict__ q, const char* __restrict__ img,
+                                                  const float* __restrict__ ktmax, T* __restrict__ out, int H,
                                                   int Lq, int M, int nT, int batch_per_group, float scale_log2,
                                                   float diag_bias_log2, int64_t q_ld, int h, int qblk, int b) {
     using Cfg = AttnCfg<D>;
+    typedef typename Elem<T>::x8 X8;
+    constexpr bool FOLD = FoldCfg<T>::ENABLE;
     static_assert(!Cfg::MCOL && Cfg::ONES, "head dims with a spare V^T row and no spare K column (D = 80)");
     constexpr int NKS = Cfg::NKS, NDB = Cfg::NDB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -911,20 +930,20 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
     const int grpB = wave_s >= 4 ? 1 : 0;
 
     // Q fragments, scaled as if folded (a wave that may not fold sends the workgroup to flash_body, which reloads them)
-    half8_t qf[2][NKS];
+    X8 qf[2][NKS];
     float q2[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int qr = qrow0 + 32 * j;
-        const half_t* qp = q + ((int64_t)b * Lq + (qr < Lq ? qr : Lq - 1)) * q_ld + h * D;
+        const T* qp = q + ((int64_t)b * Lq + (qr < Lq ? qr : Lq - 1)) * q_ld + h * D;
         q2[j] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
-            const half8_t t = *reinterpret_cast<const half8_t*>(qp + ks * 16 + hi * 8);
+            const X8 t = *reinterpret_cast<const X8*>(qp + ks * 16 + hi * 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e) q2[j] = fmaf((float)t[e], (float)t[e], q2[j]);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) qf[j][ks][e] = (half_t)((float)t[e] * scale_log2);
+            for (int e = 0; e < 8; ++e) qf[j][ks][e] = FOLD ? (T)((float)t[e] * scale_log2) : t[e];
         }
         float qa, qb;
         both_halves(q2[j], qa, qb);
@@ -944,7 +963,10 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
     }
     bool common = diag_bias_log2 == 0.f && nT >= 2;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) common = common && (scale_log2 * sqrtf(q2[j]) * kmax <= FOLD_MAX);
+    for (int j = 0; j < 2; ++j) common = common && (!FOLD || scale_log2 * sqrtf(q2[j]) * kmax <= FOLD_MAX);
+    // exponent argument = cmul * accumulator: T that never folds keeps Q exact and scales every score in fp32, as
+    // flash_body's exact pass does (m_run, the chains' start values and the thresholds are then in accumulator units)
+    const float cmul = FOLD ? 1.f : scale_log2;
 
     // ---- staging (flash_body's; the fallback below constructs its own ring over the same slots)
     const PackRing<D> ring(img, g, H, h, nT, smem, wave_s, tid);
@@ -954,10 +976,10 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
     floatx16 s[2];  // S^T of the 32 keys whose softmax comes next
     // S^T of keys 32 f .. 32 f + 31 of the tile whose K sits in `slot`; the chains start at c0 / c1
     auto qk_half = [&](floatx16 (&acc)[2], int slot, int f, float c0, float c1) __attribute__((always_inline)) {
-        half8_t kf[NKS];
+        X8 kf[NKS];
         const char* kb_ = smem + slot * Cfg::TILE + koff + f * 512;
 #pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) kf[ks] = *reinterpret_cast<const half8_t*>(kb_ + ks * 2048);
+        for (int ks = 0; ks < NKS; ++ks) kf[ks] = *reinterpret_cast<const X8*>(kb_ + ks * 2048);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             acc[0][r] = c0;
@@ -967,7 +989,7 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
         for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[j][ks], acc[j], 0, 0, 0);
+                acc[j] = Elem<T>::mfma32x32x16(kf[ks], qf[j][ks], acc[j]);
     };
 
     // ---- prologue: packs 0 .. 3 in flight, packs 0 and 1 landed; tile 0's row max (flash_body's anchor of m_run) from
@@ -989,7 +1011,10 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
             for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[j][r]), t[j][r]);
             m_run[j] = max_both_halves(mt);
             // flash_body's nomax test (folded: accumulator units are exponent units)
-            common = common && (scale_log2 * sqrtf(q2[j]) * kmax * 1.001f + 1e-3f - m_run[j] <= NOMAX_THR);
+            if constexpr (FOLD)
+                common = common && (scale_log2 * sqrtf(q2[j]) * kmax * 1.001f + 1e-3f - m_run[j] <= NOMAX_THR);
+            else
+                common = common && (cmul * (sqrtf(q2[j]) * kmax * 1.001f + 1e-3f - m_run[j]) <= NOMAX_THR);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1012,7 +1037,7 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
                 int tid_ = tid, h_ = h, qb_ = qblk * 2 + half, b_ = b;
                 asm volatile("" : "+v"(tid_), "+s"(h_), "+s"(qb_), "+s"(b_));
                 if (qb_ * 256 < Lq)
-                    flash_body<D, 1>(q, img, ktmax, out, H, Lq, M, nT, batch_per_group, scale_log2, diag_bias_log2, q_ld,
+                    flash_body<T, D, 1>(q, img, ktmax, out, H, Lq, M, nT, batch_per_group, scale_log2, diag_bias_log2, q_ld,
                                      h_, qb_, b_, tid_);
             }
             return;
@@ -1047,30 +1072,34 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
         __builtin_amdgcn_sched_barrier(0);
 
         // ---- V^T fragments of the phase's two k-steps, in flight under the softmax
-        half8_t vf[2][NDB];
+        X8 vf[2][NDB];
         {
             const char* vb_ = smem + slot * Cfg::TILE + voff + F * (4 * Cfg::DPV * 16);
 #pragma unroll
             for (int kc = 0; kc < 2; ++kc)
 #pragma unroll
                 for (int db = 0; db < NDB; ++db)
-                    vf[kc][db] = *reinterpret_cast<const half8_t*>(vb_ + (kc * 2 * Cfg::DPV + db * 32) * 16);
+                    vf[kc][db] = *reinterpret_cast<const X8*>(vb_ + (kc * 2 * Cfg::DPV + db * 32) * 16);
         }
         __builtin_amdgcn_sched_barrier(0);
 
-        half8_t pf[2][2];
+        X8 pf[2][2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             if (FIRST) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s[j][r] -= m_run[j];
             }
+            if constexpr (!FOLD) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[j][r] *= cmul;
+            }
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
                 const float p0 = __builtin_amdgcn_exp2f(s[j][r]);
                 const float p1 = __builtin_amdgcn_exp2f(s[j][r + 1]);
-                pf[j][r >> 3][r & 7] = (half_t)p0;
-                pf[j][r >> 3][(r & 7) + 1] = (half_t)p1;
+                pf[j][r >> 3][r & 7] = (T)p0;
+                pf[j][r >> 3][(r & 7) + 1] = (T)p1;
             }
             // (pins the exponentials in front of group A's barrier, as in flash_body)
 #pragma unroll
@@ -1082,11 +1111,11 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
         __builtin_amdgcn_sched_barrier(0);
 
         // ---- K fragments of the next 32 keys (second half of tile u: pack u; first half of tile u + 1: this pack)
-        half8_t kf[NKS];
+        X8 kf[NKS];
         {
             const char* kb_ = smem + (F == 0 ? ((u + 3) & 3) * Cfg::TILE + 512 : slot * Cfg::TILE) + koff;
 #pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) kf[ks] = *reinterpret_cast<const half8_t*>(kb_ + ks * 2048);
+            for (int ks = 0; ks < NKS; ++ks) kf[ks] = *reinterpret_cast<const X8*>(kb_ + ks * 2048);
         }
         __builtin_amdgcn_sched_barrier(0);
 
@@ -1097,7 +1126,7 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
             for (int db = 0; db < NDB; ++db)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
-                    o[j][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[kc][db], pf[j][kc], o[j][db], 0, 0, 0);
+                    o[j][db] = Elem<T>::mfma32x32x16(vf[kc][db], pf[j][kc], o[j][db]);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -1107,7 +1136,7 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
         for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-                s[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qf[j][ks], s[j], 0, 0, 0);
+                s[j] = Elem<T>::mfma32x32x16(kf[ks], qf[j][ks], s[j]);
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -1141,7 +1170,7 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
         floatx16 s1[2];  // the tile's second half (its K: pack u)
         qk_half(s1, (u + 3) & 3, 1, -m_run[0], -m_run[1]);
         __builtin_amdgcn_sched_barrier(0);
-        half8_t pf[2][4];
+        X8 pf[2][4];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             int kbase = u * 64 + 4 * hie;
@@ -1156,9 +1185,10 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
 #pragma unroll
             for (int r = 1; r < 16; ++r) mt = fmaxf(fmaxf(mt, s[j][r]), s1[j][r]);
             mt = max_both_halves(mt);
-            if (__builtin_amdgcn_readfirstlane((int)__any(mt > RESCALE_THR)) != 0) {
+            const float resc_thr = FOLD ? RESCALE_THR : RESCALE_THR / cmul;
+            if (__builtin_amdgcn_readfirstlane((int)__any(mt > resc_thr)) != 0) {
                 const float delta = fmaxf(mt, 0.f);
-                const float alpha = __builtin_amdgcn_exp2f(-delta);
+                const float alpha = __builtin_amdgcn_exp2f(FOLD ? -delta : -delta * cmul);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     s[j][r] -= delta;
@@ -1169,16 +1199,23 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
 #pragma unroll
                     for (int r = 0; r < 16; ++r) o[j][db][r] *= alpha;
             }
+            if constexpr (!FOLD) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    s[j][r] *= cmul;
+                    s1[j][r] *= cmul;
+                }
+            }
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
                 const float p0 = __builtin_amdgcn_exp2f(s[j][r]);
                 const float p1 = __builtin_amdgcn_exp2f(s[j][r + 1]);
                 const float p2 = __builtin_amdgcn_exp2f(s1[j][r]);
                 const float p3 = __builtin_amdgcn_exp2f(s1[j][r + 1]);
-                pf[j][r >> 3][r & 7] = (half_t)p0;
-                pf[j][r >> 3][(r & 7) + 1] = (half_t)p1;
-                pf[j][2 + (r >> 3)][r & 7] = (half_t)p2;
-                pf[j][2 + (r >> 3)][(r & 7) + 1] = (half_t)p3;
+                pf[j][r >> 3][r & 7] = (T)p0;
+                pf[j][r >> 3][(r & 7) + 1] = (T)p1;
+                pf[j][2 + (r >> 3)][r & 7] = (T)p2;
+                pf[j][2 + (r >> 3)][(r & 7) + 1] = (T)p3;
             }
 #pragma unroll
             for (int kc = 0; kc < 4; ++kc) asm volatile("" : "+v"(pf[j][kc]));
@@ -1189,53 +1226,72 @@ __device__ __forceinline__ void flash_body_halves(const half_t* __restrict__ q, 
         const char* vb_ = smem + slot * Cfg::TILE + voff;
 #pragma unroll
         for (int kc = 0; kc < 4; ++kc) {
-            half8_t vf[NDB];
+            X8 vf[NDB];
 #pragma unroll
             for (int db = 0; db < NDB; ++db)
-                vf[db] = *reinterpret_cast<const half8_t*>(vb_ + (kc * 2 * Cfg::DPV + db * 32) * 16);
+                vf[db] = *reinterpret_cast<const X8*>(vb_ + (kc * 2 * Cfg::DPV + db * 32) * 16);
 #pragma unroll
             for (int db = 0; db < NDB; ++db)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
-                    o[j][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf[db], pf[j][kc], o[j][db], 0, 0, 0);
+                    o[j][db] = Elem<T>::mfma32x32x16(vf[db], pf[j][kc], o[j][db]);
         }
     }
 
     const float no_l[2] = {0.f, 0.f};  // (the row sum is O^T row D)
-    flash_store<D, 2>(o, no_l, out, (int64_t)b * Lq, Lq, C, h, qblk * 512 + (tid2 >> 6) * 64 + l31e, l31e, hie);
+    flash_store<T, D, 2>(o, no_l, out, (int64_t)b * Lq, Lq, C, h, qblk * 512 + (tid2 >> 6) * 64 + l31e, l31e, hie);
 }
 
-template <int D, int QB>
-__global__ __launch_bounds__(512, 2) void attn_flash_kernel(const half_t* __restrict__ q,
-                                                          const char* __restrict__ img,
-                                                          const float* __restrict__ ktmax,
-                                                          half_t* __restrict__ out, int B, int H, int Lq,
-                                                          int M, int nT, int batch_per_group,
-                                                          float scale_log2, float diag_bias_log2, int64_t q_ld) {
-    const int nQblk = (Lq + 256 * QB - 1) / (256 * QB);
-    const unsigned blk = blockIdx.x;
-    const int h = blk % H;
-    const int qblk = (blk / H) % nQblk;
-    const int b = blk / (H * nQblk);
-    if constexpr (FlashHalves<D, QB>::value)
-        flash_body_halves<D>(q, img, ktmax, out, H, Lq, M, nT, batch_per_group, scale_log2, diag_bias_log2, q_ld, h, qblk, b);
+#define FRESCO_FLASH_KERNEL(NAME, T)                                                                                  \
+    template <int D, int QB>                                                                                          \
+    __global__ __launch_bounds__(512, 2) void NAME(const T* __restrict__ q, const char* __restrict__ img,             \
+                                                   const float* __restrict__ ktmax, T* __restrict__ out, int B,        \
+                                                   int H, int Lq, int M, int nT, int batch_per_group,                  \
+                                                   float scale_log2, float diag_bias_log2, int64_t q_ld) {             \
+        const int nQblk = (Lq + 256 * QB - 1) / (256 * QB);                                                           \
+        const unsigned blk = blockIdx.x;                                                                              \
+        const int h = blk % H;                                                                                        \
+        const int qblk = (blk / H) % nQblk;                                                                           \
+        const int b = blk / (H * nQblk);                                                                              \
+        if constexpr (FlashHalves<D, QB>::value)                                                                      \
+            flash_body_halves<T, D>(q, img, ktmax, out, H, Lq, M, nT, batch_per_group, scale_log2, diag_bias_log2,     \
+                                    q_ld, h, qblk, b);                                                                \
+        else                                                                                                          \
+            flash_body<T, D, QB>(q, img, ktmax, out, H, Lq, M, nT, batch_per_group, scale_log2, diag_bias_log2, q_ld,  \
+                                 h, qblk, b, threadIdx.x);                                                            \
+    }
+FRESCO_FLASH_KERNEL(attn_flash_kernel, half_t)
+FRESCO_FLASH_KERNEL(attn_flash_bf16_kernel, bf16_t)
+#undef FRESCO_FLASH_KERNEL
+
+template <typename T, int D, int QB>
+static auto flash_kernel_of() {
+    if constexpr (std::is_same<T, bf16_t>::value)
+        return &attn_flash_bf16_kernel<D, QB>;
     else
-        flash_body<D, QB>(q, img, ktmax, out, H, Lq, M, nT, batch_per_group, scale_log2, diag_bias_log2, q_ld, h, qblk, b,
-                          threadIdx.x);
+        return &attn_flash_kernel<D, QB>;
+}
+template <typename T, int D>
+static auto kv_pack_kernel_of() {
+    if constexpr (std::is_same<T, bf16_t>::value)
+        return &kv_pack_bf16_kernel<D>;
+    else
+        return &kv_pack_kernel<D>;
 }
 
-template <int D, int QB>
-static int launch_flash(const half_t* q, const char* img, half_t* out, int B, int H, int Lq, int M, int nT,
+template <typename T, int D, int QB>
+static int launch_flash(const T* q, const char* img, T* out, int B, int H, int Lq, int M, int nT,
                         int n_groups, float scale, float diag_bias, int64_t q_ld, const float* ktmax,
                         hipStream_t st) {
     using Cfg = AttnCfg<D>;
     constexpr int lds = Cfg::LDS_BYTES + (FlashHalves<D, QB>::value ? 64 : 0);  // + the eight waves' votes
-    if (int rc = allow_dyn_lds(&attn_flash_kernel<D, QB>, lds)) return rc;
+    auto kern = flash_kernel_of<T, D, QB>();
+    if (int rc = allow_dyn_lds(kern, lds)) return rc;
     const int nQblk = (Lq + 256 * QB - 1) / (256 * QB);
     const float log2e = 1.4426950408889634f;
     ProfScope ps(FRESCO_PROF_ATTN_FLASH, B * H, Lq, M, D, st);
     const int grid = H * nQblk * B;
-    hipLaunchKernelGGL((attn_flash_kernel<D, QB>), dim3(grid), dim3(512), lds, st, q, img,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, q, img,
                        ktmax, out, B, H, Lq, M, nT, B / n_groups, scale * log2e, diag_bias * log2e, q_ld);
     return check_launch();
 }
@@ -1245,8 +1301,8 @@ static int launch_flash(const half_t* q, const char* img, half_t* out, int B, in
 // 512-row workgroups would leave CUs idle (a frame shard of a multi-GPU run: 2 batch rows x 8 heads x 8 query blocks
 // = 128 workgroups for 256 CUs) takes 256-row workgroups instead -- twice as many, each half as long.  D = 80 (the
 // half-tile body) follows the same rule, and keeps 256-row workgroups for launches of at most 256 queries.
-template <int D>
-static int launch_flash_auto(const half_t* q, const char* img, half_t* out, int B, int H, int Lq, int M, int nT,
+template <typename T, int D>
+static int launch_flash_auto(const T* q, const char* img, T* out, int B, int H, int Lq, int M, int nT,
                              int n_groups, float scale, float diag_bias, int64_t q_ld, const float* ktmax,
                              hipStream_t st) {
     using Cfg = AttnCfg<D>;
@@ -1254,16 +1310,16 @@ static int launch_flash_auto(const half_t* q, const char* img, half_t* out, int 
         const int grid2 = H * ((Lq + 511) / 512) * B;
         const bool idle = grid2 < device_cus();
         if (FlashHalves<D, 2>::value ? (idle || Lq <= 256) : (idle && Lq > 256))
-            return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
-        return launch_flash<D, 2>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
+            return launch_flash<T, D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
+        return launch_flash<T, D, 2>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
     } else {
-        return launch_flash<D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
+        return launch_flash<T, D, 1>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
     }
 }
 
-template <int D>
-static int launch_attn(const half_t* q, const half_t* k, const half_t* v, const int32_t* kv_rows,
-                       half_t* out, char* ws, int B, int H, int Lq, int n_groups, int M,
+template <typename T, int D>
+static int launch_attn(const T* q, const T* k, const T* v, const int32_t* kv_rows,
+                       T* out, char* ws, int B, int H, int Lq, int n_groups, int M,
                        int64_t group_rows, float scale, float diag_bias, int64_t q_ld, int64_t kv_ld,
                        hipStream_t st) {
     using Cfg = AttnCfg<D>;
@@ -1273,10 +1329,10 @@ static int launch_attn(const half_t* q, const half_t* k, const half_t* v, const 
     dim3 pg(nT, H, n_groups);
     {
         ProfScope ps(FRESCO_PROF_KV_PACK, n_groups, H, M, D, st);
-        hipLaunchKernelGGL((kv_pack_kernel<D>), pg, dim3(256), 0, st, k, v, kv_rows, img, ktmax, H, M, nT, group_rows,
+        hipLaunchKernelGGL((kv_pack_kernel_of<T, D>()), pg, dim3(256), 0, st, k, v, kv_rows, img, ktmax, H, M, nT, group_rows,
                            kv_ld);
     }
-    return launch_flash_auto<D>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
+    return launch_flash_auto<T, D>(q, img, out, B, H, Lq, M, nT, n_groups, scale, diag_bias, q_ld, ktmax, st);
 }
 
 static size_t attn_ws_bytes(int n_groups, int H, int M, int D) {
@@ -1295,26 +1351,20 @@ extern "C" size_t fresco_attn_workspace_bytes(int n_groups, int H, int M, int D)
     return attn_ws_bytes(n_groups, H, M, D);
 }
 
-extern "C" int fresco_attn_fwd_ld(const void* q, const void* k, const void* v, const int32_t* kv_rows,
-                                  void* out, void* workspace, size_t workspace_bytes, int B, int H,
-                                  int Lq, int D, int n_groups, int M, int64_t group_rows, float scale,
-                                  float diag_bias, int64_t q_ld, int64_t kv_ld, void* stream) {
-    if (!q || !k || !v || !out || !workspace) return FRESCO_EINVAL;
-    if (q_ld < (int64_t)H * D || kv_ld < (int64_t)H * D || q_ld % 8 != 0 || kv_ld % 8 != 0) return FRESCO_EINVAL;
-    if (B <= 0 || H <= 0 || Lq <= 0 || D <= 0 || n_groups <= 0 || M <= 0 || group_rows <= 0)
-        return FRESCO_EINVAL;
-    if (B % n_groups != 0 || !(scale > 0.f)) return FRESCO_EINVAL;
-    if (workspace_bytes < attn_ws_bytes(n_groups, H, M, D)) return FRESCO_EWORKSPACE;
-    hipStream_t st = as_stream(stream);
-    const half_t* qh = static_cast<const half_t*>(q);
-    const half_t* kh = static_cast<const half_t*>(k);
-    const half_t* vh = static_cast<const half_t*>(v);
-    half_t* oh = static_cast<half_t*>(out);
+namespace fresco {
+template <typename T>
+static int attn_launch_t(const void* q, const void* k, const void* v, const int32_t* kv_rows, void* out, void* workspace,
+                         int B, int H, int Lq, int D, int n_groups, int M, int64_t group_rows, float scale,
+                         float diag_bias, int64_t q_ld, int64_t kv_ld, hipStream_t st) {
+    const T* qh = static_cast<const T*>(q);
+    const T* kh = static_cast<const T*>(k);
+    const T* vh = static_cast<const T*>(v);
+    T* oh = static_cast<T*>(out);
     char* ws = static_cast<char*>(workspace);
 #define FRESCO_ATTN_CASE(DD)                                                                       \
     case DD:                                                                                       \
-        return launch_attn<DD>(qh, kh, vh, kv_rows, oh, ws, B, H, Lq, n_groups, M, group_rows, scale, \
-                               diag_bias, q_ld, kv_ld, st);
+        return launch_attn<T, DD>(qh, kh, vh, kv_rows, oh, ws, B, H, Lq, n_groups, M, group_rows, scale, \
+                                  diag_bias, q_ld, kv_ld, st);
     switch (D) {
         FRESCO_ATTN_CASE(8)
         FRESCO_ATTN_CASE(16)
@@ -1328,6 +1378,34 @@ extern "C" int fresco_attn_fwd_ld(const void* q, const void* k, const void* v, c
             return FRESCO_EUNSUPPORTED;
     }
 #undef FRESCO_ATTN_CASE
+}
+}  // namespace fresco
+
+extern "C" int fresco_attn_fwd_dt(const void* q, const void* k, const void* v, const int32_t* kv_rows,
+                                  void* out, void* workspace, size_t workspace_bytes, int B, int H,
+                                  int Lq, int D, int n_groups, int M, int64_t group_rows, float scale,
+                                  float diag_bias, int64_t q_ld, int64_t kv_ld, int dtype, void* stream) {
+    if (dtype != FRESCO_F16 && dtype != FRESCO_BF16) return FRESCO_EINVAL;
+    if (!q || !k || !v || !out || !workspace) return FRESCO_EINVAL;
+    if (q_ld < (int64_t)H * D || kv_ld < (int64_t)H * D || q_ld % 8 != 0 || kv_ld % 8 != 0) return FRESCO_EINVAL;
+    if (B <= 0 || H <= 0 || Lq <= 0 || D <= 0 || n_groups <= 0 || M <= 0 || group_rows <= 0)
+        return FRESCO_EINVAL;
+    if (B % n_groups != 0 || !(scale > 0.f)) return FRESCO_EINVAL;
+    if (workspace_bytes < attn_ws_bytes(n_groups, H, M, D)) return FRESCO_EWORKSPACE;
+    hipStream_t st = as_stream(stream);
+    if (dtype == FRESCO_BF16)
+        return attn_launch_t<bf16_t>(q, k, v, kv_rows, out, workspace, B, H, Lq, D, n_groups, M, group_rows, scale,
+                                     diag_bias, q_ld, kv_ld, st);
+    return attn_launch_t<half_t>(q, k, v, kv_rows, out, workspace, B, H, Lq, D, n_groups, M, group_rows, scale, diag_bias,
+                                 q_ld, kv_ld, st);
+}
+
+extern "C" int fresco_attn_fwd_ld(const void* q, const void* k, const void* v, const int32_t* kv_rows,
+                                  void* out, void* workspace, size_t workspace_bytes, int B, int H,
+                                  int Lq, int D, int n_groups, int M, int64_t group_rows, float scale,
+                                  float diag_bias, int64_t q_ld, int64_t kv_ld, void* stream) {
+    return fresco_attn_fwd_dt(q, k, v, kv_rows, out, workspace, workspace_bytes, B, H, Lq, D, n_groups, M, group_rows,
+                              scale, diag_bias, q_ld, kv_ld, FRESCO_F16, stream);
 }
 
 namespace fresco {
@@ -1347,7 +1425,7 @@ static int launch_kvproj_attn(const half_t* q, const half_t* x, int64_t x_ld, co
         hipLaunchKernelGGL((kvproj_pack_kernel<KIN, D>), dim3((nT + T - 1) / T, 2 * (H * D / 160), n_groups), dim3(320), lds,
                            st, x, x_ld, x_rows, Wk, Wv, img, ktmax, H, M, nT);
     }
-    return launch_flash_auto<D>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
+    return launch_flash_auto<half_t, D>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
 }
 }  // namespace fresco
 

@@ -43,6 +43,23 @@ constexpr float NOMAX_THR = 14.0f;
 // keys ALIGNED to the query (logit = bound) both forms sit at the same error, set by P's own fp16 rounding.  Round 2
 // used 16: N(0,1) q, k (bound up to 23) then ran the exact pass on every workgroup, 11 % slower (r03_ab_variants.txt).
 constexpr float FOLD_MAX = 24.0f;
+// Whether an element type folds the scale at all.  bf16 does not: one bf16 rounding of c*q perturbs an exponent by up to
+// 2^-9 c|q||k| (log2 units), 8x the fp16 figure.  Measured (tools/fold_margin.py --dtype bf16: the same CPU emulation with
+// bf16 operands, bf16 P and m_run on the bf16 grid, worst error as a fraction of the bf16 bar 2^-7 (rms(v) + |ref|) of
+// tests/test_gpu_bf16_attention.py), folded / exact: keys at 6 x N(0,1), (200, 333): D = 40 3.72 / 0.69, D = 80 3.66 / 0.56;
+// N(0,1) keys by bound bucket: (4, 8] 0.018 / 0.017, (8, 16] 0.044 / 0.026, (16, 24] 0.40 / 0.11, (24, 32] 0.52 / 0.13,
+// (32, 48] 1.11 / 0.30, > 48 1.52 / 0.32.  A fold limit near the fp16 one would cost a factor 4 of the bar's margin, one
+// that costs nothing (<= 8) would rarely be met by N(0,1)-scale activations (bound 8 - 23 at D = 40) and would put a
+// second, folded form of every pass into the bf16 instantiations.  So they keep Q exact and multiply every score by c in
+// fp32: flash_body's "exact" pass unconditionally, and the same multiplication in flash_body_halves.
+template <typename T>
+struct FoldCfg {
+    static constexpr bool ENABLE = true;
+};
+template <>
+struct FoldCfg<bf16_t> {
+    static constexpr bool ENABLE = false;
+};
 
 static inline int ntiles_of(int M) { return (M + 63) / 64; }
 

@@ -7,6 +7,9 @@
 typedef _Float16 half_t;
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16_t;
+typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -57,6 +60,48 @@ static inline T* carve(char*& p, size_t count) {
     p += align_up(count * sizeof(T), 256);
     return r;
 }
+
+// Element type of the 16-bit MFMA kernels (attn.hip, proj.hip, temporal.hip): fp16 or bf16.  The two share operand and
+// accumulator lane maps on gfx950, so staging, swizzles and the packed images are common; what differs is the fragment
+// types, the MFMA instructions, the conversions (round to nearest even in both) and the bit pattern of 1.0.
+template <typename T>
+struct Elem;
+template <>
+struct Elem<half_t> {
+    typedef half_t scalar;
+    typedef half4_t x4;
+    typedef half8_t x8;
+    static constexpr int CODE = FRESCO_F16;
+    static constexpr unsigned ONE_BITS = 0x3C00u;
+    static __device__ __forceinline__ floatx16 mfma32x32x16(x8 a, x8 b, floatx16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ floatx4 mfma16x16x32(x8 a, x8 b, floatx4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ floatx4 mfma16x16x16(x4 a, x4 b, floatx4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ scalar from_float(float f) { return (scalar)f; }
+};
+template <>
+struct Elem<bf16_t> {
+    typedef bf16_t scalar;
+    typedef bf16x4_t x4;
+    typedef bf16x8_t x8;
+    static constexpr int CODE = FRESCO_BF16;
+    static constexpr unsigned ONE_BITS = 0x3F80u;
+    static __device__ __forceinline__ floatx16 mfma32x32x16(x8 a, x8 b, floatx16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ floatx4 mfma16x16x32(x8 a, x8 b, floatx4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ floatx4 mfma16x16x16(x4 a, x4 b, floatx4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ scalar from_float(float f) { return (scalar)f; }  // v_cvt_pk_bf16_f32
+};
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

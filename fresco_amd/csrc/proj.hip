@@ -1,4 +1,4 @@
-// Fused linear projections of the attention processor (reference: attn.to_q / to_k / to_v / to_out[0],
+// Fused linear projections of the attention processor, fp16 or bf16 operands with fp32 accumulation (reference: attn.to_q / to_k / to_v / to_out[0],
 // src/diffusion_hacked.py:201, 214-215, 260-261, 375):   out_j = x W_j^T (+ b_j),  j < nw <= 3.
 //
 // The reference issues one GEMM per projection; each re-reads x and, for M = B*HW rows against 320 or
@@ -34,6 +34,7 @@
 // HBM-bound in that phase: 59.0 -> 58.8 (profiles/r06_ab_proj_x_staging.txt; the old form is in the commit history).
 #include "common.h"
 #include "lds_dma.h"
+#include <type_traits>
 
 namespace fresco {
 
@@ -65,12 +66,14 @@ struct ProjCfg {
     static constexpr int BIAS_OFF = RING_BYTES + NWV * XST;  // [nw][N] halfs follow
 };
 
-template <int K, int NWV>
-__global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
-    const half_t* __restrict__ x, int64_t x_ld, const int32_t* __restrict__ x_rows, const half_t* __restrict__ W0,
-    const half_t* __restrict__ W1, const half_t* __restrict__ W2, const half_t* __restrict__ b0, const half_t* __restrict__ b1,
-    const half_t* __restrict__ b2, half_t* __restrict__ out0, half_t* __restrict__ out1, half_t* __restrict__ out2,
+// The body of linear_kernel / linear_bf16_kernel (T = half_t / bf16_t: same staging, same MFMA order, fp32 accumulation)
+template <typename T, int K, int NWV>
+__device__ __forceinline__ void linear_body(
+    const T* __restrict__ x, int64_t x_ld, const int32_t* __restrict__ x_rows, const T* __restrict__ W0,
+    const T* __restrict__ W1, const T* __restrict__ W2, const T* __restrict__ b0, const T* __restrict__ b1,
+    const T* __restrict__ b2, T* __restrict__ out0, T* __restrict__ out1, T* __restrict__ out2,
     int64_t ld0, int64_t ld1, int64_t ld2, int M, int N, int nF, int tiles_per_split) {
+    typedef typename Elem<T>::x8 X8;
     using Cfg = ProjCfg<K, NWV>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -84,7 +87,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
     // for W below) so that a lane's fragments are CONSECUTIVE in memory: within a K chunk, half hi of the
     // wave takes k = hi*KC/2 + 8*ks .. +7 -- 160 contiguous bytes per lane and chunk instead of 16 out of
     // every 32.
-    half8_t xf[Cfg::NXF];
+    X8 xf[Cfg::NXF];
     // A-tile row (lane & 31) is fed with weight row swap_bits_2_3(lane & 31): the 16 accumulator registers
     // of a lane then cover features 8*hi + (0..7) and 16 + 8*hi + (0..7) of its 32-row half of the tile
     const int frow = (l31 & 0x13) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
@@ -153,18 +156,18 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
             dst[j] = r * Cfg::XROW + dc * 16;
         }
         // (plain macros, not lambdas over array references: hipcc keeps such arrays in scratch memory)
-#define PROJ_LOAD_CHUNK(KCI, T)                                                              \
+#define PROJ_LOAD_CHUNK(KCI, TT)                                                             \
     _Pragma("unroll") for (int j = 0; j < Cfg::XPL; ++j)                                      \
-        T[j] = *reinterpret_cast<const xu4_t*>(x + ((int64_t)src16[j] << 3) + (KCI) * Cfg::KC);
-#define PROJ_FLUSH_CHUNK(KCI, T)                                                             \
+        TT[j] = *reinterpret_cast<const xu4_t*>(x + ((int64_t)src16[j] << 3) + (KCI) * Cfg::KC);
+#define PROJ_FLUSH_CHUNK(KCI, TT)                                                            \
     {                                                                                        \
         _Pragma("unroll") for (int j = 0; j < Cfg::XPL; ++j)                                  \
-            *reinterpret_cast<xu4_t*>(xst + dst[j]) = T[j];                                   \
+            *reinterpret_cast<xu4_t*>(xst + dst[j]) = TT[j];                                  \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                               \
         __builtin_amdgcn_wave_barrier();                                                     \
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");                               \
         _Pragma("unroll") for (int ks = 0; ks < Cfg::KS; ++ks)                                \
-            xf[(KCI) * Cfg::KS + ks] = *reinterpret_cast<const half8_t*>(                     \
+            xf[(KCI) * Cfg::KS + ks] = *reinterpret_cast<const X8*>(                     \
                 xst + l31 * Cfg::XROW + (hi * (Cfg::KC / 2) + ks * 8) * 2);                   \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                               \
         __builtin_amdgcn_wave_barrier(); /* the region is rewritten by the next chunk */     \
@@ -195,14 +198,14 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
 #undef PROJ_FLUSH_CHUNK
     }
     // biases -> LDS once (a global load inside the tile loop would make the compiler drain vmcnt there, DMA included)
-    half_t* bias_s = reinterpret_cast<half_t*>(smem + Cfg::BIAS_OFF);
+    T* bias_s = reinterpret_cast<T*>(smem + Cfg::BIAS_OFF);
     const bool has_bias = b0 || b1 || b2;
     if (has_bias) {
         const int nwN = (nF / tiles_per_out) * N;
         for (int i = tid; i < nwN; i += NWV * 64) {
             const int jb = i / N;
-            const half_t* bp = jb == 0 ? b0 : (jb == 1 ? b1 : b2);
-            bias_s[i] = bp ? bp[i - jb * N] : (half_t)0.f;
+            const T* bp = jb == 0 ? b0 : (jb == 1 ? b1 : b2);
+            bias_s[i] = bp ? bp[i - jb * N] : (T)0.f;
         }
     }
     char* scr = smem + Cfg::RING_BYTES + wave * Cfg::XST;  // (the wave's x staging region, free by now)
@@ -222,16 +225,16 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
             {   // weight fragments are read PF MFMAs ahead of their use (hipcc's own schedule is read -> wait(0) -> MFMA per
                 // fragment; r03: 60.7 -> 55.6 us for the L3 q,k,v launch, profiles/r03_ab_variants.txt)
                 constexpr int NFR = Cfg::KS * 2, PF = 4;
-                half8_t fr[NFR];
+                X8 fr[NFR];
 #pragma unroll
                 for (int i = 0; i < PF; ++i)
-                    fr[i] = *reinterpret_cast<const half8_t*>(wr + (i & 1) * 32 * Cfg::ROWB + (i >> 1) * 16);
+                    fr[i] = *reinterpret_cast<const X8*>(wr + (i & 1) * 32 * Cfg::ROWB + (i >> 1) * 16);
 #pragma unroll
                 for (int i = 0; i < NFR; ++i) {
                     if (i + PF < NFR)
-                        fr[i + PF] = *reinterpret_cast<const half8_t*>(wr + ((i + PF) & 1) * 32 * Cfg::ROWB + ((i + PF) >> 1) * 16);
+                        fr[i + PF] = *reinterpret_cast<const X8*>(wr + ((i + PF) & 1) * 32 * Cfg::ROWB + ((i + PF) >> 1) * 16);
                     const int ks = i >> 1, t = i & 1;
-                    acc[t][ks & 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[i], xf[kc * Cfg::KS + ks], acc[t][ks & 1], 0, 0, 0);
+                    acc[t][ks & 1] = Elem<T>::mfma32x32x16(fr[i], xf[kc * Cfg::KS + ks], acc[t][ks & 1]);
                 }
                 __builtin_amdgcn_sched_group_barrier(0x100, PF, 0);  // PF LDS reads up front,
 #pragma unroll
@@ -246,9 +249,9 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
             }
             slot = slot == Cfg::NBUF - 1 ? 0 : slot + 1;
         }
-        // epilogue of the feature tile: + bias, fp16, transposed through the wave's LDS scratch: lane (row, hi) holds
+        // epilogue of the feature tile: + bias, one rounding to T, transposed through the wave's LDS scratch: lane (row, hi) holds
         // the 16-byte chunks 2*c4 + hi of its row; store instruction i then writes rows 8i .. 8i+7 as whole lines
-        half_t* op = out0;
+        T* op = out0;
         int64_t ld = ld0;
         if (j == 1) { op = out1; ld = ld1; }
         if (j == 2) { op = out2; ld = ld2; }
@@ -256,16 +259,16 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
-                half8_t w;
+                X8 w;
                 float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 if (has_bias) {
-                    const half8_t b8 = *reinterpret_cast<const half8_t*>(bias_s + j * N + col + t * 32 + half * 16 + hi * 8);
+                    const X8 b8 = *reinterpret_cast<const X8*>(bias_s + j * N + col + t * 32 + half * 16 + hi * 8);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) bv[e] = (float)b8[e];
                 }
 #pragma unroll
-                for (int e = 0; e < 8; ++e) w[e] = (half_t)(acc[t][0][half * 8 + e] + acc[t][1][half * 8 + e] + bv[e]);
-                *reinterpret_cast<half8_t*>(scr + l31 * Cfg::OROW + ((t * 2 + half) * 2 + hi) * 16) = w;
+                for (int e = 0; e < 8; ++e) w[e] = (T)(acc[t][0][half * 8 + e] + acc[t][1][half * 8 + e] + bv[e]);
+                *reinterpret_cast<X8*>(scr + l31 * Cfg::OROW + ((t * 2 + half) * 2 + hi) * 16) = w;
             }
         {
             const int row0 = blockIdx.x * (NWV * 32) + wave * 32;
@@ -276,8 +279,8 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
                 // (keeps the 64-bit row addresses of the four stores INSIDE the tile loop: hoisted, they cost the K = 640
                 // instantiation -- 160 resident x registers -- a spill that is reloaded in every tile's store path)
                 asm volatile("" : "+v"(r));
-                const half8_t w = *reinterpret_cast<const half8_t*>(scr + r * Cfg::OROW + ch * 16);
-                if (row0 + r < M) *reinterpret_cast<half8_t*>(op + (int64_t)(row0 + r) * ld + col + ch * 8) = w;
+                const X8 w = *reinterpret_cast<const X8*>(scr + r * Cfg::OROW + ch * 16);
+                if (row0 + r < M) *reinterpret_cast<X8*>(op + (int64_t)(row0 + r) * ld + col + ch * 8) = w;
             }
         }
         col += Cfg::TF;
@@ -288,14 +291,37 @@ __global__ __launch_bounds__(NWV * 64, 2) void linear_kernel(
     }
 }
 
-template <int K, int NWV>
-static int launch_linear(const half_t* x, int64_t x_ld, const int32_t* x_rows, const half_t* const* W, const half_t* const* bias,
-                         half_t* out0, half_t* out1, half_t* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M,
+#define FRESCO_LINEAR_KERNEL(NAME, T)                                                                                  \
+    template <int K, int NWV>                                                                                          \
+    __global__ __launch_bounds__(NWV * 64, 2) void NAME(                                                               \
+        const T* __restrict__ x, int64_t x_ld, const int32_t* __restrict__ x_rows, const T* __restrict__ W0,            \
+        const T* __restrict__ W1, const T* __restrict__ W2, const T* __restrict__ b0, const T* __restrict__ b1,         \
+        const T* __restrict__ b2, T* __restrict__ out0, T* __restrict__ out1, T* __restrict__ out2, int64_t ld0,        \
+        int64_t ld1, int64_t ld2, int M, int N, int nF, int tiles_per_split) {                                         \
+        linear_body<T, K, NWV>(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, M, N, nF,      \
+                               tiles_per_split);                                                                       \
+    }
+FRESCO_LINEAR_KERNEL(linear_kernel, half_t)
+FRESCO_LINEAR_KERNEL(linear_bf16_kernel, bf16_t)
+#undef FRESCO_LINEAR_KERNEL
+
+template <typename T, int K, int NWV>
+static auto linear_kernel_of() {
+    if constexpr (std::is_same<T, bf16_t>::value)
+        return &linear_bf16_kernel<K, NWV>;
+    else
+        return &linear_kernel<K, NWV>;
+}
+
+template <typename T, int K, int NWV>
+static int launch_linear(const T* x, int64_t x_ld, const int32_t* x_rows, const T* const* W, const T* const* bias,
+                         T* out0, T* out1, T* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M,
                          int N, hipStream_t st) {
     using Cfg = ProjCfg<K, NWV>;
     const int lds_bytes = Cfg::BIAS_OFF + nw * N * 2;
     if (lds_bytes > 160 * 1024) return FRESCO_EUNSUPPORTED;
-    if (int rc = allow_dyn_lds(&linear_kernel<K, NWV>, lds_bytes)) return rc;
+    auto kern = linear_kernel_of<T, K, NWV>();
+    if (int rc = allow_dyn_lds(kern, lds_bytes)) return rc;
     const int nF = nw * N / Cfg::TF;
     const int row_blocks = (M + NWV * 32 - 1) / (NWV * 32);
     // enough workgroups for two rounds of the 256 CUs; every extra split re-reads x once
@@ -305,7 +331,7 @@ static int launch_linear(const half_t* x, int64_t x_ld, const int32_t* x_rows, c
     const int tiles_per_split = (nF + splits - 1) / splits;
     splits = (nF + tiles_per_split - 1) / tiles_per_split;
     ProfScope ps(FRESCO_PROF_LINEAR, M, N, K, nw, st);
-    hipLaunchKernelGGL((linear_kernel<K, NWV>), dim3(row_blocks, splits), dim3(NWV * 64), lds_bytes, st, x, x_ld, x_rows, W[0], W[1],
+    hipLaunchKernelGGL(kern, dim3(row_blocks, splits), dim3(NWV * 64), lds_bytes, st, x, x_ld, x_rows, W[0], W[1],
                        W[2], bias[0], bias[1], bias[2], out0, out1, out2, ld0, ld1, ld2, M, N, nF, tiles_per_split);
     return check_launch();
 }
@@ -314,9 +340,25 @@ static int launch_linear(const half_t* x, int64_t x_ld, const int32_t* x_rows, c
 
 using namespace fresco;
 
+template <typename T>
+static int linear_launch_t(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1, const void* W2,
+                           const void* b0, const void* b1, const void* b2, void* out0, void* out1, void* out2, int64_t ld0,
+                           int64_t ld1, int64_t ld2, int nw, int M, int N, int K, hipStream_t st) {
+    const T* xh = static_cast<const T*>(x);
+    const T* wh[3] = {static_cast<const T*>(W0), static_cast<const T*>(W1), static_cast<const T*>(W2)};
+    const T* bh[3] = {static_cast<const T*>(b0), static_cast<const T*>(b1), static_cast<const T*>(b2)};
+    T* o0 = static_cast<T*>(out0);
+    T* o1 = static_cast<T*>(out1);
+    T* o2 = static_cast<T*>(out2);
+    if (K == 320) return launch_linear<T, 320, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, st);
+    return launch_linear<T, 640, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, st);
+}
+
 static int linear_dispatch(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1,
                            const void* W2, const void* b0, const void* b1, const void* b2, void* out0, void* out1,
-                           void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, void* stream) {
+                           void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, int dtype,
+                           void* stream) {
+    if (dtype != FRESCO_F16 && dtype != FRESCO_BF16) return FRESCO_EINVAL;
     if (!x || !W0 || !out0 || nw < 1 || nw > 3 || M <= 0 || N <= 0 || K <= 0) return FRESCO_EINVAL;
     if ((nw > 1 && (!out1 || !W1)) || (nw > 2 && (!out2 || !W2))) return FRESCO_EINVAL;
     if (x_ld < K || x_ld % 8 != 0) return FRESCO_EINVAL;
@@ -325,20 +367,15 @@ static int linear_dispatch(const void* x, int64_t x_ld, const int32_t* x_rows, c
     if (N % 64 != 0 || (K != 320 && K != 640)) return FRESCO_EUNSUPPORTED;
     if ((int64_t)(M + 127) / 128 > 0x7fffffff) return FRESCO_EUNSUPPORTED;
     hipStream_t st = as_stream(stream);
-    const half_t* xh = static_cast<const half_t*>(x);
-    const half_t* wh[3] = {static_cast<const half_t*>(W0), static_cast<const half_t*>(W1), static_cast<const half_t*>(W2)};
-    const half_t* bh[3] = {static_cast<const half_t*>(b0), static_cast<const half_t*>(b1), static_cast<const half_t*>(b2)};
-    half_t* o0 = static_cast<half_t*>(out0);
-    half_t* o1 = static_cast<half_t*>(out1);
-    half_t* o2 = static_cast<half_t*>(out2);
-    if (K == 320) return launch_linear<320, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, st);
-    return launch_linear<640, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, st);
+    if (dtype == FRESCO_BF16)
+        return linear_launch_t<bf16_t>(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, st);
+    return linear_launch_t<half_t>(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, st);
 }
 
 extern "C" int fresco_linear(const void* x, int64_t x_ld, const void* W0, const void* W1, const void* W2,
                              const void* b0, const void* b1, const void* b2, void* out0, void* out1, void* out2,
                              int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, void* stream) {
-    return linear_dispatch(x, x_ld, nullptr, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, stream);
+    return linear_dispatch(x, x_ld, nullptr, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, FRESCO_F16, stream);
 }
 
 extern "C" int fresco_linear_rows(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1,
@@ -346,5 +383,23 @@ extern "C" int fresco_linear_rows(const void* x, int64_t x_ld, const int32_t* x_
                                   void* out1, void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N,
                                   int K, void* stream) {
     if (!x_rows) return FRESCO_EINVAL;
-    return linear_dispatch(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, stream);
+    return linear_dispatch(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, FRESCO_F16, stream);
+}
+
+extern "C" int fresco_linear_dt(const void* x, int64_t x_ld, const void* W0, const void* W1, const void* W2,
+                                const void* b0, const void* b1, const void* b2, void* out0, void* out1, void* out2,
+                                int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, int dtype,
+                                void* stream) {
+    return linear_dispatch(x, x_ld, nullptr, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, dtype,
+                           stream);
+}
+
+extern "C" int fresco_linear_rows_dt(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1,
+                                     const void* W2, const void* b0, const void* b1, const void* b2, void* out0,
+                                     void* out1, void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M,
+                                     int N, int K, int dtype, void* stream) {
+    if (dtype != FRESCO_F16 && dtype != FRESCO_BF16) return FRESCO_EINVAL;
+    if (!x_rows) return FRESCO_EINVAL;
+    return linear_dispatch(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, dtype,
+                           stream);
 }

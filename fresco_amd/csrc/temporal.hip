@@ -21,6 +21,7 @@
 // (all-to-all, fresco_temporal_unpack).
 #include "common.h"
 #include "lds_dma.h"
+#include <type_traits>
 
 namespace fresco {
 
@@ -50,11 +51,13 @@ typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 //                    with A = ones gives the softmax denominator in every lane
 //   O                scaled, fp16, written over the unit's own Q segment (nobody else reads it); the block
 //                    then stores whole rows.
-template <int D, int KT>
-__global__ __launch_bounds__(512) void temporal_mfma_kernel(
-    const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ v,
-    const int64_t* __restrict__ fwd_map, const uint8_t* __restrict__ mask, half_t* __restrict__ out,
+template <typename T, int D, int KT>
+__device__ __forceinline__ void temporal_mfma_body(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
+    const int64_t* __restrict__ fwd_map, const uint8_t* __restrict__ mask, T* __restrict__ out,
     int N, int HW, int H, int PB, int chunk, float scale_log2, int64_t q_ld, int64_t k_ld, int64_t v_ld, int packed) {
+    typedef typename Elem<T>::x4 X4;
+    typedef typename Elem<T>::x8 X8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NK32 = (D + 31) / 32;  // k-steps of the score product
     constexpr int NDT = (D + 15) / 16;   // 16-wide output tiles
@@ -103,7 +106,7 @@ __global__ __launch_bounds__(512) void temporal_mfma_kernel(
         for (int r = wave; r < R; r += nwaves) {
             int ro = __builtin_amdgcn_readfirstlane(rows[r]);
             if (ro < 0) ro = 0;  // rows without a trajectory: load something valid, never stored
-            const half_t* src[3] = {q + (int64_t)ro * q_ld + col0, k + (int64_t)ro * k_ld + col0,
+            const T* src[3] = {q + (int64_t)ro * q_ld + col0, k + (int64_t)ro * k_ld + col0,
                                     v + (int64_t)ro * v_ld + col0};
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
@@ -137,8 +140,8 @@ __global__ __launch_bounds__(512) void temporal_mfma_kernel(
             kg[kt][r] = KT == 1 ? rel % N : min(rel, N - 1);
         }
     }
-    const half4_t ones = {(half_t)1.f, (half_t)1.f, (half_t)1.f, (half_t)1.f};
-    const half8_t zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    const X4 ones = {(T)1.f, (T)1.f, (T)1.f, (T)1.f};
+    const X8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
 
     {
         for (int tb = 0; tb < ntiles; ++tb) {
@@ -155,17 +158,17 @@ __global__ __launch_bounds__(512) void temporal_mfma_kernel(
                 const char* kh = ks + h * D * 2;
                 const char* vh = vs + h * D * 2;
                 // every LDS read of the unit is issued before the first product
-                half8_t bq[NK32], ak[KT][NK32];
+                X8 bq[NK32], ak[KT][NK32];
 #pragma unroll
                 for (int s = 0; s < NK32; ++s) {
                     const int ch = s * 4 + lj;  // chunks past the head's D/8: a zero on the Q side is enough
-                    const half8_t tq = *reinterpret_cast<const half8_t*>(qseg + min(ch, D / 8 - 1) * 16);
+                    const X8 tq = *reinterpret_cast<const X8*>(qseg + min(ch, D / 8 - 1) * 16);
                     bq[s] = ch < D / 8 ? tq : zero8;
 #pragma unroll
                     for (int kt = 0; kt < KT; ++kt)
-                        ak[kt][s] = *reinterpret_cast<const half8_t*>(kh + koff[kt] + min(ch, D / 8 - 1) * 16);
+                        ak[kt][s] = *reinterpret_cast<const X8*>(kh + koff[kt] + min(ch, D / 8 - 1) * 16);
                 }
-                half4_t av[NDT][KT];  // V^T: channel d = dt*16 + i (channels past D: any finite row, never stored)
+                X4 av[NDT][KT];  // V^T: channel d = dt*16 + i (channels past D: any finite row, never stored)
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt) {
                     const int d = min(dt * 16 + li, D - 1);
@@ -173,7 +176,7 @@ __global__ __launch_bounds__(512) void temporal_mfma_kernel(
                     for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            av[dt][kt][r] = *reinterpret_cast<const half_t*>(vh + voff[kt][r] + d * 2);
+                            av[dt][kt][r] = *reinterpret_cast<const T*>(vh + voff[kt][r] + d * 2);
                 }
                 float sc[KT][4];
                 float m = -INFINITY;
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(512) void temporal_mfma_kernel(
                     floatx4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int s = 0; s < NK32; ++s)
-                        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ak[kt][s], bq[s], acc, 0, 0, 0);
+                        acc = Elem<T>::mfma16x16x32(ak[kt][s], bq[s], acc);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {  // acc[r] = S^T[key 4j + r][query i]
                         sc[kt][r] = ok[kt][r] ? acc[r] * scale_log2 : -INFINITY;
@@ -193,22 +196,22 @@ __global__ __launch_bounds__(512) void temporal_mfma_kernel(
                 m = fmaxf(m, __shfl_xor(m, 32, 64));
                 // (a query whose keys are all masked: exp2(-inf - -inf) = NaN, as the reference's softmax of an
                 // all -inf row)
-                half4_t pb[KT];
+                X4 pb[KT];
 #pragma unroll
                 for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) pb[kt][r] = (half_t)__builtin_amdgcn_exp2f(sc[kt][r] - m);
+                    for (int r = 0; r < 4; ++r) pb[kt][r] = (T)__builtin_amdgcn_exp2f(sc[kt][r] - m);
                 floatx4 den = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kt = 0; kt < KT; ++kt)
-                    den = __builtin_amdgcn_mfma_f32_16x16x16f16(ones, pb[kt], den, 0, 0, 0);
+                    den = Elem<T>::mfma16x16x16(ones, pb[kt], den);
                 floatx4 o[NDT];
 #pragma unroll
                 for (int dt = 0; dt < NDT; ++dt) {
                     o[dt] = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                     for (int kt = 0; kt < KT; ++kt)
-                        o[dt] = __builtin_amdgcn_mfma_f32_16x16x16f16(av[dt][kt], pb[kt], o[dt], 0, 0, 0);
+                        o[dt] = Elem<T>::mfma16x16x16(av[dt][kt], pb[kt], o[dt]);
                 }
                 const float inv = __builtin_amdgcn_rcpf(den[0]);
                 // O^T[d = dt*16 + 4j + r][query i]: 4 consecutive channels of the query's row
@@ -217,10 +220,10 @@ __global__ __launch_bounds__(512) void temporal_mfma_kernel(
                     for (int dt = 0; dt < NDT; ++dt) {
                         const int d0 = dt * 16 + 4 * lj;
                         if (d0 < D) {
-                            half4_t ov;
+                            X4 ov;
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) ov[r] = (half_t)(o[dt][r] * inv);
-                            *reinterpret_cast<half4_t*>(qseg + d0 * 2) = ov;
+                            for (int r = 0; r < 4; ++r) ov[r] = (T)(o[dt][r] * inv);
+                            *reinterpret_cast<X4*>(qseg + d0 * 2) = ov;
                         }
                     }
                 }
@@ -232,7 +235,7 @@ __global__ __launch_bounds__(512) void temporal_mfma_kernel(
         for (int r = wave; r < R; r += nwaves) {
             const int ro = __builtin_amdgcn_readfirstlane(rows[r]);
             if (ro < 0) continue;
-            half_t* dst = out + (int64_t)ro * C + col0;
+            T* dst = out + (int64_t)ro * C + col0;
             for (int part = 0; part < ppr; ++part) {
                 const int cc = part * 64 + lane;
                 if (cc < CC)
@@ -243,14 +246,36 @@ __global__ __launch_bounds__(512) void temporal_mfma_kernel(
     }
 }
 
+#define FRESCO_TEMPORAL_MFMA_KERNEL(NAME, T)                                                                        \
+    template <int D, int KT>                                                                                        \
+    __global__ __launch_bounds__(512) void NAME(                                                                    \
+        const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const int64_t* __restrict__ fwd_map, \
+        const uint8_t* __restrict__ mask, T* __restrict__ out, int N, int HW, int H, int PB, int chunk,              \
+        float scale_log2, int64_t q_ld, int64_t k_ld, int64_t v_ld, int packed) {                                   \
+        temporal_mfma_body<T, D, KT>(q, k, v, fwd_map, mask, out, N, HW, H, PB, chunk, scale_log2, q_ld, k_ld, v_ld,  \
+                                     packed);                                                                       \
+    }
+FRESCO_TEMPORAL_MFMA_KERNEL(temporal_mfma_kernel, half_t)
+FRESCO_TEMPORAL_MFMA_KERNEL(temporal_mfma_bf16_kernel, bf16_t)
+#undef FRESCO_TEMPORAL_MFMA_KERNEL
+
 // ---------------------------------------------------------------------------------------------------------------
 // Longer clips (N > 32): one work item per (trajectory, query frame, head) on the vector ALUs, running-maximum
 // softmax over the frames; same staging of whole rows through LDS.
-template <int D>
-__global__ __launch_bounds__(256, 2) void temporal_attn_kernel(
-    const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ v,
-    const int64_t* __restrict__ fwd_map, const uint8_t* __restrict__ mask, half_t* __restrict__ out,
+// q . k of two packed elements on top of `acc`: v_dot2_f32_f16 for fp16; bf16 widens (a shift) and uses two fmas
+__device__ __forceinline__ float dot2(half2_t a, half2_t b, float acc) { return __builtin_amdgcn_fdot2(a, b, acc, false); }
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float dot2(bf16x2_t a, bf16x2_t b, float acc) {
+    return fmaf((float)a[1], (float)b[1], fmaf((float)a[0], (float)b[0], acc));
+}
+
+template <typename T, int D>
+__device__ __forceinline__ void temporal_attn_body(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
+    const int64_t* __restrict__ fwd_map, const uint8_t* __restrict__ mask, T* __restrict__ out,
     int N, int HW, int H, int PB, int chunk, float scale_log2, int64_t q_ld, int64_t k_ld, int64_t v_ld, int packed) {
+    typedef T X2 __attribute__((ext_vector_type(2)));
+    typedef typename Elem<T>::x8 X8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int C = H * D;
     const int CC = C / 8;  // 16-byte chunks per row
@@ -259,9 +284,9 @@ __global__ __launch_bounds__(256, 2) void temporal_attn_kernel(
     const int tid = threadIdx.x;
     const int R = PB * N;  // staged rows per tensor
 
-    half_t* qs = reinterpret_cast<half_t*>(smem);
-    half_t* ks = qs + (size_t)R * C;
-    half_t* vs = ks + (size_t)R * C;
+    T* qs = reinterpret_cast<T*>(smem);
+    T* ks = qs + (size_t)R * C;
+    T* vs = ks + (size_t)R * C;
     int* rows = reinterpret_cast<int*>(vs + (size_t)R * C);  // [PB][N] row of frame g (-1: no such trajectory)
     uint8_t* msk = reinterpret_cast<uint8_t*>(rows + R);     // [PB][N][N] the trajectories' mask rows
 
@@ -308,31 +333,31 @@ __global__ __launch_bounds__(256, 2) void temporal_attn_kernel(
         const int pl = w / (H * N);
         const int p = p0 + pl;
         if (p >= HW) continue;
-        half_t* qseg = qs + (size_t)(pl * N + f) * C + h * D;
-        half2_t qh[D / 2];
+        T* qseg = qs + (size_t)(pl * N + f) * C + h * D;
+        X2 qh[D / 2];
 #pragma unroll
         for (int j = 0; j < D / 8; ++j) {
-            const half8_t t = *reinterpret_cast<const half8_t*>(qseg + j * 8);
+            const X8 t = *reinterpret_cast<const X8*>(qseg + j * 8);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) qh[j * 4 + e] = half2_t{t[2 * e], t[2 * e + 1]};
+            for (int e = 0; e < 4; ++e) qh[j * 4 + e] = X2{t[2 * e], t[2 * e + 1]};
         }
         float acc[D];
 #pragma unroll
         for (int d = 0; d < D; ++d) acc[d] = 0.f;
         float m_run = -1e30f, l_run = 0.f;
         const uint8_t* mrow = msk + (pl * N + f) * N;
-        const half_t* kbase = ks + (size_t)pl * N * C + h * D;
-        const half_t* vbase = vs + (size_t)pl * N * C + h * D;
+        const T* kbase = ks + (size_t)pl * N * C + h * D;
+        const T* vbase = vs + (size_t)pl * N * C + h * D;
         for (int g = 0; g < N; ++g) {
             if (mrow[g] == 0) continue;
             float s0 = 0.f, s1 = 0.f;  // two chains: even / odd 16-byte chunks
 #pragma unroll
             for (int j = 0; j < D / 8; ++j) {
-                const half8_t t = *reinterpret_cast<const half8_t*>(kbase + (size_t)g * C + j * 8);
+                const X8 t = *reinterpret_cast<const X8*>(kbase + (size_t)g * C + j * 8);
                 float& s = (j & 1) ? s1 : s0;
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    s = __builtin_amdgcn_fdot2(qh[j * 4 + e], half2_t{t[2 * e], t[2 * e + 1]}, s, false);
+                    s = dot2(qh[j * 4 + e], X2{t[2 * e], t[2 * e + 1]}, s);
             }
             const float s = (s0 + s1) * scale_log2;
             const float m_new = fmaxf(m_run, s);
@@ -342,7 +367,7 @@ __global__ __launch_bounds__(256, 2) void temporal_attn_kernel(
             l_run = fmaf(l_run, alpha, pw);
 #pragma unroll
             for (int j = 0; j < D / 8; ++j) {
-                const half8_t t = *reinterpret_cast<const half8_t*>(vbase + (size_t)g * C + j * 8);
+                const X8 t = *reinterpret_cast<const X8*>(vbase + (size_t)g * C + j * 8);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) acc[j * 8 + e] = fmaf(acc[j * 8 + e], alpha, pw * (float)t[e]);
             }
@@ -351,10 +376,10 @@ __global__ __launch_bounds__(256, 2) void temporal_attn_kernel(
         // the result replaces this work item's own query segment (nobody else reads it)
 #pragma unroll
         for (int j = 0; j < D / 8; ++j) {
-            half8_t o;
+            X8 o;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (half_t)(acc[j * 8 + e] * inv);
-            *reinterpret_cast<half8_t*>(qseg + j * 8) = o;
+            for (int e = 0; e < 8; ++e) o[e] = (T)(acc[j * 8 + e] * inv);
+            *reinterpret_cast<X8*>(qseg + j * 8) = o;
         }
     }
     __syncthreads();
@@ -369,6 +394,18 @@ __global__ __launch_bounds__(256, 2) void temporal_attn_kernel(
             *reinterpret_cast<const uint4*>(qs + (size_t)r * C + cc * 8);
     }
 }
+
+#define FRESCO_TEMPORAL_ATTN_KERNEL(NAME, T)                                                                        \
+    template <int D>                                                                                                \
+    __global__ __launch_bounds__(256, 2) void NAME(                                                                 \
+        const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, const int64_t* __restrict__ fwd_map, \
+        const uint8_t* __restrict__ mask, T* __restrict__ out, int N, int HW, int H, int PB, int chunk,              \
+        float scale_log2, int64_t q_ld, int64_t k_ld, int64_t v_ld, int packed) {                                   \
+        temporal_attn_body<T, D>(q, k, v, fwd_map, mask, out, N, HW, H, PB, chunk, scale_log2, q_ld, k_ld, v_ld, packed); \
+    }
+FRESCO_TEMPORAL_ATTN_KERNEL(temporal_attn_kernel, half_t)
+FRESCO_TEMPORAL_ATTN_KERNEL(temporal_attn_bf16_kernel, bf16_t)
+#undef FRESCO_TEMPORAL_ATTN_KERNEL
 
 // Multi-GPU, way out: this rank's n_loc frames [f0, f0 + n_loc) of q, k, v, gathered along the trajectories
 // into per-destination ranges:  dst[(d*n_loc + fl)*chunk + c][pl][0:3C] = (q | k | v)[c*n_loc + fl][fwd_map[f0+fl][d*Pw + pl]].
@@ -402,9 +439,24 @@ __global__ __launch_bounds__(256) void temporal_pack_kernel(const half_t* __rest
     }
 }
 
-template <int D, int KT>
-static int launch_temporal_mfma(const half_t* q, const half_t* k, const half_t* v, const int64_t* fwd_map,
-                                const uint8_t* mask, half_t* out, int chunk, int N, int HW, int H, float scale,
+template <typename T, int D, int KT>
+static auto temporal_mfma_kernel_of() {
+    if constexpr (std::is_same<T, bf16_t>::value)
+        return &temporal_mfma_bf16_kernel<D, KT>;
+    else
+        return &temporal_mfma_kernel<D, KT>;
+}
+template <typename T, int D>
+static auto temporal_attn_kernel_of() {
+    if constexpr (std::is_same<T, bf16_t>::value)
+        return &temporal_attn_bf16_kernel<D>;
+    else
+        return &temporal_attn_kernel<D>;
+}
+
+template <typename T, int D, int KT>
+static int launch_temporal_mfma(const T* q, const T* k, const T* v, const int64_t* fwd_map,
+                                const uint8_t* mask, T* out, int chunk, int N, int HW, int H, float scale,
                                 int64_t q_ld, int64_t k_ld, int64_t v_ld, bool packed, hipStream_t st) {
     const int C = H * D;
     // N <= 16: one 16-row tile of 16/N trajectories per block, 4 waves share its H heads (31.5 KB of LDS at C = 320:
@@ -423,24 +475,25 @@ static int launch_temporal_mfma(const half_t* q, const half_t* k, const half_t* 
     const int RS = 16 * ((C / hsplit / 8) | 1);
     const size_t lds = (size_t)PB * N * (3 * RS + 4 + N);
     if (lds > 160 * 1024) return FRESCO_EUNSUPPORTED;
+    auto kern = temporal_mfma_kernel_of<T, D, KT>();
     if (lds > 65536) {
-        if (int rc = allow_dyn_lds(&temporal_mfma_kernel<D, KT>, (int)lds)) return rc;
+        if (int rc = allow_dyn_lds(kern, (int)lds)) return rc;
     }
     dim3 grid((HW + PB - 1) / PB, chunk, hsplit);
     ProfScope ps(FRESCO_PROF_TEMPORAL, chunk * N, HW, H, D, st);
-    hipLaunchKernelGGL((temporal_mfma_kernel<D, KT>), grid, dim3(NT), lds, st, q, k, v, fwd_map, mask, out, N, HW, H,
+    hipLaunchKernelGGL(kern, grid, dim3(NT), lds, st, q, k, v, fwd_map, mask, out, N, HW, H,
                        PB, chunk, scale * 1.4426950408889634f, q_ld, k_ld, v_ld, packed ? 1 : 0);
     return check_launch();
 }
 
-template <int D>
-static int launch_temporal(const half_t* q, const half_t* k, const half_t* v, const int64_t* fwd_map,
-                           const uint8_t* mask, half_t* out, int chunk, int N, int HW, int H, float scale,
+template <typename T, int D>
+static int launch_temporal(const T* q, const T* k, const T* v, const int64_t* fwd_map,
+                           const uint8_t* mask, T* out, int chunk, int N, int HW, int H, float scale,
                            int64_t q_ld, int64_t k_ld, int64_t v_ld, bool packed, hipStream_t st) {
     if (N <= 16)
-        return launch_temporal_mfma<D, 1>(q, k, v, fwd_map, mask, out, chunk, N, HW, H, scale, q_ld, k_ld, v_ld, packed, st);
+        return launch_temporal_mfma<T, D, 1>(q, k, v, fwd_map, mask, out, chunk, N, HW, H, scale, q_ld, k_ld, v_ld, packed, st);
     if (N <= 32)
-        return launch_temporal_mfma<D, 2>(q, k, v, fwd_map, mask, out, chunk, N, HW, H, scale, q_ld, k_ld, v_ld, packed, st);
+        return launch_temporal_mfma<T, D, 2>(q, k, v, fwd_map, mask, out, chunk, N, HW, H, scale, q_ld, k_ld, v_ld, packed, st);
     const int C = H * D;
     // LDS: Q, K and V rows of PB trajectories + the row table + the mask rows; two blocks per CU where that is possible
     const size_t per_traj = (size_t)N * C * 6 + (size_t)N * 4 + (size_t)N * N;
@@ -450,10 +503,11 @@ static int launch_temporal(const half_t* q, const half_t* k, const half_t* v, co
     const int want = (256 + N * H - 1) / (N * H);  // enough work items for every thread
     if (PB > want) PB = want;
     const size_t lds = (size_t)PB * per_traj;
-    if (int rc = allow_dyn_lds(&temporal_attn_kernel<D>, (int)(lds > 65536 ? lds : 65536))) return rc;
+    auto kern = temporal_attn_kernel_of<T, D>();
+    if (int rc = allow_dyn_lds(kern, (int)(lds > 65536 ? lds : 65536))) return rc;
     dim3 grid((HW + PB - 1) / PB, chunk);
     ProfScope ps(FRESCO_PROF_TEMPORAL, chunk * N, HW, H, D, st);
-    hipLaunchKernelGGL((temporal_attn_kernel<D>), grid, dim3(256), lds, st, q, k, v, fwd_map, mask, out, N, HW, H, PB,
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, q, k, v, fwd_map, mask, out, N, HW, H, PB,
                        chunk, scale * 1.4426950408889634f, q_ld, k_ld, v_ld, packed ? 1 : 0);
     return check_launch();
 }
@@ -462,21 +516,17 @@ static int launch_temporal(const half_t* q, const half_t* k, const half_t* v, co
 
 using namespace fresco;
 
-static int temporal_dispatch(const void* q, const void* k, const void* v, const int64_t* fwd_map,
-                             const uint8_t* mask, void* out, int chunk, int N, int HW, int H, int D, float scale,
-                             int64_t q_ld, int64_t k_ld, int64_t v_ld, bool packed, void* stream) {
-    if (!q || !k || !v || (!packed && !fwd_map) || !mask || !out) return FRESCO_EINVAL;
-    if (chunk <= 0 || N <= 0 || HW <= 0 || H <= 0 || D <= 0) return FRESCO_EINVAL;
-    const int64_t Cw = (int64_t)H * D;
-    if (q_ld < Cw || k_ld < Cw || v_ld < Cw || q_ld % 8 || k_ld % 8 || v_ld % 8) return FRESCO_EINVAL;
-    hipStream_t st = as_stream(stream);
-    const half_t* qh = static_cast<const half_t*>(q);
-    const half_t* kh = static_cast<const half_t*>(k);
-    const half_t* vh = static_cast<const half_t*>(v);
-    half_t* oh = static_cast<half_t*>(out);
+template <typename T>
+static int temporal_launch_t(const void* q, const void* k, const void* v, const int64_t* fwd_map, const uint8_t* mask,
+                             void* out, int chunk, int N, int HW, int H, int D, float scale, int64_t q_ld, int64_t k_ld,
+                             int64_t v_ld, bool packed, hipStream_t st) {
+    const T* qh = static_cast<const T*>(q);
+    const T* kh = static_cast<const T*>(k);
+    const T* vh = static_cast<const T*>(v);
+    T* oh = static_cast<T*>(out);
 #define FRESCO_T_CASE(DD) \
     case DD:              \
-        return launch_temporal<DD>(qh, kh, vh, fwd_map, mask, oh, chunk, N, HW, H, scale, q_ld, k_ld, v_ld, packed, st);
+        return launch_temporal<T, DD>(qh, kh, vh, fwd_map, mask, oh, chunk, N, HW, H, scale, q_ld, k_ld, v_ld, packed, st);
     switch (D) {
         FRESCO_T_CASE(8)
         FRESCO_T_CASE(16)
@@ -490,6 +540,21 @@ static int temporal_dispatch(const void* q, const void* k, const void* v, const 
 #undef FRESCO_T_CASE
 }
 
+static int temporal_dispatch(const void* q, const void* k, const void* v, const int64_t* fwd_map,
+                             const uint8_t* mask, void* out, int chunk, int N, int HW, int H, int D, float scale,
+                             int64_t q_ld, int64_t k_ld, int64_t v_ld, bool packed, void* stream,
+                             int dtype = FRESCO_F16) {
+    if (dtype != FRESCO_F16 && dtype != FRESCO_BF16) return FRESCO_EINVAL;
+    if (!q || !k || !v || (!packed && !fwd_map) || !mask || !out) return FRESCO_EINVAL;
+    if (chunk <= 0 || N <= 0 || HW <= 0 || H <= 0 || D <= 0) return FRESCO_EINVAL;
+    const int64_t Cw = (int64_t)H * D;
+    if (q_ld < Cw || k_ld < Cw || v_ld < Cw || q_ld % 8 || k_ld % 8 || v_ld % 8) return FRESCO_EINVAL;
+    hipStream_t st = as_stream(stream);
+    if (dtype == FRESCO_BF16)
+        return temporal_launch_t<bf16_t>(q, k, v, fwd_map, mask, out, chunk, N, HW, H, D, scale, q_ld, k_ld, v_ld, packed, st);
+    return temporal_launch_t<half_t>(q, k, v, fwd_map, mask, out, chunk, N, HW, H, D, scale, q_ld, k_ld, v_ld, packed, st);
+}
+
 extern "C" int fresco_temporal_attn(const void* q, const void* k, const void* v, const int64_t* fwd_map,
                                     const uint8_t* mask, void* out, int chunk, int N, int HW, int H,
                                     int D, float scale, void* stream) {
@@ -501,6 +566,13 @@ extern "C" int fresco_temporal_attn_ld(const void* q, const void* k, const void*
                                        const uint8_t* mask, void* out, int chunk, int N, int HW, int H, int D,
                                        float scale, int64_t q_ld, int64_t k_ld, int64_t v_ld, void* stream) {
     return temporal_dispatch(q, k, v, fwd_map, mask, out, chunk, N, HW, H, D, scale, q_ld, k_ld, v_ld, false, stream);
+}
+
+extern "C" int fresco_temporal_attn_dt(const void* q, const void* k, const void* v, const int64_t* fwd_map,
+                                       const uint8_t* mask, void* out, int chunk, int N, int HW, int H, int D,
+                                       float scale, int64_t q_ld, int64_t k_ld, int64_t v_ld, int dtype, void* stream) {
+    return temporal_dispatch(q, k, v, fwd_map, mask, out, chunk, N, HW, H, D, scale, q_ld, k_ld, v_ld, false, stream,
+                             dtype);
 }
 
 extern "C" int fresco_temporal_attn_packed(const void* qkv, const uint8_t* mask, void* out, int chunk, int N, int P,

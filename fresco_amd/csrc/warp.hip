@@ -285,6 +285,10 @@ extern "C" int fresco_adain(const void* content, const void* style, void* out, i
         hipLaunchKernelGGL((adain_kernel<half_t>), dim3(rows), dim3(256), 0, st,
                            static_cast<const half_t*>(content), static_cast<const half_t*>(style),
                            static_cast<half_t*>(out), L, eps_content, eps_style);
+    else if (dtype == FRESCO_BF16)
+        hipLaunchKernelGGL((adain_kernel<bf16_t>), dim3(rows), dim3(256), 0, st,
+                           static_cast<const bf16_t*>(content), static_cast<const bf16_t*>(style),
+                           static_cast<bf16_t*>(out), L, eps_content, eps_style);
     else if (dtype == FRESCO_F32)
         hipLaunchKernelGGL((adain_kernel<float>), dim3(rows), dim3(256), 0, st,
                            static_cast<const float*>(content), static_cast<const float*>(style),
@@ -301,6 +305,9 @@ extern "C" int fresco_chan_mean_std(const void* x, float* mean, float* stdv, int
     if (dtype == FRESCO_F16)
         hipLaunchKernelGGL((chan_mean_std_kernel<half_t>), dim3(rows), dim3(256), 0, st, static_cast<const half_t*>(x), mean,
                            stdv, L, eps);
+    else if (dtype == FRESCO_BF16)
+        hipLaunchKernelGGL((chan_mean_std_kernel<bf16_t>), dim3(rows), dim3(256), 0, st, static_cast<const bf16_t*>(x), mean,
+                           stdv, L, eps);
     else if (dtype == FRESCO_F32)
         hipLaunchKernelGGL((chan_mean_std_kernel<float>), dim3(rows), dim3(256), 0, st, static_cast<const float*>(x), mean,
                            stdv, L, eps);
@@ -311,7 +318,7 @@ extern "C" int fresco_chan_mean_std(const void* x, float* mean, float* stdv, int
 
 // ------------------------------------------------------------------------------------------------
 // (f2) DDPM step pieces of src/pipe_FRESCO.py:14-77, 212-214 as fused elementwise kernels (fp32 math,
-// fp16 / fp32 storage).  x0 = (x_t - sqrt(1-abar_t) * eps) / sqrt(abar_t), with eps optionally formed in
+// fp16 / bf16 / fp32 storage).  x0 = (x_t - sqrt(1-abar_t) * eps) / sqrt(abar_t), with eps optionally formed in
 // flight by classifier-free guidance  eps = e_u + s (e_c - e_u);  x_{t-1} = c0 x0 + c1 x_t + sigma z.
 // ------------------------------------------------------------------------------------------------
 namespace fresco {
@@ -350,6 +357,10 @@ extern "C" int fresco_ddpm_x0(const void* xt, const void* eps_uncond, const void
         hipLaunchKernelGGL((ddpm_x0_kernel<half_t>), grid, dim3(256), 0, st, (const half_t*)xt,
                            (const half_t*)eps_uncond, (const half_t*)eps_text, (half_t*)x0, (half_t*)eps_out, n,
                            guidance, sqrt_beta_prod, sqrt_alpha_prod);
+    else if (dtype == FRESCO_BF16)
+        hipLaunchKernelGGL((ddpm_x0_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)xt,
+                           (const bf16_t*)eps_uncond, (const bf16_t*)eps_text, (bf16_t*)x0, (bf16_t*)eps_out, n,
+                           guidance, sqrt_beta_prod, sqrt_alpha_prod);
     else if (dtype == FRESCO_F32)
         hipLaunchKernelGGL((ddpm_x0_kernel<float>), grid, dim3(256), 0, st, (const float*)xt,
                            (const float*)eps_uncond, (const float*)eps_text, (float*)x0, (float*)eps_out, n, guidance,
@@ -368,6 +379,9 @@ extern "C" int fresco_ddpm_prev(const void* x0, const void* xt, const void* nois
     if (dtype == FRESCO_F16)
         hipLaunchKernelGGL((ddpm_prev_kernel<half_t>), grid, dim3(256), 0, st, (const half_t*)x0, (const half_t*)xt,
                            (const half_t*)noise, (half_t*)out, n, noise_period, c_x0, c_xt, sigma);
+    else if (dtype == FRESCO_BF16)
+        hipLaunchKernelGGL((ddpm_prev_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)x0, (const bf16_t*)xt,
+                           (const bf16_t*)noise, (bf16_t*)out, n, noise_period, c_x0, c_xt, sigma);
     else if (dtype == FRESCO_F32)
         hipLaunchKernelGGL((ddpm_prev_kernel<float>), grid, dim3(256), 0, st, (const float*)x0, (const float*)xt,
                            (const float*)noise, (float*)out, n, noise_period, c_x0, c_xt, sigma);

@@ -137,14 +137,19 @@ _default_ws = _PerStreamWorkspace()
 # ---------------------------------------------------------------------------------------------
 # fused linear projections
 # ---------------------------------------------------------------------------------------------
+# element types of the 16-bit MFMA kernels (linear, attention, temporal attention) -> dtype code of the *_dt entry points
+_MFMA_DTYPES = {torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+
+
 def linear_supported(K, N, dtype):
     """shapes / dtype fresco_linear takes (SD-1.5 up_blocks.2/3 attention widths); others keep torch's GEMM"""
-    return dtype == torch.float16 and K in (320, 640) and N % 64 == 0
+    return dtype in _MFMA_DTYPES and K in (320, 640) and N % 64 == 0
 
 
 def linear(x, weights, biases=None, outs=None, x_rows=None, x_rows_trusted=False):
     """out_j = x W_j^T (+ b_j) for the 1..3 weight matrices in `weights` (each (N, K) fp16, read where it lives --
     nothing is stacked or cached), x (..., K) fp16 read once; `biases`: None or a list of (N,) fp16 / None.
+    All-bf16 operands are taken the same way (bf16 MFMA, fp32 accumulation, bf16 outputs); mixed dtypes raise.
     Returns len(weights) tensors shaped x.shape[:-1] + (N,); `outs` may supply them (dense in the last dim,
     uniformly strided rows -- e.g. the two halves of a fused K|V buffer).
     x_rows (int32, (M',)): gathered form -- output row m is the projection of x's flat row x_rows[m]; the outputs are
@@ -163,12 +168,16 @@ def linear(x, weights, biases=None, outs=None, x_rows=None, x_rows_trusted=False
     N = weights[0].shape[0]
     if not 1 <= nw <= 3 or len(biases) != nw:
         raise ValueError("linear: 1..3 weights and as many biases (or None)")
+    dt = x.dtype
+    if dt not in _MFMA_DTYPES:
+        raise ValueError("linear: x must be fp16 or bf16 (got %s)" % dt)
     for W in weights:
-        if W.dtype != torch.float16 or x.dtype != torch.float16 or tuple(W.shape) != (N, K) or not W.is_contiguous():
-            raise ValueError("linear: x (...,K) and every W (N,K) must be contiguous fp16 with matching shapes")
+        if W.dtype != dt or tuple(W.shape) != (N, K) or not W.is_contiguous():
+            raise ValueError("linear: x (...,K) and every W (N,K) must be contiguous, of one dtype (fp16 or bf16), with "
+                             "matching shapes")
     for b in biases:
-        if b is not None and (b.dtype != torch.float16 or tuple(b.shape) != (N,) or not b.is_contiguous()):
-            raise ValueError("linear: a bias must be a contiguous (N,) fp16 tensor")
+        if b is not None and (b.dtype != dt or tuple(b.shape) != (N,) or not b.is_contiguous()):
+            raise ValueError("linear: a bias must be a contiguous (N,) tensor of x's dtype")
     x2, x_ld, M = _rows(x)
     if x_rows is not None:
         _need_gpu(x_rows)
@@ -185,12 +194,12 @@ def linear(x, weights, biases=None, outs=None, x_rows=None, x_rows_trusted=False
         M = x_rows.numel()
     if outs is None:
         shape = (M, N) if x_rows is not None else x.shape[:-1] + (N,)
-        outs = [torch.empty(shape, dtype=torch.float16, device=x.device) for _ in range(nw)]
+        outs = [torch.empty(shape, dtype=dt, device=x.device) for _ in range(nw)]
     ptrs, lds = [], []
     for t in outs:
         t2, ld, rows = _rows(t)
-        if t2 is not t or rows != M or t.shape[-1] != N or t.dtype != torch.float16:
-            raise ValueError("linear: every output must be a (M,N) fp16 tensor with uniformly strided rows")
+        if t2 is not t or rows != M or t.shape[-1] != N or t.dtype != dt:
+            raise ValueError("linear: every output must be a (M,N) tensor of x's dtype with uniformly strided rows")
         ptrs.append(t.data_ptr())
         lds.append(ld)
     wp = [W.data_ptr() for W in weights] + [None] * (3 - nw)
@@ -199,12 +208,12 @@ def linear(x, weights, biases=None, outs=None, x_rows=None, x_rows_trusted=False
         ptrs.append(None)
         lds.append(0)
     if x_rows is not None:
-        rc = _lib.load().fresco_linear_rows(x2.data_ptr(), x_ld, x_rows.data_ptr(), wp[0], wp[1], wp[2], bp[0], bp[1],
-                                            bp[2], ptrs[0], ptrs[1], ptrs[2], lds[0], lds[1], lds[2], nw, M, N, K,
-                                            _stream())
+        rc = _lib.load().fresco_linear_rows_dt(x2.data_ptr(), x_ld, x_rows.data_ptr(), wp[0], wp[1], wp[2], bp[0], bp[1],
+                                               bp[2], ptrs[0], ptrs[1], ptrs[2], lds[0], lds[1], lds[2], nw, M, N, K,
+                                               _MFMA_DTYPES[dt], _stream())
     else:
-        rc = _lib.load().fresco_linear(x2.data_ptr(), x_ld, wp[0], wp[1], wp[2], bp[0], bp[1], bp[2], ptrs[0], ptrs[1],
-                                       ptrs[2], lds[0], lds[1], lds[2], nw, M, N, K, _stream())
+        rc = _lib.load().fresco_linear_dt(x2.data_ptr(), x_ld, wp[0], wp[1], wp[2], bp[0], bp[1], bp[2], ptrs[0], ptrs[1],
+                                          ptrs[2], lds[0], lds[1], lds[2], nw, M, N, K, _MFMA_DTYPES[dt], _stream())
     _lib.check(rc, "fresco_linear(M=%d,N=%d,K=%d,nw=%d)" % (M, N, K, nw))
     return outs
 
@@ -216,13 +225,14 @@ def attention(q, k, v, heads, scale, *, kv_rows=None, n_groups=None, M=None, gro
               diag_bias=0.0, workspace=None):
     """softmax(scale * q k^T + diag_bias*I) v with grouped keys (fresco_attn_fwd).
 
-    q: (B, Lq, C) fp16.  k, v: (..., C) fp16 whose leading dims flatten to rows.
+    q: (B, Lq, C) fp16.  k, v: (..., C) fp16 whose leading dims flatten to rows.  Or all three bf16 (bf16 MFMA kernels:
+    fp32 scores and softmax, the scale applied in fp32, bf16 output).
     Default grouping: one key group per batch element (plain attention): k, v are (B, Lk, C).
     """
     _need_gpu(q, k, v, kv_rows)
-    if q.dtype != torch.float16 or k.dtype != torch.float16 or v.dtype != torch.float16:
-        raise TypeError("fresco_amd.attention: fp16 tensors required (got %s/%s/%s); the SD-1.5 FRESCO "
-                        "pipeline runs its UNet in fp16" % (q.dtype, k.dtype, v.dtype))
+    if q.dtype not in _MFMA_DTYPES or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError("fresco_amd.attention: q, k, v must all be fp16 or all bf16 (got %s/%s/%s)"
+                        % (q.dtype, k.dtype, v.dtype))
     B, Lq, C = q.shape
     D = C // heads
     if D * heads != C:
@@ -259,9 +269,9 @@ def attention(q, k, v, heads, scale, *, kv_rows=None, n_groups=None, M=None, gro
     ws_bytes = lib.fresco_attn_workspace_bytes(n_groups, heads, M, D)
     ws = (workspace or _default_ws).get(ws_bytes, q.device)
     out = torch.empty((B, Lq, C), dtype=q.dtype, device=q.device)
-    rc = lib.fresco_attn_fwd_ld(q.data_ptr(), k.data_ptr(), v.data_ptr(), _ptr(kv_rows), out.data_ptr(),
+    rc = lib.fresco_attn_fwd_dt(q.data_ptr(), k.data_ptr(), v.data_ptr(), _ptr(kv_rows), out.data_ptr(),
                                 ws.data_ptr(), ws.numel(), B, heads, Lq, D, n_groups, M, group_rows,
-                                float(scale), float(diag_bias), q_ld, kv_ld, _stream())
+                                float(scale), float(diag_bias), q_ld, kv_ld, _MFMA_DTYPES[q.dtype], _stream())
     _lib.check(rc, "fresco_attn_fwd(B=%d,H=%d,Lq=%d,D=%d,groups=%d,M=%d)" % (B, heads, Lq, D, n_groups, M))
     return out
 
@@ -645,11 +655,12 @@ def _prep_maps(fwd_map, mask, N, HW):
 
 
 def temporal_attention(q, k, v, fwd_map, mask, heads, scale, chunk):
-    """fresco_temporal_attn: q, k, v (chunk*N, HW, C) fp16; fwd_map (N,HW) int64 (a permutation per frame,
-    checked once per table); mask (HW,N,N) bool."""
+    """fresco_temporal_attn: q, k, v (chunk*N, HW, C) all fp16 or all bf16; fwd_map (N,HW) int64 (a permutation per
+    frame, checked once per table); mask (HW,N,N) bool."""
     _need_gpu(q, k, v, fwd_map, mask)
-    if q.dtype != torch.float16 or k.dtype != torch.float16 or v.dtype != torch.float16:
-        raise TypeError("fresco_amd.temporal_attention: fp16 tensors required")
+    if q.dtype not in _MFMA_DTYPES or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError("fresco_amd.temporal_attention: q, k, v must all be fp16 or all bf16 (got %s/%s/%s)"
+                        % (q.dtype, k.dtype, v.dtype))
     Bt, HW, C = q.shape
     N = Bt // chunk
     D = C // heads
@@ -660,9 +671,9 @@ def temporal_attention(q, k, v, fwd_map, mask, heads, scale, chunk):
     fwd_map, mask = _prep_maps(fwd_map, mask, N, HW)
     _check_permutations(owner, fwd_map, HW)
     out = torch.empty((Bt, HW, C), dtype=q.dtype, device=q.device)
-    rc = _lib.load().fresco_temporal_attn_ld(q.data_ptr(), k.data_ptr(), v.data_ptr(), fwd_map.data_ptr(),
+    rc = _lib.load().fresco_temporal_attn_dt(q.data_ptr(), k.data_ptr(), v.data_ptr(), fwd_map.data_ptr(),
                                              mask.data_ptr(), out.data_ptr(), chunk, N, HW, heads, D,
-                                             float(scale), q_ld, k_ld, v_ld, _stream())
+                                             float(scale), q_ld, k_ld, v_ld, _MFMA_DTYPES[q.dtype], _stream())
     _lib.check(rc, "fresco_temporal_attn(chunk=%d,N=%d,HW=%d,H=%d,D=%d)" % (chunk, N, HW, heads, D))
     return out
 
@@ -803,19 +814,23 @@ def warp_fuse_chain(lat, bwd_flow, fwd_flow, bwd_occ, fwd_occ, sal, warp_sal, wa
     return lat
 
 
+# storage types of the elementwise / reduction kernels that carry a dtype code (fp32 arithmetic inside, one rounding at the store)
+_ELEMWISE_DTYPES = {torch.float16: _lib.F16, torch.float32: _lib.F32, torch.bfloat16: _lib.BF16}
+
+
 def adain(content, style, eps_content=1e-5, eps_style=1.0):
     _need_gpu(content, style)
     if content.shape != style.shape:
         raise ValueError("AdaIN: content %s vs style %s" % (tuple(content.shape), tuple(style.shape)))
     dt = torch.result_type(content, style)
-    if dt not in (torch.float16, torch.float32):
+    if dt not in _ELEMWISE_DTYPES:
         dt = torch.float32
     c, s = content.to(dt).contiguous(), style.to(dt).contiguous()
     rows = c.shape[0] * c.shape[1]
     L = c.numel() // rows
     out = torch.empty_like(c)
     rc = _lib.load().fresco_adain(c.data_ptr(), s.data_ptr(), out.data_ptr(), rows, L, float(eps_content),
-                                  float(eps_style), _lib.F16 if dt == torch.float16 else _lib.F32, _stream())
+                                  float(eps_style), _ELEMWISE_DTYPES[dt], _stream())
     _lib.check(rc, "fresco_adain")
     return out
 
@@ -823,14 +838,14 @@ def adain(content, style, eps_content=1e-5, eps_style=1.0):
 def chan_mean_std(feat, eps=1e-5):
     """-> (mean, std) fp32 of shape (N*C,): per-plane mean and sqrt(unbiased variance + eps)  (src/utils.py:58-67)."""
     _need_gpu(feat)
-    dt = feat.dtype if feat.dtype in (torch.float16, torch.float32) else torch.float32
+    dt = feat.dtype if feat.dtype in _ELEMWISE_DTYPES else torch.float32
     x = feat.to(dt).contiguous()
     rows = x.shape[0] * x.shape[1]
     L = x.numel() // rows
     mean = torch.empty(rows, dtype=torch.float32, device=x.device)
     std = torch.empty(rows, dtype=torch.float32, device=x.device)
     rc = _lib.load().fresco_chan_mean_std(x.data_ptr(), mean.data_ptr(), std.data_ptr(), rows, L, float(eps),
-                                          _lib.F16 if dt == torch.float16 else _lib.F32, _stream())
+                                          _ELEMWISE_DTYPES[dt], _stream())
     _lib.check(rc, "fresco_chan_mean_std")
     return mean, std
 

@@ -45,15 +45,26 @@ class FRESCOAttnProcessor2_0:
         # and V only inside the pack
         self.fuse_kv_pack = True
 
+    # bf16 modules / activations run on the bf16 kernels (fresco_linear_dt, fresco_attn_fwd_dt, fresco_temporal_attn_dt): no
+    # cast, no warning, bf16 out.  False restores the rounding path (library GEMMs, q / k / v rounded to fp16 for the
+    # kernels, one RuntimeWarning) for A/B measurements.  The fused K | V projection-pack stays fp16-only: bf16
+    # cross-frame-only calls take the fresco_linear_rows + grouped-attention branch.
+    native_bf16 = True
+
+    def _kernel_dtype(self, dtype):
+        """activations of this dtype go through the fused projections and the attention kernels as they are"""
+        return dtype == torch.float16 or (dtype == torch.bfloat16 and self.native_bf16)
+
     # ---- fused projections ---------------------------------------------------------------------------
     def _project(self, attn, x, names, outs=None, x_rows=None):
         """[attn.<name>(x) for name in names] in ONE launch that reads x once (fresco_linear), when every module
-        is a plain bias-free fp16 nn.Linear of a supported width; otherwise the modules are called as the
+        is a plain bias-free fp16 (or bf16) nn.Linear of a supported width and of x's dtype; otherwise the modules are called as the
         reference calls them (wrapped / LoRA / quantised layers keep their own forward).  The kernel reads each
         module's weight where it lives: nothing is stacked or cached, in-place weight updates are always seen."""
         mods = [getattr(attn, n) for n in names]
-        if (self.fuse_projections and x.dtype == torch.float16 and x.is_cuda
-                and all(_plain_linear(m, False) for m in mods)
+        if (self.fuse_projections and self._kernel_dtype(x.dtype) and x.is_cuda
+                and all(_plain_linear(m, False) and m.weight.dtype == x.dtype for m in mods)
+                and (outs is None or all(o.dtype == x.dtype for o in outs))
                 and len({(m.in_features, m.out_features) for m in mods}) == 1
                 and all(m.weight.is_contiguous() and m.weight.data_ptr() % 16 == 0 for m in mods)):
             # (x_rows come from _sel_rows: positions of a mask's True entries, in range by construction)
@@ -71,7 +82,8 @@ class FRESCOAttnProcessor2_0:
         lin = attn.to_out[0]
         # (round 3 left the C = 640 case to the library GEMM; on repeated measurement the two tie within the box-to-box
         # spread -- 27-30 us here, 24-33 us hipBLASLt at (16384, 640, 640) -- so the hot path now has no library GEMM)
-        if (self.fuse_projections and hs.dtype == torch.float16 and hs.is_cuda and _plain_linear(lin, True)
+        if (self.fuse_projections and self._kernel_dtype(hs.dtype) and hs.is_cuda and _plain_linear(lin, True)
+                and lin.weight.dtype == hs.dtype and lin.bias.dtype == hs.dtype
                 and ops.linear_supported(lin.in_features, lin.out_features, hs.dtype)):
             return ops.linear(hs, [lin.weight.detach()], [lin.bias.detach()])[0]
         return lin(hs)
@@ -105,7 +117,8 @@ class FRESCOAttnProcessor2_0:
         return hit[1]
 
     def _warn_rounding(self, dtype):
-        """fp32 / bf16 pipelines: said once per processor (values beyond +-65504 would become inf in the fp16 kernels)"""
+        """fp32 pipelines (and bf16 ones with native_bf16 off or frame-sharded): said once per processor (values beyond
+        +-65504 would become inf in the fp16 kernels)"""
         if not getattr(self, "_warned_rounding", False):
             self._warned_rounding = True
             warnings.warn("fresco_amd: %s activations are rounded to fp16 for the attention kernels and the result is "
@@ -262,12 +275,14 @@ class FRESCOAttnProcessor2_0:
             key = attn.to_k(encoder_hidden_states)
             value = attn.to_v(encoder_hidden_states)
 
-        # the kernels compute in fp16 (the dtype the pipeline runs its UNet in); fp32 / bf16 activations are rounded
-        # to fp16 after the projections and the result is cast back: same HIP path, no eager branch
+        # the kernels compute in fp16 or bf16, whichever the pipeline runs its UNet in; fp32 activations (and bf16 ones
+        # with native_bf16 off) are rounded to fp16 after the projections and the result is cast back: same HIP path, no
+        # eager branch
         out_dtype = query.dtype
-        if out_dtype != torch.float16:
+        if not self._kernel_dtype(out_dtype):
             self._warn_rounding(out_dtype)
-            query, key, value = query.half(), key.half(), value.half()
+            query, value = query.half(), (None if value is None else value.half())
+            key = None if key is None else key.half()
 
         heads = attn.heads
         head_dim = query.shape[-1] // heads
@@ -282,8 +297,8 @@ class FRESCOAttnProcessor2_0:
             ref = ctrl(None)
             assert ref.shape == encoder_hidden_states.shape
             q_ref, k_ref = self._project(attn, ref, ("to_q", "to_k"))
-            if q_ref.dtype != torch.float16:
-                q_ref, k_ref = q_ref.half(), k_ref.half()
+            if q_ref.dtype != query.dtype:
+                q_ref, k_ref = q_ref.to(query.dtype), k_ref.to(query.dtype)
             q_att = ops.attention(q_ref, k_ref, query, heads, ctrl.intraattn_scale_factor * sm_scale,
                                   diag_bias=float(ctrl.intraattn_bias), workspace=self._ws)
 
@@ -350,7 +365,10 @@ class FRESCOAttnProcessor2_0:
 def _sharded_self_attention(self, attn, hidden_states, residual, input_ndim):
     """Frame-parallel form of the FRESCO self-attention branch (fresco_amd/dist.py): this rank holds
     `shard.n_loc` frames of both CFG halves.  Cross-frame keys: broadcast of frame 0 + all-gather of the
-    other frames' selected rows; temporal pass: all-to-all to trajectory shards and back; the rest is local."""
+    other frames' selected rows; temporal pass: all-to-all to trajectory shards and back; the rest is local.
+    This branch computes in fp16 whatever native_bf16 says (the packed temporal entry points and the exchange buffers are
+    fp16): bf16 activations are rounded to fp16 after the projections, with the RuntimeWarning, and the result is cast
+    back."""
     if input_ndim != 3:
         raise NotImplementedError("fresco_amd: frame-sharded attention expects (B, HW, C) hidden states")
     out_dtype = hidden_states.dtype
@@ -425,9 +443,10 @@ def apply_FRESCO_attn(pipe):
     The other attentions keep diffusers' stock AttnProcessor2_0.
 
     Narrower than the reference on purpose (there is no eager fallback behind the HIP kernels): the processor takes
-    CUDA hidden states and computes the attention in fp16 (the dtype run_fresco.py runs the UNet in, :63-80): fp32 /
-    bf16 activations are rounded to fp16 after the projections and the result is cast back (one RuntimeWarning per
-    processor; frame-sharded runs follow the same policy); an `attention_mask` (the pipeline never passes one to these layers)
+    CUDA hidden states and computes the attention in fp16 (the dtype run_fresco.py runs the UNet in, :63-80) or, for a
+    bf16 pipeline, in bf16 (FRESCOAttnProcessor2_0.native_bf16); fp32 activations are rounded to fp16 after the
+    projections and the result is cast back (one RuntimeWarning per processor), and so are bf16 ones in frame-sharded
+    runs; an `attention_mask` (the pipeline never passes one to these layers)
     is honoured on the plain / cross-attention path through a padded-head-dim side path, and rejected where the reference
     itself cannot use it (together with cross-frame attention) or where it depends on the query."""
     from diffusers.models.attention_processor import AttnProcessor2_0

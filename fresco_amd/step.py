@@ -11,7 +11,9 @@ def _dt(t):
         return _lib.F16
     if t.dtype == torch.float32:
         return _lib.F32
-    raise TypeError("fresco_amd.step: fp16 / fp32 latents only (got %s)" % t.dtype)
+    if t.dtype == torch.bfloat16:
+        return _lib.BF16
+    raise TypeError("fresco_amd.step: fp16 / bf16 / fp32 latents only (got %s)" % t.dtype)
 
 
 def predict_x0(sample, eps_uncond, eps_text=None, guidance_scale=1.0, alpha_prod_t=1.0):

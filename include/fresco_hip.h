@@ -41,6 +41,7 @@ extern "C" {
 /* dtype codes for entry points that accept more than one element type */
 #define FRESCO_F16 0
 #define FRESCO_F32 1
+#define FRESCO_BF16 2 /* bfloat16: the *_dt entry points below, fresco_adain, fresco_chan_mean_std, fresco_ddpm_* */
 
 /* library / build identification: "fresco_hip <version> gfx950" */
 const char* fresco_version(void);
@@ -124,6 +125,17 @@ int fresco_linear_rows(const void* x, int64_t x_ld, const int32_t* x_rows, const
                        const void* W2, const void* b0, const void* b1, const void* b2, void* out0, void* out1,
                        void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, void* stream);
 
+/* fresco_linear / fresco_linear_rows with an element type: dtype = FRESCO_F16 or FRESCO_BF16 for ALL operands (x, W_j,
+ * b_j, out_j; strides stay in elements of 2 bytes).  bf16 runs the same kernel on v_mfma_f32_32x32x16_bf16: fp32
+ * accumulation, one rounding to nearest even at the store.  Any other dtype code: FRESCO_EINVAL, before any HIP call. */
+int fresco_linear_dt(const void* x, int64_t x_ld, const void* W0, const void* W1, const void* W2, const void* b0,
+                     const void* b1, const void* b2, void* out0, void* out1, void* out2, int64_t ld0, int64_t ld1,
+                     int64_t ld2, int nw, int M, int N, int K, int dtype, void* stream);
+int fresco_linear_rows_dt(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1,
+                          const void* W2, const void* b0, const void* b1, const void* b2, void* out0, void* out1,
+                          void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, int dtype,
+                          void* stream);
+
 
 int fresco_attn_fwd(const void* q, const void* k, const void* v, const int32_t* kv_rows,
                     void* out, void* workspace, size_t workspace_bytes,
@@ -139,6 +151,17 @@ int fresco_attn_fwd_ld(const void* q, const void* k, const void* v, const int32_
                        int B, int H, int Lq, int D,
                        int n_groups, int M, int64_t group_rows,
                        float scale, float diag_bias, int64_t q_ld, int64_t kv_ld, void* stream);
+
+/* fresco_attn_fwd_ld with an element type: dtype = FRESCO_F16 or FRESCO_BF16 for q, k, v and out (any other code:
+ * FRESCO_EINVAL before any HIP call).  Elements are 2 bytes either way: same workspace (fresco_attn_workspace_bytes),
+ * same packed key image geometry.  bf16: scores and softmax in fp32, P and O^T products on the bf16 MFMA; the softmax
+ * scale is never folded into the bf16 Q (one bf16 rounding of scale*q costs more than P's own rounding) but applied to
+ * the fp32 scores; the running max is kept on the bf16 grid.  All eight head dims. */
+int fresco_attn_fwd_dt(const void* q, const void* k, const void* v, const int32_t* kv_rows,
+                       void* out, void* workspace, size_t workspace_bytes,
+                       int B, int H, int Lq, int D,
+                       int n_groups, int M, int64_t group_rows,
+                       float scale, float diag_bias, int64_t q_ld, int64_t kv_ld, int dtype, void* stream);
 
 /* Cross-frame pass with the K | V projection of the selected rows FUSED into the key pack (round 6) -- for layer calls
  * whose only reader of K and V is the cross-frame pass (DH:201-247 on the cross-frame-only steps): replaces
@@ -183,6 +206,14 @@ int fresco_temporal_attn_ld(const void* q, const void* k, const void* v, const i
                             const uint8_t* mask, void* out,
                             int chunk, int N, int HW, int H, int D, float scale,
                             int64_t q_ld, int64_t k_ld, int64_t v_ld, void* stream);
+
+/* The row-strided form with an element type: dtype = FRESCO_F16 or FRESCO_BF16 for q, k, v and out (any other code:
+ * FRESCO_EINVAL before any HIP call).  The scale (the reference's 0.2 key factor included) stays an fp32 factor of the
+ * scores.  The packed / sharded entry points below are fp16 only. */
+int fresco_temporal_attn_dt(const void* q, const void* k, const void* v, const int64_t* fwd_map,
+                            const uint8_t* mask, void* out,
+                            int chunk, int N, int HW, int H, int D, float scale,
+                            int64_t q_ld, int64_t k_ld, int64_t v_ld, int dtype, void* stream);
 
 /* Multi-GPU: frames are sharded over ranks, the temporal pass is sharded by TRAJECTORY, so that
  * every byte crosses the fabric once and the kernel's HBM traffic shrinks with the world size.  Rank r owns the
@@ -355,12 +386,13 @@ int fresco_warp_fuse_chain(float* lat, const float* bwd_flow, const float* fwd_f
  * (a9)  adaptive_instance_normalization (UT:58-78) over rows of L = h*w elements:
  *   out = (content - mean_c) / sqrt(var_c + eps_content) * sqrt(var_s + eps_style) + mean_s,
  *   unbiased variance.  The reference's style eps is 1.0 (UT:73 passes chunk into eps).
- *   content, style, out : (rows, L), dtype FRESCO_F16 or FRESCO_F32 (all three the same).
+ *   content, style, out : (rows, L), dtype FRESCO_F16, FRESCO_BF16 or FRESCO_F32 (all three the same; fp32 arithmetic,
+ *   one rounding to nearest even at the store).
  * ------------------------------------------------------------------------------------------ */
 int fresco_adain(const void* content, const void* style, void* out, int rows, int L,
                  float eps_content, float eps_style, int dtype, void* stream);
 
-/* calc_mean_std (src/utils.py:58-67): per row (= one (sample, channel) plane of L values, dtype F16 / F32):
+/* calc_mean_std (src/utils.py:58-67): per row (= one (sample, channel) plane of L values, dtype F16 / BF16 / F32):
  *   mean[row] = mean(x), stdv[row] = sqrt(unbiased variance + eps), both fp32.  L > 1. */
 int fresco_chan_mean_std(const void* x, float* mean, float* stdv, int rows, int L, float eps, int dtype,
                          void* stream);
@@ -470,7 +502,7 @@ int fresco_mapping_ind(const float* flow, const float* occ, const float* frames,
 
 /* ------------------------------------------------------------------------------------------
  * (f2)  DDPM step of src/pipe_FRESCO.py:14-77 (+ classifier-free guidance, 212-214), elementwise over n
- * values, dtype FRESCO_F16 / FRESCO_F32 (fp32 arithmetic inside):
+ * values, dtype FRESCO_F16 / FRESCO_BF16 / FRESCO_F32 (fp32 arithmetic inside, one rounding at the store):
  *   fresco_ddpm_x0  : eps = eps_text ? eps_uncond + guidance*(eps_text - eps_uncond) : eps_uncond
  *                     (written to eps_out if non-NULL);  x0 = (xt - sqrt_beta_prod*eps) / sqrt_alpha_prod
  *   fresco_ddpm_prev: out = c_x0*x0 + c_xt*xt + sigma*noise[i % noise_period]
