@@ -205,17 +205,13 @@ struct KvProjCfg {
     static_assert(KIN % WK == 0 && 64 % XR == 0 && XR % 32 == 0 && 160 % D == 0 && D % 8 == 0 && TILES >= 1, "shapes");
 };
 
-// __launch_bounds__' second argument is used as a REGISTER CAP here, not as an occupancy: by its LDS one workgroup fits a CU at
-// either width (5 waves on 4 SIMDs: at most 2 per SIMD).  "3" at K_in = 320 means <= 168 registers, the budget
-// tests/test_kernel_resources.py pins for this instantiation, and the build sits exactly on it (80 weight + 32 accumulator
-// + 32 hidden-row fragment registers + addresses; the lane coordinates of the epilogue are laundered to keep its addresses
-// out of the loop-invariant set): an edit that adds live registers will spill -- that test says so.  "2" at 640: <= 256 (228).
-template <int KIN, int D>
-__global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(const half_t* __restrict__ x, int64_t x_ld,
-                                                             const int32_t* __restrict__ x_rows,
-                                                             const half_t* __restrict__ Wk,
-                                                             const half_t* __restrict__ Wv, char* __restrict__ img,
-                                                             float* __restrict__ ktmax, int H, int M, int nT) {
+// (one body for both element types, Elem<T> of common.h: fragment types, the MFMA, the conversions and the bit pattern of 1.0
+// are all that differs; grid, LDS plan, DMA ring and the counted waits are common)
+template <typename T, int KIN, int D>
+__device__ __forceinline__ void kvproj_pack_body(const T* x, int64_t x_ld, const int32_t* x_rows, const T* Wk, const T* Wv,
+                                                 char* img, float* ktmax, int H, int M, int nT) {
+    typedef typename Elem<T>::x4 X4;
+    typedef typename Elem<T>::x8 X8;
     using Cfg = AttnCfg<D>;
     using PC = KvProjCfg<KIN, D>;
     constexpr int ROWB = PC::ROWB, HPW = PC::HPW, NPART = PC::NPART, CPR = PC::CPR, XR = PC::XR, NB = PC::NB, BPT = PC::BPT;
@@ -234,7 +230,7 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
     const int nblk = nt * BPT;
     const uint32_t lds0 = lds_addr(smem);
     const int ft = fg * 5 + wave;  // this wave's 32-feature tile
-    const half_t* wsrc = (kv ? Wv : Wk) + (int64_t)ft * 32 * KIN;
+    const T* wsrc = (kv ? Wv : Wk) + (int64_t)ft * 32 * KIN;
 
     // one round of this wave's weight rows -> its staging slot, consecutive lanes on consecutive chunks of a row
     auto weight_dma = [&](int round) __attribute__((always_inline)) {
@@ -245,14 +241,14 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
             lds_dma16(wsrc + (int64_t)row * KIN + round * PC::WK + dc * 8, lds0 + PC::XBUF + wave * PC::WSLOT + j * 1024);
         }
     };
-    half8_t fw[NKS];
+    X8 fw[NKS];
     auto weight_frags = [&](int round) __attribute__((always_inline)) {
         const char* slot = stage + wave * PC::WSLOT + l31 * PC::WROWB + hi * 64;
 #pragma unroll
         for (int s = 0; s < WST; ++s)
 #pragma unroll
             for (int i = 0; i < SK; ++i)
-                fw[(round * WST + s) * SK + i] = *reinterpret_cast<const half8_t*>(slot + s * 128 + i * 16);
+                fw[(round * WST + s) * SK + i] = *reinterpret_cast<const X8*>(slot + s * 128 + i * 16);
     };
     // the gathered hidden rows of block u -> buffer u & 1 (buffer 1 is the head of the staging area)
     auto gather_dma = [&](int u) __attribute__((always_inline)) {
@@ -302,8 +298,8 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
             // block u's rows have landed (every wave waited for its own pieces); everyone is done with the other buffer -- and,
             // at u = 0, with the staging slots under it.  The wait is counted: the NST image stores of block u - 1 are this
             // wave's only vector-memory operations younger than its pieces of block u, and stay in flight
-            // NST MUST equal the number of global store instructions the epilogue below issues per block (K: NB x 4 half4
-            // stores, V: NB x 2 half8 stores) and nothing else may touch vector memory after gather_dma: with fewer stores
+            // NST MUST equal the number of global store instructions the epilogue below issues per block (K: NB x 4 x4
+            // stores, V: NB x 2 x8 stores) and nothing else may touch vector memory after gather_dma: with fewer stores
             // than NST the wait returns before the rows have landed.  Check the listing's vmcnt against its stores after any
             // edit of the epilogue.
             constexpr int K_STORES = NB * 4, V_STORES = NB * 2;
@@ -322,14 +318,14 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
             // the products, hidden-row fragments one group of four ahead of their MFMAs (left alone, hipcc issues
             // read -> wait -> MFMA: an LDS round trip per step)
             constexpr int GS = 4 / NB, NG = NKS / GS;  // k-steps per group, groups
-            half8_t xq[2][4];
+            X8 xq[2][4];
             auto xfetch = [&](int q) __attribute__((always_inline)) {
 #pragma unroll
                 for (int i = 0; i < GS; ++i)
 #pragma unroll
                     for (int b = 0; b < NB; ++b) {
                         const int s = q * GS + i;
-                        xq[q & 1][i * NB + b] = *reinterpret_cast<const half8_t*>(xs + b * 32 * ROWB + (s / SK) * 128 + (s % SK) * 16);
+                        xq[q & 1][i * NB + b] = *reinterpret_cast<const X8*>(xs + b * 32 * ROWB + (s / SK) * 128 + (s % SK) * 16);
                     }
             };
             xfetch(0);
@@ -341,9 +337,8 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
                 for (int i = 0; i < GS; ++i)
 #pragma unroll
                     for (int b = 0; b < NB; ++b) {
-                        const half8_t xb = xq[q & 1][i * NB + b], wf = fw[q * GS + i];
-                        acc[b] = KV ? __builtin_amdgcn_mfma_f32_32x32x16_f16(xb, wf, acc[b], 0, 0, 0)
-                                    : __builtin_amdgcn_mfma_f32_32x32x16_f16(wf, xb, acc[b], 0, 0, 0);
+                        const X8 xb = xq[q & 1][i * NB + b], wf = fw[q * GS + i];
+                        acc[b] = KV ? Elem<T>::mfma32x32x16(xb, wf, acc[b]) : Elem<T>::mfma32x32x16(wf, xb, acc[b]);
                     }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -361,15 +356,15 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
                     for (int j = 0; j < K_STORES / NB; ++j) {  // one store each: K_STORES per block
                         const int f0 = ft * 32 + 8 * j + 4 * hie;
                         const int head = f0 / D, dd = f0 - head * D;
-                        half4_t w;
+                        X4 w;
                         float n2 = 0.f;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            w[e] = real ? (half_t)acc[b][4 * j + e] : (half_t)0;
+                            w[e] = real ? (T)acc[b][4 * j + e] : (T)0;
                             n2 = fmaf((float)w[e], (float)w[e], n2);
                         }
                         char* dst = img + ((int64_t)(g * H + head) * (nT + 1) + tile0 + tl) * Cfg::TILE;
-                        *reinterpret_cast<half4_t*>(dst + ((dd >> 3) * 64 + key) * 16 + (dd & 7) * 2) = w;
+                        *reinterpret_cast<X4*>(dst + ((dd >> 3) * 64 + key) * 16 + (dd & 7) * 2) = w;
                         n2p[(tl & 1) * PC::N2P + ((head - fg * HPW) * NPART + (dd >> 2)) * 64 + key] = n2;
                     }
                 }
@@ -383,13 +378,13 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
 #pragma unroll
                     for (int kq = 0; kq < V_STORES / NB; ++kq) {  // one store each: V_STORES per block
                         const int kc = kbase / 16 + 2 * b + kq;
-                        half8_t w;
+                        X8 w;
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             const int key = kc * 16 + (e & 3) + 8 * (e >> 2) + 4 * hie;
-                            w[e] = trow[key] >= 0 ? (half_t)acc[b][8 * kq + e] : (half_t)0;
+                            w[e] = trow[key] >= 0 ? (T)acc[b][8 * kq + e] : (T)0;
                         }
-                        *reinterpret_cast<half8_t*>(dst + ((kc * 2 + hie) * Cfg::DPV + d) * 16) = w;
+                        *reinterpret_cast<X8*>(dst + ((kc * 2 + hie) * Cfg::DPV + d) * 16) = w;
                     }
             }
         }
@@ -408,23 +403,53 @@ __global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(co
             if (!kv) {
                 const int pc = c / 64, key = c % 64;
                 uint4 val = make_uint4(0, 0, 0, 0);
-                if (Cfg::MCOL && pc == 0 && trow[key] >= 0) val.x = 0x3C00u;  // K[key][D] = 1.0 (running max rides in the QK MFMA)
+                if (Cfg::MCOL && pc == 0 && trow[key] >= 0) val.x = Elem<T>::ONE_BITS;  // K[key][D] = 1.0 (running max rides in the QK MFMA)
                 *reinterpret_cast<uint4*>(base + ((D / 8 + pc) * 64 + key) * 16) = val;
             } else {
                 const int pr = c / 8, kcc = c % 8;       // pad row, (kc, cc) chunk
                 const int kc = kcc >> 1, cc = kcc & 1;
-                half8_t o;
+                X8 o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int key = kc * 16 + (e & 3) + 8 * (e >> 2) + 4 * cc;
-                    o[e] = (Cfg::ONES && pr == 0 && trow[key] >= 0) ? (half_t)1 : (half_t)0;
+                    o[e] = (Cfg::ONES && pr == 0 && trow[key] >= 0) ? (T)1 : (T)0;
                 }
-                *reinterpret_cast<half8_t*>(base + Cfg::TILE + Cfg::KTILE + (kcc * Cfg::DPV + D + pr) * 16) = o;
+                *reinterpret_cast<X8*>(base + Cfg::TILE + Cfg::KTILE + (kcc * Cfg::DPV + D + pr) * 16) = o;
             }
         }
     }
     __syncthreads();
     reduce_ktmax(nt - 1);
+}
+
+// __launch_bounds__' second argument is used as a REGISTER CAP here, not as an occupancy: by its LDS one workgroup fits a CU at
+// either width (5 waves on 4 SIMDs: at most 2 per SIMD).  "3" at K_in = 320 means <= 168 registers, the budget
+// tests/test_kernel_resources.py pins for this instantiation, and the build sits exactly on it (80 weight + 32 accumulator
+// + 32 hidden-row fragment registers + addresses; the lane coordinates of the epilogue are laundered to keep its addresses
+// out of the loop-invariant set): an edit that adds live registers will spill -- that test says so.  "2" at 640: <= 256 (228).
+// The bf16 instantiations take the same caps (tests/test_kernel_resources_kvproj_bf16.py; counts in EXPERIMENTS.md section 8).
+template <int KIN, int D>
+__global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_kernel(const half_t* __restrict__ x, int64_t x_ld,
+                                                             const int32_t* __restrict__ x_rows,
+                                                             const half_t* __restrict__ Wk,
+                                                             const half_t* __restrict__ Wv, char* __restrict__ img,
+                                                             float* __restrict__ ktmax, int H, int M, int nT) {
+    kvproj_pack_body<half_t, KIN, D>(x, x_ld, x_rows, Wk, Wv, img, ktmax, H, M, nT);
+}
+template <int KIN, int D>
+__global__ __launch_bounds__(320, KIN == 320 ? 3 : 2) void kvproj_pack_bf16_kernel(const bf16_t* __restrict__ x, int64_t x_ld,
+                                                                  const int32_t* __restrict__ x_rows,
+                                                                  const bf16_t* __restrict__ Wk,
+                                                                  const bf16_t* __restrict__ Wv, char* __restrict__ img,
+                                                                  float* __restrict__ ktmax, int H, int M, int nT) {
+    kvproj_pack_body<bf16_t, KIN, D>(x, x_ld, x_rows, Wk, Wv, img, ktmax, H, M, nT);
+}
+template <typename T, int KIN, int D>
+static auto kvproj_pack_kernel_of() {
+    if constexpr (std::is_same<T, bf16_t>::value)
+        return &kvproj_pack_bf16_kernel<KIN, D>;
+    else
+        return &kvproj_pack_kernel<KIN, D>;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1409,10 +1434,10 @@ extern "C" int fresco_attn_fwd_ld(const void* q, const void* k, const void* v, c
 }
 
 namespace fresco {
-template <int KIN, int D>
-static int launch_kvproj_attn(const half_t* q, const half_t* x, int64_t x_ld, const int32_t* x_rows, const half_t* Wk,
-                              const half_t* Wv, half_t* out, char* ws, int B, int H, int Lq, int n_groups, int M,
-                              float scale, int64_t q_ld, hipStream_t st) {
+template <typename T, int KIN, int D>
+static int launch_kvproj_attn(const T* q, const T* x, int64_t x_ld, const int32_t* x_rows, const T* Wk, const T* Wv, T* out,
+                              char* ws, int B, int H, int Lq, int n_groups, int M, float scale, int64_t q_ld,
+                              hipStream_t st) {
     using Cfg = AttnCfg<D>;
     const int nT = ntiles_of(M);
     char* img = ws;
@@ -1420,12 +1445,28 @@ static int launch_kvproj_attn(const half_t* q, const half_t* x, int64_t x_ld, co
     {
         ProfScope ps(FRESCO_PROF_KV_PACK, n_groups, H, M, -D, st);  // (d < 0: the fused projection + pack launch)
         constexpr int lds = KvProjCfg<KIN, D>::LDS_BYTES;
-        if (int rc = allow_dyn_lds(&kvproj_pack_kernel<KIN, D>, lds)) return rc;
-        constexpr int T = KvProjCfg<KIN, D>::TILES;
-        hipLaunchKernelGGL((kvproj_pack_kernel<KIN, D>), dim3((nT + T - 1) / T, 2 * (H * D / 160), n_groups), dim3(320), lds,
-                           st, x, x_ld, x_rows, Wk, Wv, img, ktmax, H, M, nT);
+        const auto kern = kvproj_pack_kernel_of<T, KIN, D>();
+        if (int rc = allow_dyn_lds(kern, lds)) return rc;  // (every launch: the attribute is per device)
+        constexpr int TL = KvProjCfg<KIN, D>::TILES;
+        hipLaunchKernelGGL(kern, dim3((nT + TL - 1) / TL, 2 * (H * D / 160), n_groups), dim3(320), lds, st, x, x_ld, x_rows,
+                           Wk, Wv, img, ktmax, H, M, nT);
     }
-    return launch_flash_auto<half_t, D>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
+    return launch_flash_auto<T, D>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
+}
+
+template <typename T>
+static int kvproj_launch_t(const void* q, const void* x, int64_t x_ld, const int32_t* x_rows, const void* Wk,
+                           const void* Wv, void* out, void* workspace, int B, int H, int Lq, int D, int n_groups, int M,
+                           float scale, int64_t q_ld, hipStream_t st) {
+    const T* qh = static_cast<const T*>(q);
+    const T* xh = static_cast<const T*>(x);
+    const T* wk = static_cast<const T*>(Wk);
+    const T* wv = static_cast<const T*>(Wv);
+    T* oh = static_cast<T*>(out);
+    char* ws = static_cast<char*>(workspace);
+    if (D == 40)
+        return launch_kvproj_attn<T, 320, 40>(qh, xh, x_ld, x_rows, wk, wv, oh, ws, B, H, Lq, n_groups, M, scale, q_ld, st);
+    return launch_kvproj_attn<T, 640, 80>(qh, xh, x_ld, x_rows, wk, wv, oh, ws, B, H, Lq, n_groups, M, scale, q_ld, st);
 }
 }  // namespace fresco
 
@@ -1433,10 +1474,11 @@ extern "C" int fresco_attn_kvproj_supported(int H, int D, int K_in) {
     return (H > 0 && (int64_t)H * D == K_in && ((D == 40 && K_in == 320) || (D == 80 && K_in == 640))) ? 1 : 0;
 }
 
-extern "C" int fresco_attn_fwd_kvproj(const void* q, const void* x, int64_t x_ld, const int32_t* x_rows, const void* Wk,
-                                      const void* Wv, void* out, void* workspace, size_t workspace_bytes, int B, int H,
-                                      int Lq, int D, int n_groups, int M, int K_in, float scale, int64_t q_ld,
-                                      void* stream) {
+extern "C" int fresco_attn_fwd_kvproj_dt(const void* q, const void* x, int64_t x_ld, const int32_t* x_rows, const void* Wk,
+                                         const void* Wv, void* out, void* workspace, size_t workspace_bytes, int B, int H,
+                                         int Lq, int D, int n_groups, int M, int K_in, float scale, int64_t q_ld, int dtype,
+                                         void* stream) {
+    if (dtype != FRESCO_F16 && dtype != FRESCO_BF16) return FRESCO_EINVAL;
     if (!q || !x || !x_rows || !Wk || !Wv || !out || !workspace) return FRESCO_EINVAL;
     if (B <= 0 || H <= 0 || Lq <= 0 || D <= 0 || n_groups <= 0 || M <= 0 || K_in <= 0) return FRESCO_EINVAL;
     if (B % n_groups != 0 || !(scale > 0.f)) return FRESCO_EINVAL;
@@ -1444,15 +1486,17 @@ extern "C" int fresco_attn_fwd_kvproj(const void* q, const void* x, int64_t x_ld
     if (!fresco_attn_kvproj_supported(H, D, K_in)) return FRESCO_EUNSUPPORTED;
     if (workspace_bytes < attn_ws_bytes(n_groups, H, M, D)) return FRESCO_EWORKSPACE;
     hipStream_t st = as_stream(stream);
-    const half_t* qh = static_cast<const half_t*>(q);
-    const half_t* xh = static_cast<const half_t*>(x);
-    const half_t* wk = static_cast<const half_t*>(Wk);
-    const half_t* wv = static_cast<const half_t*>(Wv);
-    half_t* oh = static_cast<half_t*>(out);
-    char* ws = static_cast<char*>(workspace);
-    if (D == 40)
-        return launch_kvproj_attn<320, 40>(qh, xh, x_ld, x_rows, wk, wv, oh, ws, B, H, Lq, n_groups, M, scale, q_ld, st);
-    return launch_kvproj_attn<640, 80>(qh, xh, x_ld, x_rows, wk, wv, oh, ws, B, H, Lq, n_groups, M, scale, q_ld, st);
+    if (dtype == FRESCO_BF16)
+        return kvproj_launch_t<bf16_t>(q, x, x_ld, x_rows, Wk, Wv, out, workspace, B, H, Lq, D, n_groups, M, scale, q_ld, st);
+    return kvproj_launch_t<half_t>(q, x, x_ld, x_rows, Wk, Wv, out, workspace, B, H, Lq, D, n_groups, M, scale, q_ld, st);
+}
+
+extern "C" int fresco_attn_fwd_kvproj(const void* q, const void* x, int64_t x_ld, const int32_t* x_rows, const void* Wk,
+                                      const void* Wv, void* out, void* workspace, size_t workspace_bytes, int B, int H,
+                                      int Lq, int D, int n_groups, int M, int K_in, float scale, int64_t q_ld,
+                                      void* stream) {
+    return fresco_attn_fwd_kvproj_dt(q, x, x_ld, x_rows, Wk, Wv, out, workspace, workspace_bytes, B, H, Lq, D, n_groups, M,
+                                     K_in, scale, q_ld, FRESCO_F16, stream);
 }
 
 extern "C" int fresco_attn_fwd(const void* q, const void* k, const void* v, const int32_t* kv_rows,

@@ -575,13 +575,18 @@ extern "C" int fresco_temporal_attn_dt(const void* q, const void* k, const void*
                              dtype);
 }
 
-extern "C" int fresco_temporal_attn_packed(const void* qkv, const uint8_t* mask, void* out, int chunk, int N, int P,
-                                           int H, int D, float scale, void* stream) {
+extern "C" int fresco_temporal_attn_packed_dt(const void* qkv, const uint8_t* mask, void* out, int chunk, int N, int P,
+                                              int H, int D, float scale, int dtype, void* stream) {
     if (!qkv) return FRESCO_EINVAL;
     const int64_t Cw = (int64_t)H * D;
-    const half_t* b = static_cast<const half_t*>(qkv);
+    const half_t* b = static_cast<const half_t*>(qkv);  // (2-byte elements either way: the offsets are the same)
     return temporal_dispatch(b, b + Cw, b + 2 * Cw, nullptr, mask, out, chunk, N, P, H, D, scale, 3 * Cw, 3 * Cw,
-                             3 * Cw, true, stream);
+                             3 * Cw, true, stream, dtype);
+}
+
+extern "C" int fresco_temporal_attn_packed(const void* qkv, const uint8_t* mask, void* out, int chunk, int N, int P,
+                                           int H, int D, float scale, void* stream) {
+    return fresco_temporal_attn_packed_dt(qkv, mask, out, chunk, N, P, H, D, scale, FRESCO_F16, stream);
 }
 
 static int pack_dispatch(bool unpack, const void* q, const void* k, const void* v, const int64_t* fwd_map, void* buf,

@@ -302,7 +302,8 @@ class FrameShard:
         return 1 + (1 if plan["Rmax"] > 0 else 0)
 
     def temporal(self, q, k, v, fwd_map, mask, heads, scale):
-        """trajectory-sharded temporal-guided pass: q, k, v local (chunk*n_loc, HW, C); returns the local rows"""
+        """trajectory-sharded temporal-guided pass: q, k, v local (chunk*n_loc, HW, C), all fp16 or all bf16 (pack, both
+        all-to-alls, the packed kernel and unpack run in that dtype); returns the local rows"""
         from . import ops
         Bl, HW, C = q.shape
         if HW % self.world != 0:

@@ -285,10 +285,13 @@ def attention_kvproj(q, hidden, x_rows, w_k, w_v, heads, scale, n_groups, M, wor
 
     q (B, Lq, C) fp16; hidden (..., K_in) fp16 whose leading dims flatten to rows; x_rows int32 (n_groups * M): key m of
     group g = row x_rows[g * M + m] of `hidden` (in range: the caller's table, checked once where it is built);
-    w_k, w_v (C, K_in) fp16 contiguous -- the live weights of bias-free nn.Linear modules.  Returns (B, Lq, C)."""
+    w_k, w_v (C, K_in) fp16 contiguous -- the live weights of bias-free nn.Linear modules.  Or all four bf16 (bf16 MFMA,
+    K and V rounded to bf16 once, the bf16 flash kernels); a mix raises.  Returns (B, Lq, C) of q's dtype."""
     _need_gpu(q, hidden, x_rows, w_k, w_v)
-    if any(t.dtype != torch.float16 for t in (q, hidden, w_k, w_v)) or x_rows.dtype != torch.int32:
-        raise TypeError("fresco_amd.attention_kvproj: fp16 tensors and an int32 row table required")
+    dt = q.dtype
+    if dt not in _MFMA_DTYPES or any(t.dtype != dt for t in (hidden, w_k, w_v)) or x_rows.dtype != torch.int32:
+        raise TypeError("fresco_amd.attention_kvproj: q, hidden, w_k, w_v all fp16 or all bf16 and an int32 row table "
+                        "required (got %s/%s/%s/%s, %s)" % (q.dtype, hidden.dtype, w_k.dtype, w_v.dtype, x_rows.dtype))
     B, Lq, C = q.shape
     D = C // heads
     K_in = hidden.shape[-1]
@@ -302,9 +305,9 @@ def attention_kvproj(q, hidden, x_rows, w_k, w_v, heads, scale, n_groups, M, wor
     ws_bytes = lib.fresco_attn_workspace_bytes(n_groups, heads, M, D)
     ws = (workspace or _default_ws).get(ws_bytes, q.device)
     out = torch.empty((B, Lq, C), dtype=q.dtype, device=q.device)
-    rc = lib.fresco_attn_fwd_kvproj(q.data_ptr(), hidden.data_ptr(), x_ld, x_rows.data_ptr(), w_k.data_ptr(), w_v.data_ptr(),
-                                    out.data_ptr(), ws.data_ptr(), ws.numel(), B, heads, Lq, D, n_groups, M, K_in,
-                                    float(scale), q_ld, _stream())
+    rc = lib.fresco_attn_fwd_kvproj_dt(q.data_ptr(), hidden.data_ptr(), x_ld, x_rows.data_ptr(), w_k.data_ptr(),
+                                       w_v.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, heads, Lq, D, n_groups,
+                                       M, K_in, float(scale), q_ld, _MFMA_DTYPES[dt], _stream())
     _lib.check(rc, "fresco_attn_fwd_kvproj(B=%d,H=%d,Lq=%d,D=%d,groups=%d,M=%d,K=%d)" % (B, heads, Lq, D, n_groups, M, K_in))
     return out
 
@@ -680,13 +683,17 @@ def temporal_attention(q, k, v, fwd_map, mask, heads, scale, chunk):
 
 def temporal_pack(q, k, v, fwd_map, chunk, n_loc, f0, world):
     """Multi-GPU, way out (fresco_temporal_pack): this rank's frames [f0, f0+n_loc) of q, k, v (chunk*n_loc, HW, C)
-    gathered along the trajectories into per-destination ranges: returns (world, n_loc, chunk, HW/world, 3C)."""
+    gathered along the trajectories into per-destination ranges: returns (world, n_loc, chunk, HW/world, 3C).  q, k, v
+    all fp16 or all bf16 (the kernel copies 16-byte pieces: no arithmetic); the buffer is of their dtype."""
     _need_gpu(q, k, v, fwd_map)
+    if q.dtype not in _MFMA_DTYPES or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError("fresco_amd.temporal_pack: q, k, v must all be fp16 or all bf16 (got %s/%s/%s)"
+                        % (q.dtype, k.dtype, v.dtype))
     Bl, HW, C = q.shape
     q, q_ld, _ = _rows(q)
     k, k_ld, _ = _rows(k)
     v, v_ld, _ = _rows(v)
-    buf = torch.empty((world, n_loc, chunk, HW // world, 3 * C), dtype=torch.float16, device=q.device)
+    buf = torch.empty((world, n_loc, chunk, HW // world, 3 * C), dtype=q.dtype, device=q.device)
     rc = _lib.load().fresco_temporal_pack(q.data_ptr(), k.data_ptr(), v.data_ptr(), fwd_map.data_ptr(), buf.data_ptr(),
                                           chunk, n_loc, f0, HW, C, world, q_ld, k_ld, v_ld, _stream())
     _lib.check(rc, "fresco_temporal_pack(chunk=%d,n_loc=%d,HW=%d,C=%d,world=%d)" % (chunk, n_loc, HW, C, world))
@@ -694,31 +701,33 @@ def temporal_pack(q, k, v, fwd_map, chunk, n_loc, f0, world):
 
 
 def temporal_attention_packed(qkv, mask, heads, scale, chunk):
-    """fresco_temporal_attn_packed: qkv (N, chunk, P, 3C) fp16 = q | k | v rows already in trajectory order for a
-    range of P trajectories, mask (P, N, N) for that range -> (N, chunk, P, C)."""
+    """fresco_temporal_attn_packed_dt: qkv (N, chunk, P, 3C) fp16 or bf16 = q | k | v rows already in trajectory order
+    for a range of P trajectories, mask (P, N, N) for that range -> (N, chunk, P, C) of qkv's dtype."""
     _need_gpu(qkv, mask)
     N, ch, P, C3 = qkv.shape
     C = C3 // 3
     D = C // heads
-    if ch != chunk or qkv.dtype != torch.float16 or not qkv.is_contiguous():
-        raise ValueError("temporal_attention_packed: contiguous fp16 (N, chunk, P, 3C) expected")
+    if ch != chunk or qkv.dtype not in _MFMA_DTYPES or not qkv.is_contiguous():
+        raise ValueError("temporal_attention_packed: contiguous fp16 or bf16 (N, chunk, P, 3C) expected")
     _, mask = _prep_maps(None, mask, N, 1)
     if mask.shape[0] != P:
         raise ValueError("temporal_attention_packed: mask must cover the %d trajectories of the range" % P)
-    out = torch.empty((N, chunk, P, C), dtype=torch.float16, device=qkv.device)
-    rc = _lib.load().fresco_temporal_attn_packed(qkv.data_ptr(), mask.data_ptr(), out.data_ptr(), chunk, N, P, heads,
-                                                 D, float(scale), _stream())
+    out = torch.empty((N, chunk, P, C), dtype=qkv.dtype, device=qkv.device)
+    rc = _lib.load().fresco_temporal_attn_packed_dt(qkv.data_ptr(), mask.data_ptr(), out.data_ptr(), chunk, N, P, heads,
+                                                    D, float(scale), _MFMA_DTYPES[qkv.dtype], _stream())
     _lib.check(rc, "fresco_temporal_attn_packed(chunk=%d,N=%d,P=%d,H=%d,D=%d)" % (chunk, N, P, heads, D))
     return out
 
 
 def temporal_unpack(buf, fwd_map, chunk, n_loc, f0, world):
     """Multi-GPU, way back (fresco_temporal_unpack): buf (world, n_loc, chunk, HW/world, C) = this rank's frames'
-    result rows per trajectory range -> (chunk*n_loc, HW, C) in frame order."""
+    result rows per trajectory range -> (chunk*n_loc, HW, C) in frame order, fp16 or bf16 like buf (copies)."""
     _need_gpu(buf, fwd_map)
+    if buf.dtype not in _MFMA_DTYPES:
+        raise TypeError("fresco_amd.temporal_unpack: buf must be fp16 or bf16 (got %s)" % buf.dtype)
     w, nl, ch, Pw, C = buf.shape
     HW = Pw * world
-    out = torch.empty((chunk * n_loc, HW, C), dtype=torch.float16, device=buf.device)
+    out = torch.empty((chunk * n_loc, HW, C), dtype=buf.dtype, device=buf.device)
     rc = _lib.load().fresco_temporal_unpack(buf.contiguous().data_ptr(), fwd_map.data_ptr(), out.data_ptr(), chunk,
                                             n_loc, f0, HW, C, world, _stream())
     _lib.check(rc, "fresco_temporal_unpack(chunk=%d,n_loc=%d,HW=%d,C=%d,world=%d)" % (chunk, n_loc, HW, C, world))

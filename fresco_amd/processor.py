@@ -40,16 +40,21 @@ class FRESCOAttnProcessor2_0:
         # cross-frame-only calls (no temporal pass) read K and V of the selected tokens only: project just those
         self.sparse_kv_projection = True
         # ... and project them INSIDE the key pack: one launch instead of fresco_linear_rows + kv_pack, the selected K and V
-        # never reach HBM (fresco_attn_fwd_kvproj; plain bias-free fp16 to_k / to_v of a supported width only).  Calls with
+        # never reach HBM (fresco_attn_fwd_kvproj; plain bias-free fp16 to_k / to_v of a supported width only; bf16 ones under
+        # fuse_kv_pack_bf16).  Calls with
         # the temporal pass take it too: that pass reads K of every row but V of none, so to_q | to_k are projected in full
         # and V only inside the pack
         self.fuse_kv_pack = True
 
-    # bf16 modules / activations run on the bf16 kernels (fresco_linear_dt, fresco_attn_fwd_dt, fresco_temporal_attn_dt): no
-    # cast, no warning, bf16 out.  False restores the rounding path (library GEMMs, q / k / v rounded to fp16 for the
-    # kernels, one RuntimeWarning) for A/B measurements.  The fused K | V projection-pack stays fp16-only: bf16
-    # cross-frame-only calls take the fresco_linear_rows + grouped-attention branch.
+    # bf16 modules / activations run on the bf16 kernels (fresco_linear_dt, fresco_attn_fwd_dt, fresco_temporal_attn_dt, and
+    # fresco_temporal_attn_packed_dt in the frame-sharded branch): no cast, no warning, bf16 out.  False restores the
+    # rounding path (library GEMMs, q / k / v rounded to fp16 for the kernels, one RuntimeWarning) for A/B measurements.
     native_bf16 = True
+    # bf16 calls take the fused K | V projection-pack (fresco_attn_fwd_kvproj_dt) like fp16 ones do under fuse_kv_pack.  Off
+    # by default: no bf16 timing of the fused form against fresco_linear_rows + kv_pack has been recorded on a GPU yet
+    # (tools/bench_bf16.py measures both legs; EXPERIMENTS.md section 8), and tests/test_gpu_bf16_pipeline.py pins the
+    # default bf16 launch sequence.  Flipping the default, together with that test, is the follow-up once the numbers exist.
+    fuse_kv_pack_bf16 = False
 
     def _kernel_dtype(self, dtype):
         """activations of this dtype go through the fused projections and the attention kernels as they are"""
@@ -117,7 +122,7 @@ class FRESCOAttnProcessor2_0:
         return hit[1]
 
     def _warn_rounding(self, dtype):
-        """fp32 pipelines (and bf16 ones with native_bf16 off or frame-sharded): said once per processor (values beyond
+        """fp32 pipelines (and bf16 ones with native_bf16 off): said once per processor (values beyond
         +-65504 would become inf in the fp16 kernels)"""
         if not getattr(self, "_warned_rounding", False):
             self._warned_rounding = True
@@ -236,9 +241,12 @@ class FRESCOAttnProcessor2_0:
                 rows_all = self._sel_rows(mask, chunk_, nf, hw_, hidden_states.device)  # flat rows of both CFG halves
                 # (the spatial-guided pass in front changes nothing here: it only replaces the queries, and its use of the
                 # shared workspace is over, in stream order, before the pack writes the key image)
-                fuse_kv = (self.fuse_kv_pack and self.fuse_projections and hidden_states.dtype == torch.float16
+                fuse_kv = (self.fuse_kv_pack and self.fuse_projections
+                           and (hidden_states.dtype == torch.float16
+                                or (hidden_states.dtype == torch.bfloat16 and self.native_bf16 and self.fuse_kv_pack_bf16))
                            and hidden_states.is_cuda
                            and _plain_linear(attn.to_k, False) and _plain_linear(attn.to_v, False)
+                           and attn.to_k.weight.dtype == attn.to_v.weight.dtype == hidden_states.dtype
                            and attn.to_k.weight.is_contiguous() and attn.to_v.weight.is_contiguous()
                            # the pack copies 16-byte pieces of the weights and of the hidden rows: a contiguous but misaligned
                            # view (a slice of a flat parameter buffer) takes the unfused path
@@ -366,13 +374,16 @@ def _sharded_self_attention(self, attn, hidden_states, residual, input_ndim):
     """Frame-parallel form of the FRESCO self-attention branch (fresco_amd/dist.py): this rank holds
     `shard.n_loc` frames of both CFG halves.  Cross-frame keys: broadcast of frame 0 + all-gather of the
     other frames' selected rows; temporal pass: all-to-all to trajectory shards and back; the rest is local.
-    This branch computes in fp16 whatever native_bf16 says (the packed temporal entry points and the exchange buffers are
-    fp16): bf16 activations are rounded to fp16 after the projections, with the RuntimeWarning, and the result is cast
-    back."""
+    fp16 and (with native_bf16) bf16 activations run it in their own dtype: projections, exchange buffers, the attention
+    passes and the packed temporal entry points, no cast and no warning.  q | k | v are projected in full either way (K | V
+    cross the exchange: the fused projection-pack has no role here).  fp32 activations, and bf16 ones with native_bf16 off,
+    are rounded to fp16 after the projections, with the RuntimeWarning, and the result is cast back."""
     if input_ndim != 3:
         raise NotImplementedError("fresco_amd: frame-sharded attention expects (B, HW, C) hidden states")
     out_dtype = hidden_states.dtype
-    if out_dtype != torch.float16:  # same policy as the single-GPU path: modules in their dtype, kernels in fp16
+    # same policy as the single-GPU path: modules in their dtype, kernels in fp16 or native bf16, anything else rounded to fp16
+    kdt = out_dtype if self._kernel_dtype(out_dtype) else torch.float16
+    if kdt != out_dtype:
         self._warn_rounding(out_dtype)
     ctrl, sh = self.controller, self.shard
     chunk = self.unet_chunk_size
@@ -383,8 +394,8 @@ def _sharded_self_attention(self, attn, hidden_states, residual, input_ndim):
     sm_scale = 1.0 / math.sqrt(head_dim)
     assert B_loc == sh.B_loc and chunk == sh.chunk
     # q, k, v in one pass over the hidden states; K and V land fused per row (K | V), the layout of the exchange
-    query = torch.empty(B_loc, hw, C, dtype=torch.float16, device=hidden_states.device)
-    kv_loc = torch.empty(B_loc, hw, 2 * C, dtype=torch.float16, device=hidden_states.device)
+    query = torch.empty(B_loc, hw, C, dtype=kdt, device=hidden_states.device)
+    kv_loc = torch.empty(B_loc, hw, 2 * C, dtype=kdt, device=hidden_states.device)
     key, value = kv_loc[..., :C], kv_loc[..., C:]
     self._project(attn, hidden_states, ("to_q", "to_k", "to_v"), outs=[query, key, value])
     works = []
@@ -402,8 +413,8 @@ def _sharded_self_attention(self, attn, hidden_states, residual, input_ndim):
         ref = ctrl(None)
         assert ref.shape == hidden_states.shape
         q_ref, k_ref = self._project(attn, ref, ("to_q", "to_k"))
-        if q_ref.dtype != torch.float16:
-            q_ref, k_ref = q_ref.half(), k_ref.half()
+        if q_ref.dtype != kdt:
+            q_ref, k_ref = q_ref.to(kdt), k_ref.to(kdt)
         q_att = ops.attention(q_ref, k_ref, query, heads,
                               ctrl.intraattn_scale_factor * sm_scale, diag_bias=float(ctrl.intraattn_bias),
                               workspace=self._ws)
@@ -445,8 +456,7 @@ def apply_FRESCO_attn(pipe):
     Narrower than the reference on purpose (there is no eager fallback behind the HIP kernels): the processor takes
     CUDA hidden states and computes the attention in fp16 (the dtype run_fresco.py runs the UNet in, :63-80) or, for a
     bf16 pipeline, in bf16 (FRESCOAttnProcessor2_0.native_bf16); fp32 activations are rounded to fp16 after the
-    projections and the result is cast back (one RuntimeWarning per processor), and so are bf16 ones in frame-sharded
-    runs; an `attention_mask` (the pipeline never passes one to these layers)
+    projections and the result is cast back (one RuntimeWarning per processor); an `attention_mask` (the pipeline never passes one to these layers)
     is honoured on the plain / cross-attention path through a padded-head-dim side path, and rejected where the reference
     itself cannot use it (together with cross-frame attention) or where it depends on the query."""
     from diffusers.models.attention_processor import AttnProcessor2_0

@@ -181,6 +181,15 @@ int fresco_attn_fwd_kvproj(const void* q, const void* x, int64_t x_ld, const int
                            const void* Wv, void* out, void* workspace, size_t workspace_bytes, int B, int H, int Lq,
                            int D, int n_groups, int M, int K_in, float scale, int64_t q_ld, void* stream);
 
+/* fresco_attn_fwd_kvproj with an element type: dtype = FRESCO_F16 or FRESCO_BF16 for q, x, Wk, Wv and out (any other
+ * code: FRESCO_EINVAL; every argument check answers before any HIP call).  bf16: the projection on the bf16 MFMA with
+ * the same contraction order and one fp32 chain per output, K and V rounded to bf16 once, the ones column / row of the
+ * image in bf16, max |k|^2 over the rounded K; then the bf16 flash kernels of fresco_attn_fwd_dt (scale never folded).
+ * fresco_attn_fwd_kvproj is this with FRESCO_F16. */
+int fresco_attn_fwd_kvproj_dt(const void* q, const void* x, int64_t x_ld, const int32_t* x_rows, const void* Wk,
+                              const void* Wv, void* out, void* workspace, size_t workspace_bytes, int B, int H, int Lq,
+                              int D, int n_groups, int M, int K_in, float scale, int64_t q_ld, int dtype, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * (a4)  Temporal-guided (FLATTEN) attention -- replaces DH:309-367: 3 rearrange+gather round
  * trips, the per-pixel N x N masked SDPA and the inverse gather.
@@ -209,7 +218,7 @@ int fresco_temporal_attn_ld(const void* q, const void* k, const void* v, const i
 
 /* The row-strided form with an element type: dtype = FRESCO_F16 or FRESCO_BF16 for q, k, v and out (any other code:
  * FRESCO_EINVAL before any HIP call).  The scale (the reference's 0.2 key factor included) stays an fp32 factor of the
- * scores.  The packed / sharded entry points below are fp16 only. */
+ * scores.  The packed form has its own: fresco_temporal_attn_packed_dt below. */
 int fresco_temporal_attn_dt(const void* q, const void* k, const void* v, const int64_t* fwd_map,
                             const uint8_t* mask, void* out,
                             int chunk, int N, int HW, int H, int D, float scale,
@@ -233,6 +242,12 @@ int fresco_temporal_attn_packed(const void* qkv, const uint8_t* mask, void* out,
                                 float scale, void* stream);
 int fresco_temporal_unpack(const void* buf, const int64_t* fwd_map, void* out, int chunk, int n_loc, int f0, int HW,
                            int C, int world, void* stream);
+/* fresco_temporal_attn_packed with an element type: dtype = FRESCO_F16 or FRESCO_BF16 for qkv and out (any other code:
+ * FRESCO_EINVAL before any HIP call); fresco_temporal_attn_packed is this with FRESCO_F16.
+ * fresco_temporal_pack / fresco_temporal_unpack move 16-byte pieces of 16-bit words and do no arithmetic: they are
+ * element-type agnostic for 2-byte types (fp16 and bf16 alike) and need no dtype. */
+int fresco_temporal_attn_packed_dt(const void* qkv, const uint8_t* mask, void* out, int chunk, int N, int P, int H,
+                                   int D, float scale, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a8)  flow_warp / bilinear_sample  (GEO:41-72): bilinear, zeros padding, align_corners=True.

@@ -1,13 +1,16 @@
 """Layer-call timing of a bf16 pipeline against the alternatives, on cfg2's attention shapes:
 L3 = up_blocks.3 (16, 4096, 320) and L2 = up_blocks.2 (16, 1024, 640), Bernoulli(0.1) occlusions, modes cf / cf_temporal /
 full.  Variants, per shape and mode:
-  (a) bf16 native   : bf16 module and activations, FRESCOAttnProcessor2_0.native_bf16 = True (the bf16 kernels)
+  (a) bf16 native   : bf16 module and activations, FRESCOAttnProcessor2_0.native_bf16 = True (the bf16 kernels), the default
+                      two-launch K | V path (fresco_linear_rows + kv_pack)
+  (a') bf16 fused   : the same with fuse_kv_pack_bf16 = True (K | V projected inside the key pack, fresco_attn_fwd_kvproj_dt)
   (b) bf16 rounding : the same with native_bf16 = False (library GEMMs, q / k / v rounded to fp16, cast back)
   (c) fp16          : fp16 module and activations (the headline path, fused K | V pack included)
   (d) torch bf16    : oracle/torch_path.processor_call on bf16 cuda tensors = the reference's op sequence
 One process; warm-up, then BLOCKS timed blocks; inside a block the variants ALTERNATE call by call (REPS rounds), each call
 bracketed by its own pair of HIP events; per variant the median over blocks of the block means, and min - max over blocks.
-On a tree without native_bf16 (the parent commit) setting the attribute is harmless and (a) = (b) = that tree's bf16 time.
+On a tree without native_bf16 (the parent commit) setting the attribute is harmless and (a) = (b) = that tree's bf16 time;
+likewise (a') = (a) on a tree without fuse_kv_pack_bf16.  f/a compares the fused pack with the same tree's two-launch path.
 usage: python tools/bench_bf16.py [reps] [blocks]"""
 import copy
 import os
@@ -30,9 +33,10 @@ warnings.simplefilter("ignore", RuntimeWarning)  # (b) says once per processor t
 
 
 def variants(case, mode):
-    def ours(dtype, native):
+    def ours(dtype, native, fused_bf16=False):
         proc = fresco_amd.FRESCOAttnProcessor2_0(2, synth.controller_for(case, mode, DEV, dtype=dtype))
         proc.native_bf16 = native
+        proc.fuse_kv_pack_bf16 = fused_bf16
         attn = copy.deepcopy(case["attn"]).to(DEV).to(dtype)
         x = case["hidden"].to(DEV).to(dtype)
         return lambda: proc(attn, x)
@@ -48,7 +52,8 @@ def variants(case, mode):
         return lambda: TP.processor_call(x, a.to_q.weight, a.to_k.weight, a.to_v.weight, a.to_out[0].weight,
                                          a.to_out[0].bias, case["heads"], **kw)
 
-    return [("(a) bf16 native", ours(torch.bfloat16, True)), ("(b) bf16 rounding", ours(torch.bfloat16, False)),
+    return [("(a) bf16 native", ours(torch.bfloat16, True)), ("(a') bf16 fused", ours(torch.bfloat16, True, True)),
+            ("(b) bf16 rounding", ours(torch.bfloat16, False)),
             ("(c) fp16", ours(torch.float16, True)), ("(d) torch bf16", torch_seq())]
 
 
@@ -81,8 +86,8 @@ def main():
             for name, _ in vs:
                 m = means[name]
                 row += " | %s %7.1f [%7.1f - %7.1f]" % (name, statistics.median(m), min(m), max(m))
-            a, b, c, d = (statistics.median(means[name]) for name, _ in vs)
-            print(row + " | a/b %.2f a/c %.2f a/d %.2f" % (a / b, a / c, a / d), flush=True)
+            a, f, b, c, d = (statistics.median(means[name]) for name, _ in vs)
+            print(row + " | f/a %.3f a/b %.2f a/c %.2f a/d %.2f" % (f / a, a / b, a / c, a / d), flush=True)
 
 
 if __name__ == "__main__":
