@@ -62,6 +62,7 @@ SIGNATURES = {
                               _i, _vp]),
     "fresco_linear_rows_dt": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i,
                                    _i, _i, _i, _vp]),
+    "fresco_linear_plan": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
     "fresco_attn_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "fresco_attn_f32_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fresco_attn_f32_ws": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _f, _vp]),

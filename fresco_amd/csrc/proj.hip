@@ -12,9 +12,14 @@
 // ds_read_b128); the weights (<= 2.4 MB) stay L2-resident.
 //
 // grid (ceil(M/256), splits): 8 waves x 32 rows; blockIdx.y takes a contiguous range of 64-feature tiles
-// (splits > 1 only when M/256 alone cannot fill the chip).  What bounds the kernel is the rate at which a CU
-// can stream the weight slabs into LDS (~25 GB/s per CU for LDS-DMA): every workgroup reads all of W, so rows per
-// workgroup, not MFMA or HBM time, set the floor -- 256 rows (one workgroup per CU) halve that traffic vs 128.
+// (splits > 1 only when M/256 alone cannot fill the chip).  Loop regimes (plan_linear below decides,
+// fresco_linear_plan reports, tests/test_gpu_linear_regimes.py walks them): while ceil(256 / row blocks) covers the
+// nw * N / 64 tiles (q,k,v at 320: up to M = 4608) a workgroup gets ONE tile -- at K = 320 the ring sees its
+// prologue only and the output cursor never moves; beyond, several -- in-loop staging, the ring wraps, and a split
+// may begin inside an output, run across two or three outputs, or (the last one) be shorter; from M = 65281 on one
+// split walks every tile.  What bounds the kernel is the rate at which a CU can stream the weight slabs into LDS
+// (~25 GB/s per CU for LDS-DMA): every workgroup reads all of W, so rows per workgroup, not MFMA or HBM time, set
+// the floor -- 256 rows (one workgroup per CU) halve that traffic vs 128.
 // Measured (MI355X, M = 65536, K = 320, q,k,v in one launch): 56.6 us (round 1: 63.6); tools/proj_abl.hip: x loads +
 // loop 11 us, + LDS fragment reads 10, + weight DMA 6.5, + MFMA 17, + output stores 12 -- the parts ADD UP: with one
 // barrier-coupled workgroup per CU nothing overlaps.  Splitting the features over more workgroups (staggered
@@ -313,26 +318,49 @@ static auto linear_kernel_of() {
         return &linear_kernel<K, NWV>;
 }
 
-template <typename T, int K, int NWV>
-static int launch_linear(const T* x, int64_t x_ld, const int32_t* x_rows, const T* const* W, const T* const* bias,
-                         T* out0, T* out1, T* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M,
-                         int N, hipStream_t st) {
+// What a launch for (nw, M, N, K) looks like, decided on the host alone (fresco_linear_plan reports it; tests ask it which loop
+// regime a shape lands in): grid (row_blocks, splits), every workgroup walking up to tiles_per_split 64-feature tiles of the
+// nw * N / 64 tiles of the concatenated outputs.  tiles_per_split == 1: the weight ring sees its prologue only (K = 320) and
+// the output cursor never moves; >= 2: in-loop staging, the ring wraps, and a split may begin in the middle of an output, run
+// across two or three outputs, or -- the last one -- be shorter than the others.
+struct LinearPlan {
+    int lds_bytes, nF, row_blocks, splits, tiles_per_split;
+};
+
+template <int K, int NWV>
+static int plan_linear_k(int nw, int M, int N, LinearPlan* p) {
     using Cfg = ProjCfg<K, NWV>;
-    const int lds_bytes = Cfg::BIAS_OFF + nw * N * 2;
+    const int64_t lds_bytes = Cfg::BIAS_OFF + (int64_t)nw * N * 2;  // (the bias region is part of the plan with or without biases)
     if (lds_bytes > 160 * 1024) return FRESCO_EUNSUPPORTED;
-    auto kern = linear_kernel_of<T, K, NWV>();
-    if (int rc = allow_dyn_lds(kern, lds_bytes)) return rc;
     const int nF = nw * N / Cfg::TF;
-    const int row_blocks = (M + NWV * 32 - 1) / (NWV * 32);
+    const int row_blocks = (int)(((int64_t)M + NWV * 32 - 1) / (NWV * 32));
     // enough workgroups for two rounds of the 256 CUs; every extra split re-reads x once
     int splits = (2048 / NWV + row_blocks - 1) / row_blocks;
     if (splits > nF) splits = nF;
     if (splits < 1) splits = 1;
     const int tiles_per_split = (nF + splits - 1) / splits;
     splits = (nF + tiles_per_split - 1) / tiles_per_split;
+    *p = LinearPlan{(int)lds_bytes, nF, row_blocks, splits, tiles_per_split};
+    return FRESCO_OK;
+}
+
+// The shape checks of linear_dispatch and the plan of the launch it would make: host arithmetic only
+static int plan_linear(int nw, int M, int N, int K, LinearPlan* p) {
+    if (nw < 1 || nw > 3 || M <= 0 || N <= 0 || K <= 0) return FRESCO_EINVAL;
+    if (N % 64 != 0 || (K != 320 && K != 640)) return FRESCO_EUNSUPPORTED;
+    if (K == 320) return plan_linear_k<320, 8>(nw, M, N, p);
+    return plan_linear_k<640, 8>(nw, M, N, p);
+}
+
+template <typename T, int K, int NWV>
+static int launch_linear(const T* x, int64_t x_ld, const int32_t* x_rows, const T* const* W, const T* const* bias,
+                         T* out0, T* out1, T* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M,
+                         int N, const LinearPlan& p, hipStream_t st) {
+    auto kern = linear_kernel_of<T, K, NWV>();
+    if (int rc = allow_dyn_lds(kern, p.lds_bytes)) return rc;
     ProfScope ps(FRESCO_PROF_LINEAR, M, N, K, nw, st);
-    hipLaunchKernelGGL(kern, dim3(row_blocks, splits), dim3(NWV * 64), lds_bytes, st, x, x_ld, x_rows, W[0], W[1],
-                       W[2], bias[0], bias[1], bias[2], out0, out1, out2, ld0, ld1, ld2, M, N, nF, tiles_per_split);
+    hipLaunchKernelGGL(kern, dim3(p.row_blocks, p.splits), dim3(NWV * 64), p.lds_bytes, st, x, x_ld, x_rows, W[0], W[1],
+                       W[2], bias[0], bias[1], bias[2], out0, out1, out2, ld0, ld1, ld2, M, N, p.nF, p.tiles_per_split);
     return check_launch();
 }
 
@@ -343,15 +371,16 @@ using namespace fresco;
 template <typename T>
 static int linear_launch_t(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1, const void* W2,
                            const void* b0, const void* b1, const void* b2, void* out0, void* out1, void* out2, int64_t ld0,
-                           int64_t ld1, int64_t ld2, int nw, int M, int N, int K, hipStream_t st) {
+                           int64_t ld1, int64_t ld2, int nw, int M, int N, int K, const LinearPlan& p,
+                           hipStream_t st) {
     const T* xh = static_cast<const T*>(x);
     const T* wh[3] = {static_cast<const T*>(W0), static_cast<const T*>(W1), static_cast<const T*>(W2)};
     const T* bh[3] = {static_cast<const T*>(b0), static_cast<const T*>(b1), static_cast<const T*>(b2)};
     T* o0 = static_cast<T*>(out0);
     T* o1 = static_cast<T*>(out1);
     T* o2 = static_cast<T*>(out2);
-    if (K == 320) return launch_linear<T, 320, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, st);
-    return launch_linear<T, 640, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, st);
+    if (K == 320) return launch_linear<T, 320, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, p, st);
+    return launch_linear<T, 640, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, p, st);
 }
 
 static int linear_dispatch(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1,
@@ -359,17 +388,26 @@ static int linear_dispatch(const void* x, int64_t x_ld, const int32_t* x_rows, c
                            void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, int dtype,
                            void* stream) {
     if (dtype != FRESCO_F16 && dtype != FRESCO_BF16) return FRESCO_EINVAL;
-    if (!x || !W0 || !out0 || nw < 1 || nw > 3 || M <= 0 || N <= 0 || K <= 0) return FRESCO_EINVAL;
+    if (!x || !W0 || !out0) return FRESCO_EINVAL;  // (nw and the sizes: plan_linear, below)
     if ((nw > 1 && (!out1 || !W1)) || (nw > 2 && (!out2 || !W2))) return FRESCO_EINVAL;
     if (x_ld < K || x_ld % 8 != 0) return FRESCO_EINVAL;
     if (ld0 < N || ld0 % 8 != 0 || (nw > 1 && (ld1 < N || ld1 % 8 != 0)) || (nw > 2 && (ld2 < N || ld2 % 8 != 0)))
         return FRESCO_EINVAL;
-    if (N % 64 != 0 || (K != 320 && K != 640)) return FRESCO_EUNSUPPORTED;
-    if ((int64_t)(M + 127) / 128 > 0x7fffffff) return FRESCO_EUNSUPPORTED;
+    LinearPlan plan;
+    if (int rc = plan_linear(nw, M, N, K, &plan)) return rc;
     hipStream_t st = as_stream(stream);
     if (dtype == FRESCO_BF16)
-        return linear_launch_t<bf16_t>(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, st);
-    return linear_launch_t<half_t>(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, st);
+        return linear_launch_t<bf16_t>(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, plan, st);
+    return linear_launch_t<half_t>(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, plan, st);
+}
+
+extern "C" int fresco_linear_plan(int nw, int M, int N, int K, int* row_blocks, int* splits, int* tiles_per_split) {
+    LinearPlan plan;
+    if (int rc = plan_linear(nw, M, N, K, &plan)) return rc;
+    if (row_blocks) *row_blocks = plan.row_blocks;
+    if (splits) *splits = plan.splits;
+    if (tiles_per_split) *tiles_per_split = plan.tiles_per_split;
+    return FRESCO_OK;
 }
 
 extern "C" int fresco_linear(const void* x, int64_t x_ld, const void* W0, const void* W1, const void* W2,

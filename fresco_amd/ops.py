@@ -4,6 +4,7 @@ PyTorch is used for device memory, the current HIP stream and dtype casts only; 
 below is one call into libfresco_hip.so.  All functions require HIP ("cuda") tensors and raise on
 CPU tensors -- there is no fallback path.
 """
+import ctypes
 import math
 
 import torch
@@ -79,7 +80,6 @@ class OptContext:
     by the caller -- the library keeps no process-wide stream table; one context per host thread and device."""
 
     def __init__(self):
-        import ctypes
         p = ctypes.c_void_p()
         _lib.check(_lib.load().fresco_ctx_create(ctypes.byref(p)), "fresco_ctx_create")
         self.ptr = p
@@ -141,9 +141,29 @@ _default_ws = _PerStreamWorkspace()
 _MFMA_DTYPES = {torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 
 
-def linear_supported(K, N, dtype):
-    """shapes / dtype fresco_linear takes (SD-1.5 up_blocks.2/3 attention widths); others keep torch's GEMM"""
-    return dtype in _MFMA_DTYPES and K in (320, 640) and N % 64 == 0
+_linear_supported = {}
+
+
+def linear_plan(nw, M, N, K):
+    """(rc, row_blocks, splits, tiles_per_split) of the launch `linear` would make for nw weights of (N, K) and M rows
+    (fresco_linear_plan: host arithmetic, no GPU needed); rc != 0 (the library's refusal) leaves the rest at 0"""
+    rb, sp, tps = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    rc = _lib.load().fresco_linear_plan(int(nw), int(M), int(N), int(K), ctypes.byref(rb), ctypes.byref(sp),
+                                        ctypes.byref(tps))
+    return rc, rb.value, sp.value, tps.value
+
+
+def linear_supported(K, N, dtype, nw=1):
+    """shapes / dtype fresco_linear takes for a launch of `nw` weights (SD-1.5 up_blocks.2/3 attention widths; nw * N is
+    bounded by the kernel's LDS plan); others keep torch's GEMM.  The library answers (fresco_linear_plan), not a copy of
+    its rules; the answer per (K, N, nw) is kept, the processor asks on every layer call)."""
+    if dtype not in _MFMA_DTYPES:
+        return False
+    key = (K, N, nw)
+    ok = _linear_supported.get(key)
+    if ok is None:
+        ok = _linear_supported[key] = linear_plan(nw, 1, N, K)[0] == _lib.OK
+    return ok
 
 
 def linear(x, weights, biases=None, outs=None, x_rows=None, x_rows_trusted=False):

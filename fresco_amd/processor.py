@@ -22,10 +22,11 @@ from . import _lib, ops
 from .control import AttentionControl
 
 
-def _plain_linear(m, with_bias):
-    """an unwrapped nn.Linear whose forward is exactly x W^T (+ b): safe to run through fresco_linear"""
+def _plain_linear(m, with_bias, nw=1):
+    """an unwrapped nn.Linear whose forward is exactly x W^T (+ b): safe to run through fresco_linear, in a launch of
+    `nw` such weights"""
     return (type(m) is torch.nn.Linear and (m.bias is not None) == with_bias and m.weight.is_cuda
-            and ops.linear_supported(m.in_features, m.out_features, m.weight.dtype))
+            and ops.linear_supported(m.in_features, m.out_features, m.weight.dtype, nw))
 
 
 class FRESCOAttnProcessor2_0:
@@ -68,7 +69,7 @@ class FRESCOAttnProcessor2_0:
         module's weight where it lives: nothing is stacked or cached, in-place weight updates are always seen."""
         mods = [getattr(attn, n) for n in names]
         if (self.fuse_projections and self._kernel_dtype(x.dtype) and x.is_cuda
-                and all(_plain_linear(m, False) and m.weight.dtype == x.dtype for m in mods)
+                and all(_plain_linear(m, False, len(mods)) and m.weight.dtype == x.dtype for m in mods)
                 and (outs is None or all(o.dtype == x.dtype for o in outs))
                 and len({(m.in_features, m.out_features) for m in mods}) == 1
                 and all(m.weight.is_contiguous() and m.weight.data_ptr() % 16 == 0 for m in mods)):
@@ -87,9 +88,8 @@ class FRESCOAttnProcessor2_0:
         lin = attn.to_out[0]
         # (round 3 left the C = 640 case to the library GEMM; on repeated measurement the two tie within the box-to-box
         # spread -- 27-30 us here, 24-33 us hipBLASLt at (16384, 640, 640) -- so the hot path now has no library GEMM)
-        if (self.fuse_projections and self._kernel_dtype(hs.dtype) and hs.is_cuda and _plain_linear(lin, True)
-                and lin.weight.dtype == hs.dtype and lin.bias.dtype == hs.dtype
-                and ops.linear_supported(lin.in_features, lin.out_features, hs.dtype)):
+        if (self.fuse_projections and self._kernel_dtype(hs.dtype) and hs.is_cuda and _plain_linear(lin, True, 1)
+                and lin.weight.dtype == hs.dtype and lin.bias.dtype == hs.dtype):
             return ops.linear(hs, [lin.weight.detach()], [lin.bias.detach()])[0]
         return lin(hs)
 

@@ -111,8 +111,8 @@ size_t fresco_attn_workspace_bytes(int n_groups, int H, int M, int D);
  *   b_j  : (N) half or NULL
  *   out_j: (M, N) half, row stride ld_j (elements); unused outputs NULL
  *   fp32 accumulation, one rounding to half at the end (what the library GEMM behind nn.Linear does).
- *   Supported: K in {320, 640} (SD-1.5 up_blocks.3 / up_blocks.2), N % 64 == 0; anything else returns
- *   FRESCO_EUNSUPPORTED and the caller keeps its own GEMM.
+ *   Supported: K in {320, 640} (SD-1.5 up_blocks.3 / up_blocks.2), N % 64 == 0, nw * N <= 2048 (fresco_linear_plan
+ *   answers without a launch); anything else returns FRESCO_EUNSUPPORTED and the caller keeps its own GEMM.
  * ------------------------------------------------------------------------------------------ */
 int fresco_linear(const void* x, int64_t x_ld, const void* W0, const void* W1, const void* W2, const void* b0,
                   const void* b1, const void* b2, void* out0, void* out1, void* out2, int64_t ld0, int64_t ld1,
@@ -135,6 +135,17 @@ int fresco_linear_rows_dt(const void* x, int64_t x_ld, const int32_t* x_rows, co
                           const void* W2, const void* b0, const void* b1, const void* b2, void* out0, void* out1,
                           void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, int dtype,
                           void* stream);
+
+
+/* The launch fresco_linear* would make for (nw, M, N, K), decided on the host alone (no launch, no HIP call, no GPU needed):
+ * returns what those entry points return for the same four arguments -- FRESCO_EINVAL for nw outside 1..3 or a size <= 0,
+ * FRESCO_EUNSUPPORTED for N % 64 != 0, K outside {320, 640} or an LDS plan beyond 160 KiB (ring + x staging + an nw * N
+ * bias image, charged with or without biases: nw * N <= 2048) -- and, on FRESCO_OK, writes the grid (row_blocks =
+ * ceil(M / 256), splits) and the number of 64-feature tiles of the nw * N / 64 a workgroup walks (the last split may get
+ * fewer).  Each output pointer may be NULL.  Callers use it to ask "is this width supported"; tests, which loop regime of
+ * the kernel a shape lands in (one tile per split; several, where the weight ring wraps and a split may begin inside an
+ * output or run across two or three). */
+int fresco_linear_plan(int nw, int M, int N, int K, int* row_blocks, int* splits, int* tiles_per_split);
 
 
 int fresco_attn_fwd(const void* q, const void* k, const void* v, const int32_t* kv_rows,

@@ -19,6 +19,8 @@ def _ref(x, W, b, nw):
                                             (320, 320, 1, 4096, True), (640, 640, 2, 129, True),
                                             (320, 64, 1, 5, False), (640, 128, 3, 128, True), (320, 960, 1, 777, True)])
 def test_linear_matches_fp32_matmul(K, N, nw, M, bias):
+    """(every shape here gives a workgroup ONE feature tile; tests/test_gpu_linear_regimes.py walks the multi-tile regimes,
+    per element against fp64)"""
     import fresco_amd.ops as ops
     g = synth.gen(K + N + nw + M)
     x = torch.randn(M, K, generator=g).half()
@@ -66,6 +68,22 @@ def test_linear_rejects_unsupported():
         ops.linear(x, W)
     with pytest.raises(ValueError):
         ops.linear(x.float(), W)
+    # a width beyond the kernel's LDS plan (nw * N = 2112 > 2048), an output with another row count than x, an output whose
+    # last dimension is not dense: all refused before any launch -- the outputs keep their fill
+    x = torch.ones(8, 320, dtype=torch.float16, device=DEV)
+    W = torch.ones(704, 320, dtype=torch.float16, device=DEV)
+    assert ops.linear_supported(320, 704, torch.float16, 2) and not ops.linear_supported(320, 704, torch.float16, 3)
+    outs = [torch.full((8, 704), -7.0, dtype=torch.float16, device=DEV) for _ in range(3)]
+    with pytest.raises(fresco_amd.FrescoHipError):
+        ops.linear(x, [W, W, W], outs=outs)
+    short = torch.full((7, 704), -7.0, dtype=torch.float16, device=DEV)
+    with pytest.raises(ValueError):
+        ops.linear(x, W, outs=[short])
+    sparse = torch.full((8, 1408), -7.0, dtype=torch.float16, device=DEV)
+    with pytest.raises(ValueError):
+        ops.linear(x, W, outs=[sparse[:, ::2]])
+    torch.cuda.synchronize()
+    assert all(bool((t == -7.0).all()) for t in outs + [short, sparse])
 
 
 class _Scaled(torch.nn.Linear):

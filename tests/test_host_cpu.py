@@ -176,6 +176,44 @@ def test_capi_argument_validation_without_gpu():
     assert run(wsb=need - 1) == EWS
 
 
+def test_linear_supported_answers_from_the_launch_plan():
+    """ops.linear_supported(K, N, dtype, nw) is true exactly where fresco_linear_plan -- the host function the launch itself
+    plans with -- accepts the shape: N % 64 == 0, K in {320, 640}, and an LDS plan within 160 KiB, i.e. nw * N <= 2048 (the
+    bias image is charged with or without biases).  The processor trusts this answer before it skips a module's forward."""
+    import ctypes
+    import fresco_amd.ops as ops
+    from fresco_amd import _lib
+    lib = _lib.load()
+    EINVAL, EUNSUP = -1, -2
+    for K in (320, 640, 256):
+        for N in (64, 320, 640, 672, 704, 1024, 1088, 2048, 2112, 100):
+            for nw in (1, 2, 3):
+                rc = lib.fresco_linear_plan(nw, 4096, N, K, None, None, None)
+                want = K in (320, 640) and N % 64 == 0 and nw * N <= 2048
+                assert rc == (0 if want else EUNSUP), (K, N, nw, rc)
+                for dt in (torch.float16, torch.bfloat16):
+                    assert ops.linear_supported(K, N, dt, nw) == (rc == 0), (K, N, nw)
+                assert not ops.linear_supported(K, N, torch.float32, nw)
+    assert ops.linear_supported(320, 1088, torch.float16) and not ops.linear_supported(320, 1088, torch.float16, nw=2)
+    # the argument checks of the launch, in its order; every output pointer is optional
+    for bad in ((0, 8, 64, 320), (4, 8, 64, 320), (1, 0, 64, 320), (1, 8, 0, 320), (1, 8, 64, 0), (1, -1, 100, 256)):
+        assert lib.fresco_linear_plan(*bad, None, None, None) == EINVAL, bad
+    # the plan: ceil(M / 256) row blocks; splits = min(tiles, ceil(256 / row blocks)), evened out over the tiles
+    rb, sp, tps = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    plan = lambda nw, M, N, K: (lib.fresco_linear_plan(nw, M, N, K, ctypes.byref(rb), ctypes.byref(sp), ctypes.byref(tps)),
+                                rb.value, sp.value, tps.value)
+    assert plan(3, 1000, 320, 320) == (0, 4, 15, 1)
+    assert plan(3, 4700, 320, 320) == (0, 19, 8, 2)      # 14 splits asked, 2 tiles each -> 8 splits, the last with 1
+    assert plan(3, 65281, 320, 320) == (0, 256, 1, 15)
+    assert plan(3, 65535, 640, 640) == (0, 256, 1, 30)
+    assert plan(1, 2 ** 31 - 1, 64, 320) == (0, 2 ** 23, 1, 1)
+    assert ops.linear_plan(2, 8500, 640, 640) == (0, 34, 7, 3)
+    for nw, M, N, K in ((3, 777, 320, 320), (2, 8500, 640, 640), (1, 3000, 2048, 320), (3, 45000, 64, 320)):
+        rc, b, s, t = plan(nw, M, N, K)
+        nF = nw * N // 64
+        assert rc == 0 and b == -(-M // 256) and (s - 1) * t < nF <= s * t and 1 <= s <= nF
+
+
 def test_standin_unet_has_the_sd15_shapes():
     """tools/standin_unet.py (full-step measurement only): parameter counts and the tensors entering the four
     up-blocks must be SD-1.5's, and the hook of apply_FRESCO_opt must see them."""

@@ -63,5 +63,6 @@ def test_kvproj_dt_unsupported_shape_without_a_device(lib):
     del keep
 
 
-def test_version_is_0_3_0(lib):
-    assert "0.3.0" in lib.fresco_version().decode()
+def test_version_is_0_4_0(lib):
+    """(0.3.0 added the bf16 K | V pack entry points; 0.4.0, fresco_linear_plan)"""
+    assert "0.4.0" in lib.fresco_version().decode()
