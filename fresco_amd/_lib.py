@@ -115,6 +115,9 @@ SIGNATURES = {
     "fresco_poisson_fusion": (_i, [_vp] * 4 + [_i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "fresco_flowcalc_input": (_i, [_vp] * 4 + [_i] * 4 + [_vp]),
     "fresco_flowcalc_output": (_i, [_vp] * 5 + [_i, _i, _i, _f, _f, _vp]),
+    "fresco_freeu_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "fresco_freeu_fourier": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _f, _i, _vp]),
+    "fresco_freeu_backbone": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _f, _vp, _sz, _i, _vp]),
 }
 
 _lib = None

@@ -880,6 +880,84 @@ def chan_mean_std(feat, eps=1e-5):
 
 
 # ---------------------------------------------------------------------------------------------
+# FreeU (src/free_lunch_utils.py): closed-form skip filter and backbone scaling at the up-block sites
+# ---------------------------------------------------------------------------------------------
+def _freeu_dense_nchw(t, name):
+    """(batch stride in elements) of a 4-D tensor whose samples are dense (C, H, W) blocks: a contiguous tensor or a
+    channel slice of one (the tail of a concat buffer)."""
+    B, C, H, W = t.shape
+    if t.stride(3) != 1 or t.stride(2) != W or t.stride(1) != H * W or (B > 1 and t.stride(0) < C * H * W):
+        raise ValueError("%s: samples must be dense (C, H, W) blocks, got strides %s" % (name, tuple(t.stride())))
+    return t.stride(0) if B > 1 else C * H * W
+
+
+def freeu_fourier(x, scale, out=None):
+    """Fourier_filter(x, threshold=1, scale) (free_lunch_utils.py:25-52) in closed form; x (B, C, H, W) fp16 / bf16 / fp32.
+    out: a (B, C, H, W) tensor of the same dtype with dense samples (e.g. buf[:, C0:] of a concat buffer); default a new
+    tensor.  scale == 1 copies."""
+    _need_gpu(x, out)
+    if x.dim() != 4:
+        raise ValueError("freeu_fourier: expected (B, C, H, W), got %s" % (tuple(x.shape),))
+    if x.dtype not in _ELEMWISE_DTYPES:
+        raise ValueError("freeu_fourier: dtype %s (fp16, bf16 or fp32)" % x.dtype)
+    x = x.contiguous()
+    B, C, H, W = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+        raise ValueError("freeu_fourier: out %s %s vs x %s %s" % (tuple(out.shape), out.dtype, tuple(x.shape), x.dtype))
+    if x.numel() == 0:
+        return out
+    rc = _lib.load().fresco_freeu_fourier(x.data_ptr(), out.data_ptr(), _freeu_dense_nchw(out, "freeu_fourier: out"), B, C,
+                                          H, W, float(scale), _ELEMWISE_DTYPES[x.dtype], _stream())
+    _lib.check(rc, "fresco_freeu_fourier")
+    return out
+
+
+def freeu_backbone(hidden, n_scaled, b, cat=None, workspace=None):
+    """hidden[:, :n_scaled] *= (b - 1) * normalised channel mean + 1, IN PLACE (free_lunch_utils.py:130-135); hidden must
+    be contiguous (B, C, H, W) fp16 / bf16 / fp32.  cat: a tensor of the same dtype whose first C channels receive hidden
+    after the update (dense samples of >= C channels)."""
+    _need_gpu(hidden, cat)
+    if hidden.dim() != 4 or not hidden.is_contiguous():
+        raise ValueError("freeu_backbone: hidden must be a contiguous (B, C, H, W) tensor")
+    if hidden.dtype not in _ELEMWISE_DTYPES:
+        raise ValueError("freeu_backbone: dtype %s (fp16, bf16 or fp32)" % hidden.dtype)
+    B, C, H, W = hidden.shape
+    cat_bs = 0
+    if cat is not None:
+        if (cat.dim() != 4 or cat.dtype != hidden.dtype or cat.device != hidden.device or cat.shape[0] != B
+                or cat.shape[1] < C or tuple(cat.shape[2:]) != (H, W)):
+            raise ValueError("freeu_backbone: cat %s %s vs hidden %s %s" % (tuple(cat.shape), cat.dtype,
+                                                                          tuple(hidden.shape), hidden.dtype))
+        cat_bs = _freeu_dense_nchw(cat, "freeu_backbone: cat")
+    if hidden.numel() == 0:
+        return hidden
+    lib = _lib.load()
+    nbytes = lib.fresco_freeu_workspace_bytes(B, C, H, W)
+    ws = (workspace or _default_ws).get(nbytes, hidden.device)
+    rc = lib.fresco_freeu_backbone(hidden.data_ptr(), _ptr(cat), cat_bs, B, C, int(n_scaled), H, W, float(b),
+                                   ws.data_ptr(), ws.numel(), _ELEMWISE_DTYPES[hidden.dtype], _stream())
+    _lib.check(rc, "fresco_freeu_backbone")
+    return hidden
+
+
+def freeu_site(hidden, skip, n_scaled, b, s, workspace=None):
+    """One FreeU site (free_lunch_utils.py:127-149): scales hidden[:, :n_scaled] in place, filters skip, and returns
+    cat([hidden, filtered skip], dim=1) -- two library calls that write straight into the concat tensor."""
+    _need_gpu(hidden, skip)
+    B, C, H, W = hidden.shape
+    if skip.dim() != 4 or skip.shape[0] != B or tuple(skip.shape[2:]) != (H, W) or skip.dtype != hidden.dtype:
+        raise ValueError("freeu_site: skip %s %s vs hidden %s %s" % (tuple(skip.shape), skip.dtype, tuple(hidden.shape),
+                                                                    hidden.dtype))
+    cat = torch.empty((B, C + skip.shape[1], H, W), dtype=hidden.dtype, device=hidden.device)
+    freeu_backbone(hidden, n_scaled, b, cat=cat, workspace=workspace)
+    if skip.shape[1]:
+        freeu_fourier(skip, s, out=cat[:, C:])
+    return cat
+
+
+# ---------------------------------------------------------------------------------------------
 # feature optimisation (fp32)
 # ---------------------------------------------------------------------------------------------
 def _opt_args(cs, prep, target, chunk):

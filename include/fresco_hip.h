@@ -41,7 +41,7 @@ extern "C" {
 /* dtype codes for entry points that accept more than one element type */
 #define FRESCO_F16 0
 #define FRESCO_F32 1
-#define FRESCO_BF16 2 /* bfloat16: the *_dt entry points below, fresco_adain, fresco_chan_mean_std, fresco_ddpm_* */
+#define FRESCO_BF16 2 /* bfloat16: the *_dt entry points below, fresco_adain, fresco_chan_mean_std, fresco_ddpm_*, fresco_freeu_* */
 
 /* library / build identification: "fresco_hip <version> gfx950" */
 const char* fresco_version(void);
@@ -665,6 +665,32 @@ int fresco_flowcalc_input(const uint8_t* frames, const int* first, const int* se
                           int W, void* stream);
 int fresco_flowcalc_output(const float* flows, float* bwd_flow, uint8_t* bwd_occ, float* fwd_flow, uint8_t* fwd_occ,
                            int P, int H, int W, float alpha, float beta, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (k)  FreeU (src/free_lunch_utils.py:25-52, 127-147, 291-311) at the decoder's up-block sites.  DESIGN.md section 11.
+ * dtype FRESCO_F16 / FRESCO_BF16 / FRESCO_F32 for every tensor of a call (fp32 arithmetic, one rounding to nearest even
+ * at the store); tensors are dense NCHW; same inputs give bit-identical outputs (fixed reduction trees, no float atomics).
+ *   fresco_freeu_fourier : Fourier_filter(x, threshold = 1, scale) in closed form -- the four scaled FFT bins are the
+ *     frequencies {-1, 0}^2, so the filter is x plus (scale - 1) / (H W) times a seven-term combination of plane sums; no
+ *     FFT, one read and one write of x for planes up to 64 x 64.  x (B, C, H, W); out[b] starts at out +
+ *     b * out_batch_stride elements (>= C H W: the result can land in the tail of a concat buffer).  scale == 1.0f is a
+ *     plain strided copy (the reference returns x up to its FFT noise).  2 <= H, W and H + W <= 8192.
+ *   fresco_freeu_backbone: m = mean over C of hidden (B, C, H, W); per sample lo = min m, hi = max m;
+ *     hidden[:, :n_scaled] *= (b - 1) * ((m - lo) / (hi - lo)) + 1 IN PLACE (the reference mutates its input, and callers
+ *     that kept a handle on it see that); with cat != NULL, hidden after the update is also written to cat[:, :C],
+ *     cat[b] at cat + b * cat_batch_stride elements.  b == 1 runs like any other value.  A constant mean map gives
+ *     0 / 0 like the reference: the scaled channels become non-finite.  Three launches; workspace from
+ *     fresco_freeu_workspace_bytes (0 for sizes the call would refuse), 16-byte aligned.
+ * FRESCO_EUNSUPPORTED for H or W < 2 (or sizes beyond the limits above, B > 65535); FRESCO_EINVAL for null pointers,
+ * non-positive sizes, an unknown dtype, n_scaled outside [0, C], a batch stride under C H W, cat == hidden, or pointers
+ * not aligned to the element size; FRESCO_EWORKSPACE for a short workspace; all before any launch.  16-byte accesses are
+ * used when the pointers, H W and the batch stride allow; anything else takes the element-wise form of the same kernels.
+ * ------------------------------------------------------------------------------------------ */
+size_t fresco_freeu_workspace_bytes(int B, int C, int H, int W);
+int fresco_freeu_fourier(const void* x, void* out, int64_t out_batch_stride, int B, int C, int H, int W, float scale,
+                         int dtype, void* stream);
+int fresco_freeu_backbone(void* hidden, void* cat /* may be NULL */, int64_t cat_batch_stride, int B, int C, int n_scaled,
+                          int H, int W, float b, void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
