@@ -118,6 +118,9 @@ SIGNATURES = {
     "fresco_freeu_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "fresco_freeu_fourier": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _f, _i, _vp]),
     "fresco_freeu_backbone": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _f, _vp, _sz, _i, _vp]),
+    "fresco_hed_input": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
+    "fresco_hed_side_pool": (_i, [_vp] * 6 + [_i, _i, _i, _i, _f, _vp, _vp]),
+    "fresco_hed_fuse": (_i, [_vp] * 8 + [_i, _i, _i, _i, _vp]),
 }
 
 _lib = None

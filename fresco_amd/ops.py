@@ -492,8 +492,10 @@ def fn_colstats(x, n_img, eps=1e-5):
 
 
 def fn_gemm(a, w, N, K, bias=None, act=0, conv=None, M=None, want_f32=True, want_split=False, out_split=None,
-            instance_norm_eps=None, a_rows=None, out_rows=None, out_f32=None, out_blocks=0):
+            instance_norm_eps=None, a_rows=None, out_rows=None, out_f32=None, out_blocks=0, a_scale=FN_A_SCALE,
+            out_scale=FN_A_SCALE):
     """act(A W^T + bias) (fresco_fn_gemm).  a = (hi, lo) planes, (rows, lda); w = (hi, lo) planes (N, K).
+    a_scale / out_scale: the power of two the planes of `a` were written with / the output planes are written with.
     conv = (n_img, H, W, kh, kw, stride, pad): implicit im2col of the NHWC tensor behind `a` (K = kh kw cin).
     a_rows / out_rows (linear layers): int32 (M) tables -- problem row m reads input row a_rows[m], writes output row
     out_rows[m] (the rows of `out` not named by the table keep whatever they held: pass a full permutation).
@@ -542,8 +544,8 @@ def fn_gemm(a, w, N, K, bias=None, act=0, conv=None, M=None, want_f32=True, want
         zeros = _fn_zero_page[dev] = torch.zeros(64, dtype=torch.float16, device=dev)
     lib = _lib.load()
     rc = lib.fresco_fn_gemm(ah.data_ptr(), al.data_ptr(), lda, wh.data_ptr(), wl.data_ptr(), _ptr(bias), _ptr(out),
-                            _ptr(oh), _ptr(ol), int(ldc), int(ldo), M, N, K, int(act), 1.0 / (FN_A_SCALE * FN_W_SCALE),
-                            FN_A_SCALE, *cargs, _ptr(stats), zeros.data_ptr(), _ptr(a_rows), _ptr(out_rows),
+                            _ptr(oh), _ptr(ol), int(ldc), int(ldo), M, N, K, int(act), 1.0 / (float(a_scale) * FN_W_SCALE),
+                            float(out_scale), *cargs, _ptr(stats), zeros.data_ptr(), _ptr(a_rows), _ptr(out_rows),
                             _fn_flag_ptr(dev), int(ocb), int(obs), _stream())
     _lib.check(rc, "fresco_fn_gemm(M=%d,N=%d,K=%d,conv=%s)" % (M, N, K, conv))
     res = (out, ((oh, ol) if oh is not None else None))
@@ -955,6 +957,120 @@ def freeu_site(hidden, skip, n_scaled, b, s, workspace=None):
     if skip.shape[1]:
         freeu_fourier(skip, s, out=cat[:, C:])
     return cat
+
+
+# ---------------------------------------------------------------------------------------------
+# HED annotator (src/ControlNet/annotator/hed/__init__.py): the pieces around the fn_gemm convolutions (csrc/hed.hip)
+# ---------------------------------------------------------------------------------------------
+HED_CHANNELS = (64, 128, 256, 512)
+
+
+def _hed_scale(scale):
+    scale = float(scale)
+    if not (scale > 0 and math.isfinite(scale) and math.frexp(scale)[0] == 0.5):
+        raise ValueError("HED: split scale %r must be a power of two" % (scale,))
+    return scale
+
+
+def _hed_dense(t, name, dtype, shape=None, align=1):
+    """the kernels read raw words: dtype, density and (where they move 16-byte pieces) alignment are checked here, on the
+    host; the caller ends its checks with _need_gpu"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: expected a tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != dtype:
+        raise TypeError("%s: dtype %s, expected %s" % (name, t.dtype, dtype))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s: must be contiguous" % name)
+    if t.data_ptr() % align:
+        raise ValueError("%s: must be %d-byte aligned" % (name, align))
+    return t
+
+
+def hed_input(frames, norm, scale=FN_A_SCALE):
+    """frames (n, H, W, 3) uint8 RGB, norm 3 fp32 values on the device -> (hi, lo) planes (n H W, 32) of
+    (frames - norm) * scale, channels 3..31 zero (fresco_hed_input)"""
+    _hed_dense(frames, "hed_input: frames", torch.uint8)
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise ValueError("hed_input: frames must be (n, H, W, 3), got %s" % (tuple(frames.shape),))
+    norm = _hed_dense(norm, "hed_input: norm", torch.float32)
+    if norm.numel() != 3 or norm.device != frames.device:
+        raise ValueError("hed_input: norm must hold 3 values on the frames' device")
+    scale = _hed_scale(scale)
+    _need_gpu(frames)
+    n, H, W, _ = frames.shape
+    hi = torch.empty(n * H * W, 32, dtype=torch.float16, device=frames.device)
+    lo = torch.empty_like(hi)
+    rc = _lib.load().fresco_hed_input(frames.data_ptr(), norm.data_ptr(), hi.data_ptr(), lo.data_ptr(), n, H, W, scale,
+                                      _fn_flag_ptr(frames.device), _stream())
+    _lib.check(rc, "fresco_hed_input(n=%d,H=%d,W=%d)" % (n, H, W))
+    return hi, lo
+
+
+def hed_side_pool(h, n, H, W, weight, bias=None, want_proj=True, want_pool=True, scale=FN_A_SCALE):
+    """h (n H W, C) fp32 NHWC rows (post-ReLU), weight (C) / bias (1) of the block's 1 x 1 projection -> (proj (n, H, W)
+    fp32 or None, (hi, lo) planes (n (H//2) (W//2), C) of max_pool2d(h, 2, 2) * scale or None) (fresco_hed_side_pool)"""
+    _hed_dense(h, "hed_side_pool: h", torch.float32, align=16)
+    if h.dim() != 2 or h.shape[0] != n * H * W or n <= 0 or H <= 0 or W <= 0:
+        raise ValueError("hed_side_pool: h %s is not (n H W, C) rows for n, H, W = %d, %d, %d" % (tuple(h.shape), n, H, W))
+    C = h.shape[1]
+    if C not in HED_CHANNELS:
+        raise ValueError("hed_side_pool: C = %d (built for %s)" % (C, HED_CHANNELS))
+    if not (want_proj or want_pool):
+        raise ValueError("hed_side_pool: nothing asked for")
+    if want_pool and (H < 2 or W < 2):
+        raise ValueError("hed_side_pool: a %d x %d map has no pooled pixel" % (H, W))
+    weight = _hed_dense(weight, "hed_side_pool: weight", torch.float32, align=16)
+    if weight.numel() != C or weight.device != h.device:
+        raise ValueError("hed_side_pool: weight must hold C = %d values on h's device" % C)
+    if bias is not None:
+        bias = _hed_dense(bias, "hed_side_pool: bias", torch.float32)
+        if bias.numel() != 1 or bias.device != h.device:
+            raise ValueError("hed_side_pool: bias must hold one value on h's device")
+    scale = _hed_scale(scale)
+    _need_gpu(h)
+    proj = torch.empty(n, H, W, dtype=torch.float32, device=h.device) if want_proj else None
+    hi = lo = None
+    if want_pool:
+        hi = torch.empty(n * (H // 2) * (W // 2), C, dtype=torch.float16, device=h.device)
+        lo = torch.empty_like(hi)
+    rc = _lib.load().fresco_hed_side_pool(h.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(proj), _ptr(hi), _ptr(lo), n, H,
+                                          W, C, scale, _fn_flag_ptr(h.device), _stream())
+    _lib.check(rc, "fresco_hed_side_pool(n=%d,H=%d,W=%d,C=%d)" % (n, H, W, C))
+    return proj, ((hi, lo) if want_pool else None)
+
+
+def hed_level_sizes(H, W):
+    """the five block resolutions of an (H, W) frame: halved with floor four times"""
+    return [(H >> k, W >> k) for k in range(5)]
+
+
+def hed_fuse(sides, want_logit=False, cond_dtype=None):
+    """five side maps, level k (n, H >> k, W >> k) fp32 -> (edge map (n, H, W) uint8, fused logit (n, H, W) fp32 or None,
+    ControlNet condition (n, 3, H, W) of cond_dtype or None) (fresco_hed_fuse)"""
+    if len(sides) != 5:
+        raise ValueError("hed_fuse: five side maps, got %d" % len(sides))
+    s0 = _hed_dense(sides[0], "hed_fuse: side 1", torch.float32)
+    if s0.dim() != 3 or s0.numel() == 0:
+        raise ValueError("hed_fuse: side maps are (n, h, w), got %s" % (tuple(s0.shape),))
+    n, H, W = s0.shape
+    if H < 16 or W < 16:
+        raise ValueError("hed_fuse: frames of at least 16 x 16 (level 5 is the size halved four times), got %d x %d" % (H, W))
+    for k, (hk, wk) in enumerate(hed_level_sizes(H, W)):
+        _hed_dense(sides[k], "hed_fuse: side %d" % (k + 1), torch.float32, (n, hk, wk))
+        if sides[k].device != s0.device:
+            raise ValueError("hed_fuse: side maps on different devices")
+    if cond_dtype is not None and cond_dtype not in _ELEMWISE_DTYPES:
+        raise TypeError("hed_fuse: cond_dtype %s (fp16, bf16 or fp32)" % (cond_dtype,))
+    _need_gpu(s0)
+    out = torch.empty(n, H, W, dtype=torch.uint8, device=s0.device)
+    logit = torch.empty(n, H, W, dtype=torch.float32, device=s0.device) if want_logit else None
+    cond = torch.empty(n, 3, H, W, dtype=cond_dtype, device=s0.device) if cond_dtype is not None else None
+    rc = _lib.load().fresco_hed_fuse(*[t.data_ptr() for t in sides], out.data_ptr(), _ptr(logit), _ptr(cond),
+                                     _ELEMWISE_DTYPES.get(cond_dtype, _lib.F32), n, H, W, _stream())
+    _lib.check(rc, "fresco_hed_fuse(n=%d,H=%d,W=%d)" % (n, H, W))
+    return out, logit, cond
 
 
 # ---------------------------------------------------------------------------------------------

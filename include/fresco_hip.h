@@ -41,7 +41,7 @@ extern "C" {
 /* dtype codes for entry points that accept more than one element type */
 #define FRESCO_F16 0
 #define FRESCO_F32 1
-#define FRESCO_BF16 2 /* bfloat16: the *_dt entry points below, fresco_adain, fresco_chan_mean_std, fresco_ddpm_*, fresco_freeu_* */
+#define FRESCO_BF16 2 /* bfloat16: the *_dt entry points below, fresco_adain, fresco_chan_mean_std, fresco_ddpm_*, fresco_freeu_*, fresco_hed_fuse */
 
 /* library / build identification: "fresco_hip <version> gfx950" */
 const char* fresco_version(void);
@@ -691,6 +691,38 @@ int fresco_freeu_fourier(const void* x, void* out, int64_t out_batch_stride, int
                          int dtype, void* stream);
 int fresco_freeu_backbone(void* hidden, void* cat /* may be NULL */, int64_t cat_batch_stride, int B, int C, int n_scaled,
                           int H, int W, float b, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (l)  The HED annotator of the ControlNet condition (src/ControlNet/annotator/hed/__init__.py).  DESIGN.md section 12.
+ * The network's 3 x 3 convolutions are fresco_fn_gemm calls (bias + ReLU in the epilogue); these are the pieces around
+ * them.  "Planes" are the (hi, lo) fp16 operands of fresco_fn_gemm: x * split_scale = hi + lo, saturating beyond +-65000;
+ * a producer that had to saturate (or saw a NaN) ORs 1 into *range_flag (may be NULL).  Same inputs give bit-identical
+ * outputs (no float atomics).
+ *   fresco_hed_input    : frames (n, H, W, 3) uint8 RGB, norm[3] fp32 ON THE DEVICE -> the planes of (x - norm) as NHWC rows
+ *     of 32 channels, channels 3..31 zero: (n H W, 32) each.  The first convolution reads them as a 3 x 3 convolution with
+ *     cin = 32 (K = 288, weights zero-padded); its zero padding is applied to x - norm, as in the reference.
+ *   fresco_hed_side_pool: h (n, H, W, C) fp32 NHWC, the last (post-ReLU) activation of a block, C in {64, 128, 256, 512},
+ *     read once.  proj (n, H, W) fp32 = sum_c h[..][c] w[c] + bias[0]  (w: C floats, bias: 1 float or NULL; fused
+ *     multiply-adds in a fixed order).  pool_hi / pool_lo: the planes of max_pool2d(h, 2, 2) as (n, H / 2, W / 2, C) rows,
+ *     floor semantics (an odd last row / column is dropped).  Either proj or the plane pair may be NULL, not both.
+ *   fresco_hed_fuse     : side maps s1 .. s5, level k of shape (n, H >> (k - 1), W >> (k - 1)) fp32 -> for every level
+ *     cv2.resize(INTER_LINEAR) to (H, W) [source position ((d + 0.5) (src / dst) - 0.5), the scale in double, positions
+ *     clamped to the first / last sample, horizontal pass then vertical, fp32, identity at level 1], the mean in fp32
+ *     (adds in level order, / 5), 1 / (1 + exp(-mean)) in double, * 255, clip, truncation: out (n, H, W) uint8.
+ *     logit (n, H, W) fp32 (optional): the mean.  cond (n, 3, H, W) of cond_dtype (optional): ((u / 255) 2 - 1) 0.5 + 0.5
+ *     in fp32, rounded once, the same in the three channels -- the ControlNet condition run_fresco.py:199-200 builds.
+ * FRESCO_EUNSUPPORTED: C outside the list, H or W < 16 (fuse; < 2 for a pooled output), n H W >= 2^31.  FRESCO_EINVAL: null
+ * pointers, non-positive sizes or scale, an unknown cond_dtype, h / w / the planes not 16-byte aligned (they are read and
+ * written in 16-byte pieces).  All before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int fresco_hed_input(const uint8_t* frames, const float* norm, void* out_hi, void* out_lo, int n, int H, int W,
+                     float split_scale, int32_t* range_flag, void* stream);
+int fresco_hed_side_pool(const float* h, const float* w, const float* bias /* may be NULL */, float* proj /* may be NULL */,
+                         void* pool_hi /* may be NULL */, void* pool_lo, int n, int H, int W, int C, float split_scale,
+                         int32_t* range_flag, void* stream);
+int fresco_hed_fuse(const float* s1, const float* s2, const float* s3, const float* s4, const float* s5, uint8_t* out,
+                    float* logit /* may be NULL */, void* cond /* may be NULL */, int cond_dtype, int n, int H, int W,
+                    void* stream);
 
 #ifdef __cplusplus
 }
