@@ -19,6 +19,9 @@ ERRORS = {
     -4: "FRESCO_ELAUNCH (HIP launch failed)",
 }
 F16, F32, BF16 = 0, 1, 2
+# what fresco_version() of the library these SIGNATURES describe reports: an older build exports the same names with other
+# argument lists
+VERSION = "0.5.0"
 
 
 class FrescoHipError(RuntimeError):
@@ -36,38 +39,23 @@ SIGNATURES = {
     "fresco_prof_disable": (_i, []),
     "fresco_prof_read": (_i, [_i, _vp, _vp, _vp]),
     "fresco_attn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "fresco_attn_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i64, _f, _f, _vp]),
-    "fresco_attn_fwd_ld": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i64, _f, _f, _i64, _i64, _vp]),
-    "fresco_attn_fwd_dt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i64, _f, _f, _i64, _i64, _i, _vp]),
+    "fresco_attn_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i64, _f, _f, _i64, _i64, _i, _vp]),
     "fresco_attn_kvproj_supported": (_i, [_i, _i, _i]),
-    "fresco_attn_fwd_kvproj": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _f, _i64, _vp]),
-    "fresco_attn_fwd_kvproj_dt": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _f, _i64, _i,
-                                       _vp]),
-    "fresco_temporal_attn_ld": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i64, _i64, _i64, _vp]),
-    "fresco_temporal_attn_dt": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i64, _i64, _i64, _i, _vp]),
-    "fresco_temporal_attn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "fresco_attn_fwd_kvproj": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _f, _i64, _i,
+                                    _vp]),
+    "fresco_temporal_attn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i64, _i64, _i64, _i, _vp]),
     "fresco_temporal_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _vp]),
-    "fresco_temporal_attn_packed": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
-    "fresco_temporal_attn_packed_dt": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "fresco_temporal_attn_packed": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp]),
     "fresco_temporal_unpack": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "fresco_flow_warp": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fresco_resize_bilinear": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp]),
     "fresco_max_pool": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "fresco_dilate": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "fresco_linear": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i,
-                           _vp]),
-    "fresco_linear_rows": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i,
-                                _i, _vp]),
-    "fresco_linear_dt": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i,
-                              _i, _vp]),
-    "fresco_linear_rows_dt": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i,
-                                   _i, _i, _i, _vp]),
+    "fresco_linear": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i,
+                           _i, _i, _i, _vp]),
     "fresco_linear_plan": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
-    "fresco_attn_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
     "fresco_attn_f32_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "fresco_attn_f32_ws": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _f, _vp]),
-    "fresco_attn_f32_guarded": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _f, _vp]),
-    "fresco_attn_f32_guarded_ws": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "fresco_attn_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "fresco_fn_gemm": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64] + [_i] * 4 + [_f, _f] + [_i] * 7 + [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp]),
     "fresco_fn_colstats_finish": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp]),
     "fresco_fn_colstats_workspace_bytes": (_sz, [_i, _i, _i]),
@@ -81,19 +69,18 @@ SIGNATURES = {
     "fresco_adain": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _i, _vp]),
     "fresco_chan_mean_std": (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _vp]),
     "fresco_opt_workspace_bytes": (_sz, [_i] * 7),
-    "fresco_opt_run": (_i, [_vp] * 7 + [_sz, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _vp]),
     "fresco_ctx_create": (_i, [_vp]),
     "fresco_ctx_destroy": (_i, [_vp]),
-    "fresco_opt_run_ctx": (_i, [_vp] * 8 + [_sz, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _vp]),
+    "fresco_opt_run": (_i, [_vp] * 8 + [_sz, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _vp]),
     "fresco_opt_loss_grad": (_i, [_vp] * 9 + [_sz, _i, _i, _i, _i, _i, _f, _vp]),
     "fresco_opt_sharded_workspace_bytes": (_sz, [_i] * 7),
     "fresco_opt_sharded_begin": (_i, [_vp] * 5 + [_sz, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "fresco_opt_sharded_step": (_i, [_vp] * 9 + [_sz, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _vp]),
-    "fresco_opt_sharded_step_part": (_i, [_vp] * 9 + [_sz, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _i, _vp]),
+    "fresco_opt_sharded_step": (_i, [_vp] * 9 + [_sz, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _f, _i, _vp]),
     "fresco_mapping_workspace_bytes": (_sz, [_i, _i, _i]),
     "fresco_mapping_ind": (_i, [_vp] * 7 + [_sz, _i, _i, _i, _f, _vp]),
     "fresco_ddpm_x0": (_i, [_vp] * 5 + [_i64, _f, _f, _f, _i, _vp]),
     "fresco_ddpm_prev": (_i, [_vp] * 4 + [_i64, _i64, _f, _f, _f, _i, _vp]),
+    "fresco_gram_target_workspace_bytes": (_sz, [_i, _i, _i]),
     "fresco_gram_target": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "fresco_ebsynth_max_levels": (_i, [_i] * 5),
     "fresco_ebsynth_workspace_bytes": (_sz, [_i] * 9),
@@ -146,6 +133,10 @@ def load():
             raise FrescoHipError("fresco_amd: %s does not export %s (stale build?)" % (LIB_PATH, name))
         fn.restype = res
         fn.argtypes = args
+    built = lib.fresco_version().decode().split()
+    if built[1:2] != [VERSION]:
+        raise FrescoHipError("fresco_amd: %s is version %s, this package binds %s (stale build?)"
+                             % (LIB_PATH, " ".join(built[1:2]) or "?", VERSION))
     _lib = lib
     return lib
 

@@ -152,7 +152,7 @@ FRESCO_KV_PACK_KERNEL(kv_pack_bf16_kernel, bf16_t)
 
 // ---------------------------------------------------------------------------------------------
 // kvproj_pack: the K | V projection of the SELECTED rows and the pack in ONE launch, for layer calls whose K and V are
-// read through the cross-frame pass's key image (V by nothing else).  The two-launch form is fresco_linear_rows (K | V of
+// read through the cross-frame pass's key image (V by nothing else).  The two-launch form is fresco_linear with x_rows (K | V of
 // the 2 x M gathered hidden rows -> HBM) then kv_pack_kernel (gather again, transpose, pad -> image), two latency-bound
 // launches in front of the flash kernel.  K and V never exist in HBM here.
 //
@@ -1376,40 +1376,10 @@ extern "C" size_t fresco_attn_workspace_bytes(int n_groups, int H, int M, int D)
     return attn_ws_bytes(n_groups, H, M, D);
 }
 
-namespace fresco {
-template <typename T>
-static int attn_launch_t(const void* q, const void* k, const void* v, const int32_t* kv_rows, void* out, void* workspace,
-                         int B, int H, int Lq, int D, int n_groups, int M, int64_t group_rows, float scale,
-                         float diag_bias, int64_t q_ld, int64_t kv_ld, hipStream_t st) {
-    const T* qh = static_cast<const T*>(q);
-    const T* kh = static_cast<const T*>(k);
-    const T* vh = static_cast<const T*>(v);
-    T* oh = static_cast<T*>(out);
-    char* ws = static_cast<char*>(workspace);
-#define FRESCO_ATTN_CASE(DD)                                                                       \
-    case DD:                                                                                       \
-        return launch_attn<T, DD>(qh, kh, vh, kv_rows, oh, ws, B, H, Lq, n_groups, M, group_rows, scale, \
-                                  diag_bias, q_ld, kv_ld, st);
-    switch (D) {
-        FRESCO_ATTN_CASE(8)
-        FRESCO_ATTN_CASE(16)
-        FRESCO_ATTN_CASE(32)
-        FRESCO_ATTN_CASE(40)
-        FRESCO_ATTN_CASE(64)
-        FRESCO_ATTN_CASE(80)
-        FRESCO_ATTN_CASE(96)
-        FRESCO_ATTN_CASE(128)
-        default:
-            return FRESCO_EUNSUPPORTED;
-    }
-#undef FRESCO_ATTN_CASE
-}
-}  // namespace fresco
-
-extern "C" int fresco_attn_fwd_dt(const void* q, const void* k, const void* v, const int32_t* kv_rows,
-                                  void* out, void* workspace, size_t workspace_bytes, int B, int H,
-                                  int Lq, int D, int n_groups, int M, int64_t group_rows, float scale,
-                                  float diag_bias, int64_t q_ld, int64_t kv_ld, int dtype, void* stream) {
+extern "C" int fresco_attn_fwd(const void* q, const void* k, const void* v, const int32_t* kv_rows,
+                               void* out, void* workspace, size_t workspace_bytes, int B, int H,
+                               int Lq, int D, int n_groups, int M, int64_t group_rows, float scale,
+                               float diag_bias, int64_t q_ld, int64_t kv_ld, int dtype, void* stream) {
     if (dtype != FRESCO_F16 && dtype != FRESCO_BF16) return FRESCO_EINVAL;
     if (!q || !k || !v || !out || !workspace) return FRESCO_EINVAL;
     if (q_ld < (int64_t)H * D || kv_ld < (int64_t)H * D || q_ld % 8 != 0 || kv_ld % 8 != 0) return FRESCO_EINVAL;
@@ -1418,19 +1388,31 @@ extern "C" int fresco_attn_fwd_dt(const void* q, const void* k, const void* v, c
     if (B % n_groups != 0 || !(scale > 0.f)) return FRESCO_EINVAL;
     if (workspace_bytes < attn_ws_bytes(n_groups, H, M, D)) return FRESCO_EWORKSPACE;
     hipStream_t st = as_stream(stream);
-    if (dtype == FRESCO_BF16)
-        return attn_launch_t<bf16_t>(q, k, v, kv_rows, out, workspace, B, H, Lq, D, n_groups, M, group_rows, scale,
-                                     diag_bias, q_ld, kv_ld, st);
-    return attn_launch_t<half_t>(q, k, v, kv_rows, out, workspace, B, H, Lq, D, n_groups, M, group_rows, scale, diag_bias,
-                                 q_ld, kv_ld, st);
-}
-
-extern "C" int fresco_attn_fwd_ld(const void* q, const void* k, const void* v, const int32_t* kv_rows,
-                                  void* out, void* workspace, size_t workspace_bytes, int B, int H,
-                                  int Lq, int D, int n_groups, int M, int64_t group_rows, float scale,
-                                  float diag_bias, int64_t q_ld, int64_t kv_ld, void* stream) {
-    return fresco_attn_fwd_dt(q, k, v, kv_rows, out, workspace, workspace_bytes, B, H, Lq, D, n_groups, M, group_rows,
-                              scale, diag_bias, q_ld, kv_ld, FRESCO_F16, stream);
+    char* ws = static_cast<char*>(workspace);
+    return with_elem(dtype, [&](auto e) {
+        using T = decltype(e);
+        const T* qh = static_cast<const T*>(q);
+        const T* kh = static_cast<const T*>(k);
+        const T* vh = static_cast<const T*>(v);
+        T* oh = static_cast<T*>(out);
+#define FRESCO_ATTN_CASE(DD)                                                                       \
+    case DD:                                                                                       \
+        return launch_attn<T, DD>(qh, kh, vh, kv_rows, oh, ws, B, H, Lq, n_groups, M, group_rows, scale, \
+                                  diag_bias, q_ld, kv_ld, st);
+        switch (D) {
+            FRESCO_ATTN_CASE(8)
+            FRESCO_ATTN_CASE(16)
+            FRESCO_ATTN_CASE(32)
+            FRESCO_ATTN_CASE(40)
+            FRESCO_ATTN_CASE(64)
+            FRESCO_ATTN_CASE(80)
+            FRESCO_ATTN_CASE(96)
+            FRESCO_ATTN_CASE(128)
+            default:
+                return FRESCO_EUNSUPPORTED;
+        }
+#undef FRESCO_ATTN_CASE
+    });
 }
 
 namespace fresco {
@@ -1453,31 +1435,16 @@ static int launch_kvproj_attn(const T* q, const T* x, int64_t x_ld, const int32_
     }
     return launch_flash_auto<T, D>(q, img, out, B, H, Lq, M, nT, n_groups, scale, 0.f, q_ld, ktmax, st);
 }
-
-template <typename T>
-static int kvproj_launch_t(const void* q, const void* x, int64_t x_ld, const int32_t* x_rows, const void* Wk,
-                           const void* Wv, void* out, void* workspace, int B, int H, int Lq, int D, int n_groups, int M,
-                           float scale, int64_t q_ld, hipStream_t st) {
-    const T* qh = static_cast<const T*>(q);
-    const T* xh = static_cast<const T*>(x);
-    const T* wk = static_cast<const T*>(Wk);
-    const T* wv = static_cast<const T*>(Wv);
-    T* oh = static_cast<T*>(out);
-    char* ws = static_cast<char*>(workspace);
-    if (D == 40)
-        return launch_kvproj_attn<T, 320, 40>(qh, xh, x_ld, x_rows, wk, wv, oh, ws, B, H, Lq, n_groups, M, scale, q_ld, st);
-    return launch_kvproj_attn<T, 640, 80>(qh, xh, x_ld, x_rows, wk, wv, oh, ws, B, H, Lq, n_groups, M, scale, q_ld, st);
-}
 }  // namespace fresco
 
 extern "C" int fresco_attn_kvproj_supported(int H, int D, int K_in) {
     return (H > 0 && (int64_t)H * D == K_in && ((D == 40 && K_in == 320) || (D == 80 && K_in == 640))) ? 1 : 0;
 }
 
-extern "C" int fresco_attn_fwd_kvproj_dt(const void* q, const void* x, int64_t x_ld, const int32_t* x_rows, const void* Wk,
-                                         const void* Wv, void* out, void* workspace, size_t workspace_bytes, int B, int H,
-                                         int Lq, int D, int n_groups, int M, int K_in, float scale, int64_t q_ld, int dtype,
-                                         void* stream) {
+extern "C" int fresco_attn_fwd_kvproj(const void* q, const void* x, int64_t x_ld, const int32_t* x_rows, const void* Wk,
+                                      const void* Wv, void* out, void* workspace, size_t workspace_bytes, int B, int H,
+                                      int Lq, int D, int n_groups, int M, int K_in, float scale, int64_t q_ld, int dtype,
+                                      void* stream) {
     if (dtype != FRESCO_F16 && dtype != FRESCO_BF16) return FRESCO_EINVAL;
     if (!q || !x || !x_rows || !Wk || !Wv || !out || !workspace) return FRESCO_EINVAL;
     if (B <= 0 || H <= 0 || Lq <= 0 || D <= 0 || n_groups <= 0 || M <= 0 || K_in <= 0) return FRESCO_EINVAL;
@@ -1486,23 +1453,16 @@ extern "C" int fresco_attn_fwd_kvproj_dt(const void* q, const void* x, int64_t x
     if (!fresco_attn_kvproj_supported(H, D, K_in)) return FRESCO_EUNSUPPORTED;
     if (workspace_bytes < attn_ws_bytes(n_groups, H, M, D)) return FRESCO_EWORKSPACE;
     hipStream_t st = as_stream(stream);
-    if (dtype == FRESCO_BF16)
-        return kvproj_launch_t<bf16_t>(q, x, x_ld, x_rows, Wk, Wv, out, workspace, B, H, Lq, D, n_groups, M, scale, q_ld, st);
-    return kvproj_launch_t<half_t>(q, x, x_ld, x_rows, Wk, Wv, out, workspace, B, H, Lq, D, n_groups, M, scale, q_ld, st);
-}
-
-extern "C" int fresco_attn_fwd_kvproj(const void* q, const void* x, int64_t x_ld, const int32_t* x_rows, const void* Wk,
-                                      const void* Wv, void* out, void* workspace, size_t workspace_bytes, int B, int H,
-                                      int Lq, int D, int n_groups, int M, int K_in, float scale, int64_t q_ld,
-                                      void* stream) {
-    return fresco_attn_fwd_kvproj_dt(q, x, x_ld, x_rows, Wk, Wv, out, workspace, workspace_bytes, B, H, Lq, D, n_groups, M,
-                                     K_in, scale, q_ld, FRESCO_F16, stream);
-}
-
-extern "C" int fresco_attn_fwd(const void* q, const void* k, const void* v, const int32_t* kv_rows,
-                               void* out, void* workspace, size_t workspace_bytes, int B, int H,
-                               int Lq, int D, int n_groups, int M, int64_t group_rows, float scale,
-                               float diag_bias, void* stream) {
-    return fresco_attn_fwd_ld(q, k, v, kv_rows, out, workspace, workspace_bytes, B, H, Lq, D, n_groups, M,
-                              group_rows, scale, diag_bias, (int64_t)H * D, (int64_t)H * D, stream);
+    char* ws = static_cast<char*>(workspace);
+    return with_elem(dtype, [&](auto e) {
+        using T = decltype(e);
+        const T* qh = static_cast<const T*>(q);
+        const T* xh = static_cast<const T*>(x);
+        const T* wk = static_cast<const T*>(Wk);
+        const T* wv = static_cast<const T*>(Wv);
+        T* oh = static_cast<T*>(out);
+        if (D == 40)
+            return launch_kvproj_attn<T, 320, 40>(qh, xh, x_ld, x_rows, wk, wv, oh, ws, B, H, Lq, n_groups, M, scale, q_ld, st);
+        return launch_kvproj_attn<T, 640, 80>(qh, xh, x_ld, x_rows, wk, wv, oh, ws, B, H, Lq, n_groups, M, scale, q_ld, st);
+    });
 }

@@ -15,6 +15,7 @@
 //   * K and V tiles of 32 keys are staged in LDS (rows padded by 4 floats: conflict-free 16-byte reads).
 //
 // q (B, Lq, D), k (B, Lk, D), v (B, Lk, DV), out (B, Lq, DV), all fp32 row-major.  grid (ceil(Lq/128), B).
+#include <type_traits>
 #include "common.h"
 #include "lds_dma.h"
 
@@ -30,7 +31,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__
                                                         const float* __restrict__ v, float* __restrict__ out,
                                                         int Lq, int Lk, int dv_real, float scale_log2,
                                                         const int* __restrict__ only_if) {
-    // guarded launches (fresco_attn_f32_guarded): this exact-fp32 form only runs -- and overwrites the split-fp16 result --
+    // guarded launches (fresco_attn_f32 with a flag): this exact-fp32 form only runs -- and overwrites the split-fp16 result --
     // when the range pass found an operand outside what the fp16 pieces can hold (uniform branch, one scalar load)
     if (only_if && __builtin_amdgcn_readfirstlane(*only_if) == 0) return;
     constexpr int KR = D + 4;    // LDS row strides (floats)
@@ -355,7 +356,7 @@ struct A32Img {
 template <int D, int DV>
 __global__ __launch_bounds__(256) void kv_split_kernel(const float* __restrict__ k, const float* __restrict__ v,
                                                         char* __restrict__ img, int Lk, int dv_real, int* __restrict__ flag) {
-    // flag != NULL (fresco_attn_f32_guarded_ws): the range test of the guarded entry on the values this pass reads anyway --
+    // flag != NULL (fresco_attn_f32, flag_is_zero): the range test of the guarded entry on the values this pass reads anyway --
     // |k|, |v| >= 1000 (or NaN) would overflow the hi piece after the 2^6 pre-scale: OR 1 into the launch's flag word
     using I = A32Img<D, DV>;
     constexpr int KROW = I::KROW, VROW = I::VROW;
@@ -583,7 +584,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void attn_f32p_kernel(con
 
 template <int D, int DV>
 static int launch_attn32p(const float* q, const float* k, const float* v, float* out, char* img, int B, int Lq, int Lk, int dv,
-                          float scale, hipStream_t st, int* flag = nullptr) {
+                          float scale, hipStream_t st, int* flag) {
     ProfScope ps(FRESCO_PROF_ATTN_F32, B, Lq, Lk, D, st);
     const int nT = (Lk + 31) / 32;
     hipLaunchKernelGGL((kv_split_kernel<D, DV>), dim3(nT, B), dim3(256), 0, st, k, v, img, Lk, dv, flag);
@@ -643,138 +644,62 @@ static int launch_attn32_fallback(const float* q, const float* k, const float* v
 
 using namespace fresco;
 
-extern "C" int fresco_attn_f32(const float* q, const float* k, const float* v, float* out, int B, int Lq, int Lk,
-                               int D, int Dv, float scale, void* stream) {
-    if (!q || !k || !v || !out || B <= 0 || Lq <= 0 || Lk <= 0 || D <= 0 || Dv <= 0 || !(scale > 0.f))
-        return FRESCO_EINVAL;
-    if (B > 65535) return FRESCO_EUNSUPPORTED;
-    hipStream_t st = as_stream(stream);
-#define FRESCO_A32(DD)                                                                           \
-    if (D == DD) {                                                                               \
-        if (Dv <= 32) return launch_attn32<DD, 32>(q, k, v, out, B, Lq, Lk, Dv, scale, st);      \
-        if (Dv <= 64) return launch_attn32<DD, 64>(q, k, v, out, B, Lq, Lk, Dv, scale, st);      \
-        if (Dv <= 128) return launch_attn32<DD, 128>(q, k, v, out, B, Lq, Lk, Dv, scale, st);    \
-        return FRESCO_EUNSUPPORTED;                                                              \
-    }
-    FRESCO_A32(32)
-    FRESCO_A32(64)
-    FRESCO_A32(128)
-#undef FRESCO_A32
-    return FRESCO_EUNSUPPORTED;
-}
-
-// ---- the same with a caller-provided workspace: K / V are split once per launch (kv_split_kernel + attn_f32p_kernel) ----
-template <int D, int DV>
-static size_t a32_ws_bytes(int B, int Lk) {
-    return (size_t)B * ((Lk + 31) / 32) * A32Img<D, DV>::TILE;
+// Calls f(integral_constant<int, D>, integral_constant<int, DV>) for the instantiation that serves (D, Dv): D in {32, 64, 128},
+// DV = Dv rounded up to 32 / 64 / 128.  `none` for every other shape.
+template <typename R, typename F>
+static R a32_dispatch(int D, int Dv, R none, F&& f) {
+    auto with_dv = [&](auto d) -> R {
+        if (Dv <= 0) return none;
+        if (Dv <= 32) return f(d, std::integral_constant<int, 32>{});
+        if (Dv <= 64) return f(d, std::integral_constant<int, 64>{});
+        if (Dv <= 128) return f(d, std::integral_constant<int, 128>{});
+        return none;
+    };
+    if (D == 32) return with_dv(std::integral_constant<int, 32>{});
+    if (D == 64) return with_dv(std::integral_constant<int, 64>{});
+    if (D == 128) return with_dv(std::integral_constant<int, 128>{});
+    return none;
 }
 
 extern "C" size_t fresco_attn_f32_workspace_bytes(int B, int Lk, int D, int Dv) {
-    if (B <= 0 || Lk <= 0 || Dv <= 0 || Dv > 128) return 0;
-#define FRESCO_A32W(DD)                                                  \
-    if (D == DD) {                                                       \
-        if (Dv <= 32) return a32_ws_bytes<DD, 32>(B, Lk);                \
-        if (Dv <= 64) return a32_ws_bytes<DD, 64>(B, Lk);                \
-        return a32_ws_bytes<DD, 128>(B, Lk);                             \
-    }
-    FRESCO_A32W(32)
-    FRESCO_A32W(64)
-    FRESCO_A32W(128)
-#undef FRESCO_A32W
-    return 0;
+    if (B <= 0 || Lk <= 0) return 0;
+    return a32_dispatch(D, Dv, (size_t)0, [&](auto d, auto dv) {
+        return (size_t)B * ((Lk + 31) / 32) * A32Img<decltype(d)::value, decltype(dv)::value>::TILE;
+    });
 }
 
-extern "C" int fresco_attn_f32_ws(const float* q, const float* k, const float* v, float* out, void* workspace,
-                                  size_t workspace_bytes, int B, int Lq, int Lk, int D, int Dv, float scale, void* stream) {
-    if (!q || !k || !v || !out || !workspace || B <= 0 || Lq <= 0 || Lk <= 0 || D <= 0 || Dv <= 0 || !(scale > 0.f))
-        return FRESCO_EINVAL;
+// workspace: K / V are split into their fp16 LDS images once per launch (kv_split_kernel + attn_f32p_kernel); without one,
+// every 128-query workgroup stages and splits its own (attn_f32s_kernel).
+// flag (no range limit on the operands): the exact-fp32 MFMA kernel runs behind the split-fp16 ones and returns
+// at once unless the flag was raised.  What raises it: with flag_is_zero == 0, a memset + one range pass over q, k, v in
+// front; with flag_is_zero != 0, the k / v test inside the split pass (which reads them anyway) and the q test in the
+// attention kernel's Q prologue -- no short launches around the flow network's attention calls.
+extern "C" int fresco_attn_f32(const float* q, const float* k, const float* v, float* out, void* workspace,
+                               size_t workspace_bytes, int* flag, int flag_is_zero, int B, int Lq, int Lk, int D, int Dv,
+                               float scale, void* stream) {
+    if (!q || !k || !v || !out || B <= 0 || Lq <= 0 || Lk <= 0 || D <= 0 || Dv <= 0 || !(scale > 0.f)) return FRESCO_EINVAL;
+    if (flag_is_zero && (!flag || !workspace)) return FRESCO_EINVAL;  // only the workspace kernels carry the in-kernel test
     if (B > 65535) return FRESCO_EUNSUPPORTED;
     const size_t need = fresco_attn_f32_workspace_bytes(B, Lk, D, Dv);
     if (need == 0) return FRESCO_EUNSUPPORTED;
-    if (workspace_bytes < need) return FRESCO_EWORKSPACE;
+    if (workspace && workspace_bytes < need) return FRESCO_EWORKSPACE;
     hipStream_t st = as_stream(stream);
-    char* img = static_cast<char*>(workspace);
-#define FRESCO_A32P(DD)                                                                                  \
-    if (D == DD) {                                                                                       \
-        if (Dv <= 32) return launch_attn32p<DD, 32>(q, k, v, out, img, B, Lq, Lk, Dv, scale, st);        \
-        if (Dv <= 64) return launch_attn32p<DD, 64>(q, k, v, out, img, B, Lq, Lk, Dv, scale, st);        \
-        return launch_attn32p<DD, 128>(q, k, v, out, img, B, Lq, Lk, Dv, scale, st);                     \
+    if (flag && !flag_is_zero) {
+        if (hipMemsetAsync(flag, 0, sizeof(int), st) != hipSuccess) return FRESCO_ELAUNCH;
+        const int64_t nq = (int64_t)B * Lq * D, nk = (int64_t)B * Lk * D, nv = (int64_t)B * Lk * Dv;
+        const int64_t nmax = nq > nk ? (nq > nv ? nq : nv) : (nk > nv ? nk : nv);
+        int blocks = (int)((nmax + 256 * 8 - 1) / (256 * 8));
+        blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+        const float lim = 1000.f;
+        hipLaunchKernelGGL(a32_range_kernel, dim3(blocks), dim3(256), 0, st, q, k, v, nq, nk, nv,
+                           lim / (scale * 1.4426950408889634f), lim, flag);
     }
-    FRESCO_A32P(32)
-    FRESCO_A32P(64)
-    FRESCO_A32P(128)
-#undef FRESCO_A32P
-    return FRESCO_EUNSUPPORTED;
-}
-
-// ---- guarded form: no range limit on the operands.  `flag` = one int32 of device memory owned by the caller
-// for the duration of the call.  Range pass -> split-fp16 kernels (with the workspace when one is given, else the
-// per-workgroup staging form) -> the exact-fp32 MFMA kernel, which returns at once unless the range pass raised the flag.
-// In range (every call of the flow network): the results of fresco_attn_f32 / _ws bit for bit, + ~2 short launches. ----
-extern "C" int fresco_attn_f32_guarded(const float* q, const float* k, const float* v, float* out, void* workspace,
-                                       size_t workspace_bytes, int* flag, int B, int Lq, int Lk, int D, int Dv, float scale,
-                                       void* stream) {
-    if (!flag) return FRESCO_EINVAL;
-    if (!q || !k || !v || !out || B <= 0 || Lq <= 0 || Lk <= 0 || D <= 0 || Dv <= 0 || !(scale > 0.f)) return FRESCO_EINVAL;
-    hipStream_t st = as_stream(stream);
-    if (hipMemsetAsync(flag, 0, sizeof(int), st) != hipSuccess) return FRESCO_ELAUNCH;
-    const int64_t nq = (int64_t)B * Lq * D, nk = (int64_t)B * Lk * D, nv = (int64_t)B * Lk * Dv;
-    const int64_t nmax = nq > nk ? (nq > nv ? nq : nv) : (nk > nv ? nk : nv);
-    int blocks = (int)((nmax + 256 * 8 - 1) / (256 * 8));
-    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
-    const float lim = 1000.f;
-    hipLaunchKernelGGL(a32_range_kernel, dim3(blocks), dim3(256), 0, st, q, k, v, nq, nk, nv,
-                       lim / (scale * 1.4426950408889634f), lim, flag);
-    int rc = workspace ? fresco_attn_f32_ws(q, k, v, out, workspace, workspace_bytes, B, Lq, Lk, D, Dv, scale, stream)
-                       : fresco_attn_f32(q, k, v, out, B, Lq, Lk, D, Dv, scale, stream);
-    if (rc != FRESCO_OK) return rc;
-#define FRESCO_A32G(DD)                                                                                     \
-    if (D == DD) {                                                                                          \
-        if (Dv <= 32) return launch_attn32_fallback<DD, 32>(q, k, v, out, B, Lq, Lk, Dv, scale, flag, st);  \
-        if (Dv <= 64) return launch_attn32_fallback<DD, 64>(q, k, v, out, B, Lq, Lk, Dv, scale, flag, st);  \
-        return launch_attn32_fallback<DD, 128>(q, k, v, out, B, Lq, Lk, Dv, scale, flag, st);               \
-    }
-    FRESCO_A32G(32)
-    FRESCO_A32G(64)
-    FRESCO_A32G(128)
-#undef FRESCO_A32G
-    return FRESCO_EUNSUPPORTED;
-}
-
-// ---- guarded workspace form WITHOUT the range pass and the flag memset (round 6: 20 us of short launches around every one of
-// the flow network's 26 attention calls).  `zero_flag` = one int32 of device memory that the CALLER guarantees to be zero in
-// stream order when the call is issued and that nobody else touches until the call's kernels are done (fresco_amd.ops hands out
-// the words of a zero-filled pool, each once).  The k / v range test runs inside the split pass (which reads them anyway), the
-// q test in the attention kernel's Q prologue; the exact-fp32 kernel behind them returns at once unless one of them raised
-// the flag.  Same results as fresco_attn_f32_guarded with a workspace, bit for bit, in range and out of range.
-extern "C" int fresco_attn_f32_guarded_ws(const float* q, const float* k, const float* v, float* out, void* workspace,
-                                          size_t workspace_bytes, int* zero_flag, int B, int Lq, int Lk, int D, int Dv,
-                                          float scale, void* stream) {
-    if (!zero_flag || !workspace) return FRESCO_EINVAL;
-    if (!q || !k || !v || !out || B <= 0 || Lq <= 0 || Lk <= 0 || D <= 0 || Dv <= 0 || !(scale > 0.f)) return FRESCO_EINVAL;
-    if (B > 65535) return FRESCO_EUNSUPPORTED;
-    const size_t need = fresco_attn_f32_workspace_bytes(B, Lk, D, Dv);
-    if (need == 0) return FRESCO_EUNSUPPORTED;
-    if (workspace_bytes < need) return FRESCO_EWORKSPACE;
-    hipStream_t st = as_stream(stream);
-    char* img = static_cast<char*>(workspace);
-#define FRESCO_A32GW(DD)                                                                                                  \
-    if (D == DD) {                                                                                                        \
-        int rc;                                                                                                           \
-        if (Dv <= 32) {                                                                                                   \
-            rc = launch_attn32p<DD, 32>(q, k, v, out, img, B, Lq, Lk, Dv, scale, st, zero_flag);                          \
-            return rc != FRESCO_OK ? rc : launch_attn32_fallback<DD, 32>(q, k, v, out, B, Lq, Lk, Dv, scale, zero_flag, st);   \
-        }                                                                                                                 \
-        if (Dv <= 64) {                                                                                                   \
-            rc = launch_attn32p<DD, 64>(q, k, v, out, img, B, Lq, Lk, Dv, scale, st, zero_flag);                          \
-            return rc != FRESCO_OK ? rc : launch_attn32_fallback<DD, 64>(q, k, v, out, B, Lq, Lk, Dv, scale, zero_flag, st);   \
-        }                                                                                                                 \
-        rc = launch_attn32p<DD, 128>(q, k, v, out, img, B, Lq, Lk, Dv, scale, st, zero_flag);                             \
-        return rc != FRESCO_OK ? rc : launch_attn32_fallback<DD, 128>(q, k, v, out, B, Lq, Lk, Dv, scale, zero_flag, st);      \
-    }
-    FRESCO_A32GW(32)
-    FRESCO_A32GW(64)
-    FRESCO_A32GW(128)
-#undef FRESCO_A32GW
-    return FRESCO_EUNSUPPORTED;
+    return a32_dispatch(D, Dv, FRESCO_EUNSUPPORTED, [&](auto d, auto dv) {
+        constexpr int DD = decltype(d)::value, DV = decltype(dv)::value;
+        int rc = workspace ? launch_attn32p<DD, DV>(q, k, v, out, static_cast<char*>(workspace), B, Lq, Lk, Dv, scale, st,
+                                                    flag_is_zero ? flag : nullptr)
+                           : launch_attn32<DD, DV>(q, k, v, out, B, Lq, Lk, Dv, scale, st);
+        if (rc != FRESCO_OK || !flag) return rc;
+        return launch_attn32_fallback<DD, DV>(q, k, v, out, B, Lq, Lk, Dv, scale, flag, st);
+    });
 }

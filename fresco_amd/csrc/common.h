@@ -103,6 +103,14 @@ struct Elem<bf16_t> {
     static __device__ __forceinline__ scalar from_float(float f) { return (scalar)f; }  // v_cvt_pk_bf16_f32
 };
 
+// Calls f with a value of the element type that `dtype` names, f(half_t{}) or f(bf16_t{}); any other code: FRESCO_EINVAL.
+template <typename F>
+static inline int with_elem(int dtype, F&& f) {
+    if (dtype == FRESCO_F16) return f(half_t{});
+    if (dtype == FRESCO_BF16) return f(bf16_t{});
+    return FRESCO_EINVAL;
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -1162,15 +1162,6 @@ static int opt_run_impl(SideStream* ctx, float* cs, const float* fwd_flow, const
     return check_launch();
 }
 
-extern "C" int fresco_opt_run(float* cs, const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
-                              const float* bwd_occ, const float* target, void* workspace,
-                              size_t workspace_bytes, int chunk, int N, int C, int h, int w,
-                              float intra_weight, int iters, float lr, float beta1, float beta2, float eps,
-                              void* stream) {
-    return opt_run_impl(nullptr, cs, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, workspace, workspace_bytes, chunk, N, C, h,
-                        w, intra_weight, iters, lr, beta1, beta2, eps, stream);
-}
-
 extern "C" int fresco_ctx_create(void** ctx) {
     if (!ctx) return FRESCO_EINVAL;
     *ctx = new (std::nothrow) SideStream();
@@ -1193,10 +1184,10 @@ extern "C" int fresco_ctx_destroy(void* ctx) {
     return FRESCO_OK;
 }
 
-extern "C" int fresco_opt_run_ctx(void* ctx, float* cs, const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
-                                  const float* bwd_occ, const float* target, void* workspace, size_t workspace_bytes,
-                                  int chunk, int N, int C, int h, int w, float intra_weight, int iters, float lr,
-                                  float beta1, float beta2, float eps, void* stream) {
+extern "C" int fresco_opt_run(void* ctx, float* cs, const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
+                              const float* bwd_occ, const float* target, void* workspace, size_t workspace_bytes,
+                              int chunk, int N, int C, int h, int w, float intra_weight, int iters, float lr,
+                              float beta1, float beta2, float eps, void* stream) {
     return opt_run_impl(static_cast<SideStream*>(ctx), cs, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, workspace,
                         workspace_bytes, chunk, N, C, h, w, intra_weight, iters, lr, beta1, beta2, eps, stream);
 }
@@ -1265,12 +1256,12 @@ extern "C" int fresco_opt_sharded_begin(const float* fwd_flow, const float* bwd_
     return check_launch();
 }
 
-extern "C" int fresco_opt_sharded_step_part(float* cs, const float* halo_l, const float* halo_r,
-                                            const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
-                                            const float* bwd_occ, const float* target, void* workspace,
-                                            size_t workspace_bytes, int chunk, int n_loc, int N_total, int C, int h,
-                                            int w, float intra_weight, int it, float lr, float beta1, float beta2,
-                                            float eps, int part, void* stream) {
+extern "C" int fresco_opt_sharded_step(float* cs, const float* halo_l, const float* halo_r,
+                                       const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
+                                       const float* bwd_occ, const float* target, void* workspace,
+                                       size_t workspace_bytes, int chunk, int n_loc, int N_total, int C, int h,
+                                       int w, float intra_weight, int it, float lr, float beta1, float beta2,
+                                       float eps, int part, void* stream) {
     if (!cs || !workspace || chunk <= 0 || n_loc <= 0 || N_total < n_loc || C <= 0 || h <= 1 || w <= 1 || it < 1)
         return FRESCO_EINVAL;
     if (part < 1 || part > 3) return FRESCO_EINVAL;
@@ -1299,15 +1290,9 @@ extern "C" int fresco_opt_sharded_step_part(float* cs, const float* halo_l, cons
     return check_launch();
 }
 
-extern "C" int fresco_opt_sharded_step(float* cs, const float* halo_l, const float* halo_r,
-                                       const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
-                                       const float* bwd_occ, const float* target, void* workspace,
-                                       size_t workspace_bytes, int chunk, int n_loc, int N_total, int C, int h,
-                                       int w, float intra_weight, int it, float lr, float beta1, float beta2,
-                                       float eps, void* stream) {
-    return fresco_opt_sharded_step_part(cs, halo_l, halo_r, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, workspace,
-                                        workspace_bytes, chunk, n_loc, N_total, C, h, w, intra_weight, it, lr, beta1, beta2,
-                                        eps, 3, stream);
+extern "C" size_t fresco_gram_target_workspace_bytes(int B, int C, int hw) {
+    if (B <= 0 || C <= 0 || hw <= 0) return 0;
+    return align_up((size_t)B * C * hw * 4, 256) + align_up((size_t)B * hw * 4, 256) * 33;
 }
 
 extern "C" int fresco_gram_target(const float* x, float* target, void* workspace, size_t workspace_bytes,
@@ -1315,7 +1300,7 @@ extern "C" int fresco_gram_target(const float* x, float* target, void* workspace
     if (!x || !target || !workspace || B <= 0 || C <= 0 || hw <= 0) return FRESCO_EINVAL;
     if (B > 65535) return FRESCO_EUNSUPPORTED;
     const size_t E = (size_t)B * C * hw;
-    if (workspace_bytes < align_up(E * 4, 256) + align_up((size_t)B * hw * 4, 256) * 33) return FRESCO_EWORKSPACE;
+    if (workspace_bytes < fresco_gram_target_workspace_bytes(B, C, hw)) return FRESCO_EWORKSPACE;
     char* p = static_cast<char*>(workspace);
     float* vt = carve<float>(p, E);
     float* nrm = carve<float>(p, (size_t)B * hw);

@@ -105,7 +105,7 @@ struct PrepArgs {
     // frame-sharded form only: 0 = everything; 1 = the part that needs no halo frame (normalisation + copies of every
     // local frame, signs of the interior pairs); 2 = the signs of the two pairs that touch a halo frame, nothing else.
     // 1 followed by 2 performs, per element, exactly the operations of 0 (results identical bit for bit): the split only
-    // lets the neighbour exchange of the halo frames run under the Gram / S V launches (fresco_opt_sharded_step_part)
+    // lets the neighbour exchange of the halo frames run under the Gram / S V launches (fresco_opt_sharded_step, part 1 / part 2)
     int phase;
 };
 

@@ -368,39 +368,6 @@ static int launch_linear(const T* x, int64_t x_ld, const int32_t* x_rows, const 
 
 using namespace fresco;
 
-template <typename T>
-static int linear_launch_t(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1, const void* W2,
-                           const void* b0, const void* b1, const void* b2, void* out0, void* out1, void* out2, int64_t ld0,
-                           int64_t ld1, int64_t ld2, int nw, int M, int N, int K, const LinearPlan& p,
-                           hipStream_t st) {
-    const T* xh = static_cast<const T*>(x);
-    const T* wh[3] = {static_cast<const T*>(W0), static_cast<const T*>(W1), static_cast<const T*>(W2)};
-    const T* bh[3] = {static_cast<const T*>(b0), static_cast<const T*>(b1), static_cast<const T*>(b2)};
-    T* o0 = static_cast<T*>(out0);
-    T* o1 = static_cast<T*>(out1);
-    T* o2 = static_cast<T*>(out2);
-    if (K == 320) return launch_linear<T, 320, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, p, st);
-    return launch_linear<T, 640, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, p, st);
-}
-
-static int linear_dispatch(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1,
-                           const void* W2, const void* b0, const void* b1, const void* b2, void* out0, void* out1,
-                           void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, int dtype,
-                           void* stream) {
-    if (dtype != FRESCO_F16 && dtype != FRESCO_BF16) return FRESCO_EINVAL;
-    if (!x || !W0 || !out0) return FRESCO_EINVAL;  // (nw and the sizes: plan_linear, below)
-    if ((nw > 1 && (!out1 || !W1)) || (nw > 2 && (!out2 || !W2))) return FRESCO_EINVAL;
-    if (x_ld < K || x_ld % 8 != 0) return FRESCO_EINVAL;
-    if (ld0 < N || ld0 % 8 != 0 || (nw > 1 && (ld1 < N || ld1 % 8 != 0)) || (nw > 2 && (ld2 < N || ld2 % 8 != 0)))
-        return FRESCO_EINVAL;
-    LinearPlan plan;
-    if (int rc = plan_linear(nw, M, N, K, &plan)) return rc;
-    hipStream_t st = as_stream(stream);
-    if (dtype == FRESCO_BF16)
-        return linear_launch_t<bf16_t>(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, plan, st);
-    return linear_launch_t<half_t>(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, plan, st);
-}
-
 extern "C" int fresco_linear_plan(int nw, int M, int N, int K, int* row_blocks, int* splits, int* tiles_per_split) {
     LinearPlan plan;
     if (int rc = plan_linear(nw, M, N, K, &plan)) return rc;
@@ -410,34 +377,28 @@ extern "C" int fresco_linear_plan(int nw, int M, int N, int K, int* row_blocks, 
     return FRESCO_OK;
 }
 
-extern "C" int fresco_linear(const void* x, int64_t x_ld, const void* W0, const void* W1, const void* W2,
-                             const void* b0, const void* b1, const void* b2, void* out0, void* out1, void* out2,
-                             int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, void* stream) {
-    return linear_dispatch(x, x_ld, nullptr, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, FRESCO_F16, stream);
-}
-
-extern "C" int fresco_linear_rows(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1,
-                                  const void* W2, const void* b0, const void* b1, const void* b2, void* out0,
-                                  void* out1, void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N,
-                                  int K, void* stream) {
-    if (!x_rows) return FRESCO_EINVAL;
-    return linear_dispatch(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, FRESCO_F16, stream);
-}
-
-extern "C" int fresco_linear_dt(const void* x, int64_t x_ld, const void* W0, const void* W1, const void* W2,
-                                const void* b0, const void* b1, const void* b2, void* out0, void* out1, void* out2,
-                                int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, int dtype,
-                                void* stream) {
-    return linear_dispatch(x, x_ld, nullptr, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, dtype,
-                           stream);
-}
-
-extern "C" int fresco_linear_rows_dt(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1,
-                                     const void* W2, const void* b0, const void* b1, const void* b2, void* out0,
-                                     void* out1, void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M,
-                                     int N, int K, int dtype, void* stream) {
+extern "C" int fresco_linear(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1,
+                             const void* W2, const void* b0, const void* b1, const void* b2, void* out0, void* out1,
+                             void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, int dtype,
+                             void* stream) {
     if (dtype != FRESCO_F16 && dtype != FRESCO_BF16) return FRESCO_EINVAL;
-    if (!x_rows) return FRESCO_EINVAL;
-    return linear_dispatch(x, x_ld, x_rows, W0, W1, W2, b0, b1, b2, out0, out1, out2, ld0, ld1, ld2, nw, M, N, K, dtype,
-                           stream);
+    if (!x || !W0 || !out0) return FRESCO_EINVAL;  // (nw and the sizes: plan_linear, below)
+    if ((nw > 1 && (!out1 || !W1)) || (nw > 2 && (!out2 || !W2))) return FRESCO_EINVAL;
+    if (x_ld < K || x_ld % 8 != 0) return FRESCO_EINVAL;
+    if (ld0 < N || ld0 % 8 != 0 || (nw > 1 && (ld1 < N || ld1 % 8 != 0)) || (nw > 2 && (ld2 < N || ld2 % 8 != 0)))
+        return FRESCO_EINVAL;
+    LinearPlan plan;
+    if (int rc = plan_linear(nw, M, N, K, &plan)) return rc;
+    hipStream_t st = as_stream(stream);
+    return with_elem(dtype, [&](auto e) {
+        using T = decltype(e);
+        const T* xh = static_cast<const T*>(x);
+        const T* wh[3] = {static_cast<const T*>(W0), static_cast<const T*>(W1), static_cast<const T*>(W2)};
+        const T* bh[3] = {static_cast<const T*>(b0), static_cast<const T*>(b1), static_cast<const T*>(b2)};
+        T* o0 = static_cast<T*>(out0);
+        T* o1 = static_cast<T*>(out1);
+        T* o2 = static_cast<T*>(out2);
+        if (K == 320) return launch_linear<T, 320, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, plan, st);
+        return launch_linear<T, 640, 8>(xh, x_ld, x_rows, wh, bh, o0, o1, o2, ld0, ld1, ld2, nw, M, N, plan, st);
+    });
 }

@@ -516,77 +516,52 @@ static int launch_temporal(const T* q, const T* k, const T* v, const int64_t* fw
 
 using namespace fresco;
 
-template <typename T>
-static int temporal_launch_t(const void* q, const void* k, const void* v, const int64_t* fwd_map, const uint8_t* mask,
-                             void* out, int chunk, int N, int HW, int H, int D, float scale, int64_t q_ld, int64_t k_ld,
-                             int64_t v_ld, bool packed, hipStream_t st) {
-    const T* qh = static_cast<const T*>(q);
-    const T* kh = static_cast<const T*>(k);
-    const T* vh = static_cast<const T*>(v);
-    T* oh = static_cast<T*>(out);
-#define FRESCO_T_CASE(DD) \
-    case DD:              \
-        return launch_temporal<T, DD>(qh, kh, vh, fwd_map, mask, oh, chunk, N, HW, H, scale, q_ld, k_ld, v_ld, packed, st);
-    switch (D) {
-        FRESCO_T_CASE(8)
-        FRESCO_T_CASE(16)
-        FRESCO_T_CASE(32)
-        FRESCO_T_CASE(40)
-        FRESCO_T_CASE(64)
-        FRESCO_T_CASE(80)
-        default:
-            return FRESCO_EUNSUPPORTED;
-    }
-#undef FRESCO_T_CASE
-}
-
 static int temporal_dispatch(const void* q, const void* k, const void* v, const int64_t* fwd_map,
                              const uint8_t* mask, void* out, int chunk, int N, int HW, int H, int D, float scale,
-                             int64_t q_ld, int64_t k_ld, int64_t v_ld, bool packed, void* stream,
-                             int dtype = FRESCO_F16) {
+                             int64_t q_ld, int64_t k_ld, int64_t v_ld, bool packed, int dtype, void* stream) {
     if (dtype != FRESCO_F16 && dtype != FRESCO_BF16) return FRESCO_EINVAL;
     if (!q || !k || !v || (!packed && !fwd_map) || !mask || !out) return FRESCO_EINVAL;
     if (chunk <= 0 || N <= 0 || HW <= 0 || H <= 0 || D <= 0) return FRESCO_EINVAL;
     const int64_t Cw = (int64_t)H * D;
     if (q_ld < Cw || k_ld < Cw || v_ld < Cw || q_ld % 8 || k_ld % 8 || v_ld % 8) return FRESCO_EINVAL;
     hipStream_t st = as_stream(stream);
-    if (dtype == FRESCO_BF16)
-        return temporal_launch_t<bf16_t>(q, k, v, fwd_map, mask, out, chunk, N, HW, H, D, scale, q_ld, k_ld, v_ld, packed, st);
-    return temporal_launch_t<half_t>(q, k, v, fwd_map, mask, out, chunk, N, HW, H, D, scale, q_ld, k_ld, v_ld, packed, st);
+    return with_elem(dtype, [&](auto e) {
+        using T = decltype(e);
+        const T* qh = static_cast<const T*>(q);
+        const T* kh = static_cast<const T*>(k);
+        const T* vh = static_cast<const T*>(v);
+        T* oh = static_cast<T*>(out);
+#define FRESCO_T_CASE(DD) \
+    case DD:              \
+        return launch_temporal<T, DD>(qh, kh, vh, fwd_map, mask, oh, chunk, N, HW, H, scale, q_ld, k_ld, v_ld, packed, st);
+        switch (D) {
+            FRESCO_T_CASE(8)
+            FRESCO_T_CASE(16)
+            FRESCO_T_CASE(32)
+            FRESCO_T_CASE(40)
+            FRESCO_T_CASE(64)
+            FRESCO_T_CASE(80)
+            default:
+                return FRESCO_EUNSUPPORTED;
+        }
+#undef FRESCO_T_CASE
+    });
 }
 
 extern "C" int fresco_temporal_attn(const void* q, const void* k, const void* v, const int64_t* fwd_map,
-                                    const uint8_t* mask, void* out, int chunk, int N, int HW, int H,
-                                    int D, float scale, void* stream) {
-    const int64_t Cw = (int64_t)H * D;
-    return temporal_dispatch(q, k, v, fwd_map, mask, out, chunk, N, HW, H, D, scale, Cw, Cw, Cw, false, stream);
+                                    const uint8_t* mask, void* out, int chunk, int N, int HW, int H, int D,
+                                    float scale, int64_t q_ld, int64_t k_ld, int64_t v_ld, int dtype, void* stream) {
+    return temporal_dispatch(q, k, v, fwd_map, mask, out, chunk, N, HW, H, D, scale, q_ld, k_ld, v_ld, false, dtype,
+                             stream);
 }
 
-extern "C" int fresco_temporal_attn_ld(const void* q, const void* k, const void* v, const int64_t* fwd_map,
-                                       const uint8_t* mask, void* out, int chunk, int N, int HW, int H, int D,
-                                       float scale, int64_t q_ld, int64_t k_ld, int64_t v_ld, void* stream) {
-    return temporal_dispatch(q, k, v, fwd_map, mask, out, chunk, N, HW, H, D, scale, q_ld, k_ld, v_ld, false, stream);
-}
-
-extern "C" int fresco_temporal_attn_dt(const void* q, const void* k, const void* v, const int64_t* fwd_map,
-                                       const uint8_t* mask, void* out, int chunk, int N, int HW, int H, int D,
-                                       float scale, int64_t q_ld, int64_t k_ld, int64_t v_ld, int dtype, void* stream) {
-    return temporal_dispatch(q, k, v, fwd_map, mask, out, chunk, N, HW, H, D, scale, q_ld, k_ld, v_ld, false, stream,
-                             dtype);
-}
-
-extern "C" int fresco_temporal_attn_packed_dt(const void* qkv, const uint8_t* mask, void* out, int chunk, int N, int P,
-                                              int H, int D, float scale, int dtype, void* stream) {
+extern "C" int fresco_temporal_attn_packed(const void* qkv, const uint8_t* mask, void* out, int chunk, int N, int P,
+                                           int H, int D, float scale, int dtype, void* stream) {
     if (!qkv) return FRESCO_EINVAL;
     const int64_t Cw = (int64_t)H * D;
     const half_t* b = static_cast<const half_t*>(qkv);  // (2-byte elements either way: the offsets are the same)
     return temporal_dispatch(b, b + Cw, b + 2 * Cw, nullptr, mask, out, chunk, N, P, H, D, scale, 3 * Cw, 3 * Cw,
-                             3 * Cw, true, stream, dtype);
-}
-
-extern "C" int fresco_temporal_attn_packed(const void* qkv, const uint8_t* mask, void* out, int chunk, int N, int P,
-                                           int H, int D, float scale, void* stream) {
-    return fresco_temporal_attn_packed_dt(qkv, mask, out, chunk, N, P, H, D, scale, FRESCO_F16, stream);
+                             3 * Cw, true, dtype, stream);
 }
 
 static int pack_dispatch(bool unpack, const void* q, const void* k, const void* v, const int64_t* fwd_map, void* buf,

@@ -33,7 +33,7 @@ received to use 2): a rank sends its last frame to the right neighbour and its f
 (chunk, C, h, w) slabs out, two in, whatever the world size; one slab each way when n_loc = 1 on two ranks (first frame
 = last frame, left neighbour = right neighbour).  The exchange is started asynchronously right after Adam(it - 1), runs
 under the launches of step it that read no halo frame (normalise, signs of the interior pairs, Gram, S V:
-`fresco_opt_sharded_step_part` part 1) and is waited for only in front of the two boundary pairs' signs + Adam (part 2).
+`fresco_opt_sharded_step` part 1) and is waited for only in front of the two boundary pairs' signs + Adam (part 2).
 Each rank evaluates the n_loc+1 frame pairs touching its frames.  warp_tensor's frame chain is a scan over frames and is
 not sharded (replicas).
 

@@ -76,7 +76,7 @@ class Workspace:
 
 
 class OptContext:
-    """A fresco_ctx (include/fresco_hip.h): the side stream + events the two-pipeline form of fresco_opt_run_ctx uses.  Owned
+    """A fresco_ctx (include/fresco_hip.h): the side stream + events the two-pipeline form of fresco_opt_run uses.  Owned
     by the caller -- the library keeps no process-wide stream table; one context per host thread and device."""
 
     def __init__(self):
@@ -137,7 +137,7 @@ _default_ws = _PerStreamWorkspace()
 # ---------------------------------------------------------------------------------------------
 # fused linear projections
 # ---------------------------------------------------------------------------------------------
-# element types of the 16-bit MFMA kernels (linear, attention, temporal attention) -> dtype code of the *_dt entry points
+# element types of the 16-bit MFMA kernels (linear, attention, temporal attention) -> dtype code of their entry points
 _MFMA_DTYPES = {torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 
 
@@ -227,13 +227,8 @@ def linear(x, weights, biases=None, outs=None, x_rows=None, x_rows_trusted=False
     while len(ptrs) < 3:
         ptrs.append(None)
         lds.append(0)
-    if x_rows is not None:
-        rc = _lib.load().fresco_linear_rows_dt(x2.data_ptr(), x_ld, x_rows.data_ptr(), wp[0], wp[1], wp[2], bp[0], bp[1],
-                                               bp[2], ptrs[0], ptrs[1], ptrs[2], lds[0], lds[1], lds[2], nw, M, N, K,
-                                               _MFMA_DTYPES[dt], _stream())
-    else:
-        rc = _lib.load().fresco_linear_dt(x2.data_ptr(), x_ld, wp[0], wp[1], wp[2], bp[0], bp[1], bp[2], ptrs[0], ptrs[1],
-                                          ptrs[2], lds[0], lds[1], lds[2], nw, M, N, K, _MFMA_DTYPES[dt], _stream())
+    rc = _lib.load().fresco_linear(x2.data_ptr(), x_ld, _ptr(x_rows), wp[0], wp[1], wp[2], bp[0], bp[1], bp[2], ptrs[0],
+                                   ptrs[1], ptrs[2], lds[0], lds[1], lds[2], nw, M, N, K, _MFMA_DTYPES[dt], _stream())
     _lib.check(rc, "fresco_linear(M=%d,N=%d,K=%d,nw=%d)" % (M, N, K, nw))
     return outs
 
@@ -289,9 +284,9 @@ def attention(q, k, v, heads, scale, *, kv_rows=None, n_groups=None, M=None, gro
     ws_bytes = lib.fresco_attn_workspace_bytes(n_groups, heads, M, D)
     ws = (workspace or _default_ws).get(ws_bytes, q.device)
     out = torch.empty((B, Lq, C), dtype=q.dtype, device=q.device)
-    rc = lib.fresco_attn_fwd_dt(q.data_ptr(), k.data_ptr(), v.data_ptr(), _ptr(kv_rows), out.data_ptr(),
-                                ws.data_ptr(), ws.numel(), B, heads, Lq, D, n_groups, M, group_rows,
-                                float(scale), float(diag_bias), q_ld, kv_ld, _MFMA_DTYPES[q.dtype], _stream())
+    rc = lib.fresco_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _ptr(kv_rows), out.data_ptr(),
+                             ws.data_ptr(), ws.numel(), B, heads, Lq, D, n_groups, M, group_rows,
+                             float(scale), float(diag_bias), q_ld, kv_ld, _MFMA_DTYPES[q.dtype], _stream())
     _lib.check(rc, "fresco_attn_fwd(B=%d,H=%d,Lq=%d,D=%d,groups=%d,M=%d)" % (B, heads, Lq, D, n_groups, M))
     return out
 
@@ -325,15 +320,15 @@ def attention_kvproj(q, hidden, x_rows, w_k, w_v, heads, scale, n_groups, M, wor
     ws_bytes = lib.fresco_attn_workspace_bytes(n_groups, heads, M, D)
     ws = (workspace or _default_ws).get(ws_bytes, q.device)
     out = torch.empty((B, Lq, C), dtype=q.dtype, device=q.device)
-    rc = lib.fresco_attn_fwd_kvproj_dt(q.data_ptr(), hidden.data_ptr(), x_ld, x_rows.data_ptr(), w_k.data_ptr(),
-                                       w_v.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, heads, Lq, D, n_groups,
-                                       M, K_in, float(scale), q_ld, _MFMA_DTYPES[dt], _stream())
+    rc = lib.fresco_attn_fwd_kvproj(q.data_ptr(), hidden.data_ptr(), x_ld, x_rows.data_ptr(), w_k.data_ptr(),
+                                    w_v.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, heads, Lq, D, n_groups,
+                                    M, K_in, float(scale), q_ld, _MFMA_DTYPES[dt], _stream())
     _lib.check(rc, "fresco_attn_fwd_kvproj(B=%d,H=%d,Lq=%d,D=%d,groups=%d,M=%d,K=%d)" % (B, heads, Lq, D, n_groups, M, K_in))
     return out
 
 
 def attention_f32(q, k, v, scale):
-    """softmax(scale * q k^T) v at fp32 accuracy (fresco_attn_f32_guarded): q (B,Lq,D), k (B,Lk,D), v (B,Lk,Dv) ->
+    """softmax(scale * q k^T) v at fp32 accuracy (fresco_attn_f32 with a flag): q (B,Lq,D), k (B,Lk,D), v (B,Lk,Dv) ->
     (B,Lq,Dv).  One head; batch entries are independent problems (windows).  When several 128-query workgroups share a
     key set (Lq >= 256) K and V are converted to the kernel's operand images once per launch, into a workspace taken from
     the caching allocator PER CALL (stream-safe: two streams running the flow network never share it; nothing is kept).
@@ -350,16 +345,16 @@ def attention_f32(q, k, v, scale):
     need = lib.fresco_attn_f32_workspace_bytes(B, Lk, D, Dv) if Lq >= 256 else 0
     if need:
         # workspace form: the range tests ride in the split pass and the attention prologue; the flag is a word of a
-        # zero-filled pool, handed out once (no memset, no range pass: 20 us of short launches per call, round 6)
+        # zero-filled pool, handed out once (no memset, no range pass: 20 us of short launches per call)
         ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-        rc = lib.fresco_attn_f32_guarded_ws(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ws.data_ptr(), need,
-                                            _a32_zero_flag(q.device), B, Lq, Lk, D, Dv, float(scale), _stream())
-        _lib.check(rc, "fresco_attn_f32_guarded_ws(B=%d,Lq=%d,Lk=%d,D=%d,Dv=%d)" % (B, Lq, Lk, D, Dv))
-        return out
-    flag = torch.empty(1, dtype=torch.int32, device=q.device)
-    rc = lib.fresco_attn_f32_guarded(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), None, 0,
-                                     flag.data_ptr(), B, Lq, Lk, D, Dv, float(scale), _stream())
-    _lib.check(rc, "fresco_attn_f32_guarded(B=%d,Lq=%d,Lk=%d,D=%d,Dv=%d)" % (B, Lq, Lk, D, Dv))
+        flag = _a32_zero_flag(q.device)
+    else:
+        ws = None
+        fresh = torch.empty(1, dtype=torch.int32, device=q.device)  # (the call clears it and runs the range pass)
+        flag = fresh.data_ptr()
+    rc = lib.fresco_attn_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(ws), need, flag,
+                             1 if need else 0, B, Lq, Lk, D, Dv, float(scale), _stream())
+    _lib.check(rc, "fresco_attn_f32(B=%d,Lq=%d,Lk=%d,D=%d,Dv=%d)" % (B, Lq, Lk, D, Dv))
     return out
 
 
@@ -696,9 +691,9 @@ def temporal_attention(q, k, v, fwd_map, mask, heads, scale, chunk):
     fwd_map, mask = _prep_maps(fwd_map, mask, N, HW)
     _check_permutations(owner, fwd_map, HW)
     out = torch.empty((Bt, HW, C), dtype=q.dtype, device=q.device)
-    rc = _lib.load().fresco_temporal_attn_dt(q.data_ptr(), k.data_ptr(), v.data_ptr(), fwd_map.data_ptr(),
-                                             mask.data_ptr(), out.data_ptr(), chunk, N, HW, heads, D,
-                                             float(scale), q_ld, k_ld, v_ld, _MFMA_DTYPES[q.dtype], _stream())
+    rc = _lib.load().fresco_temporal_attn(q.data_ptr(), k.data_ptr(), v.data_ptr(), fwd_map.data_ptr(),
+                                          mask.data_ptr(), out.data_ptr(), chunk, N, HW, heads, D,
+                                          float(scale), q_ld, k_ld, v_ld, _MFMA_DTYPES[q.dtype], _stream())
     _lib.check(rc, "fresco_temporal_attn(chunk=%d,N=%d,HW=%d,H=%d,D=%d)" % (chunk, N, HW, heads, D))
     return out
 
@@ -723,7 +718,7 @@ def temporal_pack(q, k, v, fwd_map, chunk, n_loc, f0, world):
 
 
 def temporal_attention_packed(qkv, mask, heads, scale, chunk):
-    """fresco_temporal_attn_packed_dt: qkv (N, chunk, P, 3C) fp16 or bf16 = q | k | v rows already in trajectory order
+    """fresco_temporal_attn_packed: qkv (N, chunk, P, 3C) fp16 or bf16 = q | k | v rows already in trajectory order
     for a range of P trajectories, mask (P, N, N) for that range -> (N, chunk, P, C) of qkv's dtype."""
     _need_gpu(qkv, mask)
     N, ch, P, C3 = qkv.shape
@@ -735,8 +730,8 @@ def temporal_attention_packed(qkv, mask, heads, scale, chunk):
     if mask.shape[0] != P:
         raise ValueError("temporal_attention_packed: mask must cover the %d trajectories of the range" % P)
     out = torch.empty((N, chunk, P, C), dtype=qkv.dtype, device=qkv.device)
-    rc = _lib.load().fresco_temporal_attn_packed_dt(qkv.data_ptr(), mask.data_ptr(), out.data_ptr(), chunk, N, P, heads,
-                                                    D, float(scale), _MFMA_DTYPES[qkv.dtype], _stream())
+    rc = _lib.load().fresco_temporal_attn_packed(qkv.data_ptr(), mask.data_ptr(), out.data_ptr(), chunk, N, P, heads,
+                                                 D, float(scale), _MFMA_DTYPES[qkv.dtype], _stream())
     _lib.check(rc, "fresco_temporal_attn_packed(chunk=%d,N=%d,P=%d,H=%d,D=%d)" % (chunk, N, P, heads, D))
     return out
 
@@ -1104,7 +1099,7 @@ def opt_run(cs, prep, target, intra_weight, iters, chunk, lr=0.2, betas=(0.9, 0.
     nbytes = lib.fresco_opt_workspace_bytes(chunk, N, C, h, w, has_t, has_s)
     ws = (workspace or _default_ws).get(nbytes, cs.device)
     ctx = context or _opt_contexts.get(cs.device)
-    rc = lib.fresco_opt_run_ctx(ctx.ptr, cs.data_ptr(), _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]),
+    rc = lib.fresco_opt_run(ctx.ptr, cs.data_ptr(), _ptr(keep[0]), _ptr(keep[1]), _ptr(keep[2]), _ptr(keep[3]),
                             _ptr(target), ws.data_ptr(), ws.numel(), chunk, N, C, h, w, float(intra_weight),
                             int(iters), float(lr), float(betas[0]), float(betas[1]), float(eps), _stream())
     _lib.check(rc, "fresco_opt_run(chunk=%d,N=%d,C=%d,h=%d,w=%d)" % (chunk, N, C, h, w))
@@ -1144,11 +1139,11 @@ def opt_run_sharded(cs, prep_pairs, target, intra_weight, iters, chunk, N_total,
     overlapped = hasattr(exchange, "halo_start") and hasattr(exchange, "halo_finish")
 
     def step(it, halo_l, halo_r, part):
-        rc = lib.fresco_opt_sharded_step_part(cs.data_ptr(), _ptr(halo_l), _ptr(halo_r), _ptr(keep[0]), _ptr(keep[1]),
-                                              _ptr(keep[2]), _ptr(keep[3]), _ptr(target), ws.data_ptr(), ws.numel(),
-                                              chunk, n_loc, N_total, C, h, w, float(intra_weight), it, float(lr),
-                                              float(betas[0]), float(betas[1]), float(eps), part, _stream())
-        _lib.check(rc, "fresco_opt_sharded_step_part(it=%d, part=%d)" % (it, part))
+        rc = lib.fresco_opt_sharded_step(cs.data_ptr(), _ptr(halo_l), _ptr(halo_r), _ptr(keep[0]), _ptr(keep[1]),
+                                         _ptr(keep[2]), _ptr(keep[3]), _ptr(target), ws.data_ptr(), ws.numel(),
+                                         chunk, n_loc, N_total, C, h, w, float(intra_weight), it, float(lr),
+                                         float(betas[0]), float(betas[1]), float(eps), part, _stream())
+        _lib.check(rc, "fresco_opt_sharded_step(it=%d, part=%d)" % (it, part))
 
     for it in range(1, iters + 1):
         if not has_t:
@@ -1191,7 +1186,7 @@ def gram_target(x, workspace=None):
     B, C, h, w = x.shape
     hw = h * w
     out = torch.empty(B, hw, hw, dtype=torch.float32, device=x.device)
-    nbytes = (B * C * hw * 4 + 255) // 256 * 256 + 33 * ((B * hw * 4 + 255) // 256 * 256) + 512
+    nbytes = _lib.load().fresco_gram_target_workspace_bytes(B, C, hw)
     ws = (workspace or _default_ws).get(nbytes, x.device)
     rc = _lib.load().fresco_gram_target(x.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), B, C, hw,
                                         _stream())

@@ -40,19 +40,19 @@ class FRESCOAttnProcessor2_0:
         self.fuse_projections = True  # q/k/v (and to_out at C = 320) through fresco_linear when they are plain Linears
         # cross-frame-only calls (no temporal pass) read K and V of the selected tokens only: project just those
         self.sparse_kv_projection = True
-        # ... and project them INSIDE the key pack: one launch instead of fresco_linear_rows + kv_pack, the selected K and V
+        # ... and project them INSIDE the key pack: one launch instead of fresco_linear with x_rows + kv_pack, the selected K and V
         # never reach HBM (fresco_attn_fwd_kvproj; plain bias-free fp16 to_k / to_v of a supported width only; bf16 ones under
         # fuse_kv_pack_bf16).  Calls with
         # the temporal pass take it too: that pass reads K of every row but V of none, so to_q | to_k are projected in full
         # and V only inside the pack
         self.fuse_kv_pack = True
 
-    # bf16 modules / activations run on the bf16 kernels (fresco_linear_dt, fresco_attn_fwd_dt, fresco_temporal_attn_dt, and
-    # fresco_temporal_attn_packed_dt in the frame-sharded branch): no cast, no warning, bf16 out.  False restores the
+    # bf16 modules / activations run on the bf16 kernels (fresco_linear, fresco_attn_fwd, fresco_temporal_attn with FRESCO_BF16, and
+    # fresco_temporal_attn_packed in the frame-sharded branch): no cast, no warning, bf16 out.  False restores the
     # rounding path (library GEMMs, q / k / v rounded to fp16 for the kernels, one RuntimeWarning) for A/B measurements.
     native_bf16 = True
-    # bf16 calls take the fused K | V projection-pack (fresco_attn_fwd_kvproj_dt) like fp16 ones do under fuse_kv_pack.  Off
-    # by default: no bf16 timing of the fused form against fresco_linear_rows + kv_pack has been recorded on a GPU yet
+    # bf16 calls take the fused K | V projection-pack (fresco_attn_fwd_kvproj) like fp16 ones do under fuse_kv_pack.  Off
+    # by default: no bf16 timing of the fused form against fresco_linear with x_rows + kv_pack has been recorded on a GPU yet
     # (tools/bench_bf16.py measures both legs; EXPERIMENTS.md section 8), and tests/test_gpu_bf16_pipeline.py pins the
     # default bf16 launch sequence.  Flipping the default, together with that test, is the follow-up once the numbers exist.
     fuse_kv_pack_bf16 = False
@@ -113,7 +113,7 @@ class FRESCOAttnProcessor2_0:
         if hit is None or (mask is not None and hit[0]() is not mask):
             base = (torch.arange(hw, device=device) if mask is None else self._kv_rows(mask, as_long=True).to(device))
             rows = torch.cat([base + c * n_frames * hw for c in range(chunk)]).to(torch.int32).contiguous()
-            # the table is handed to fresco_linear_rows unchecked on every later call: check it once, here
+            # the table is handed to fresco_linear unchecked on every later call: check it once, here
             if rows.numel() and not (0 <= int(rows.min()) and int(rows.max()) < chunk * n_frames * hw):
                 raise ValueError("fresco_amd: cross-frame mask of shape %s addresses tokens outside the (%d, %d, %d) batch"
                                  % (tuple(mask.shape), chunk, n_frames, hw))

@@ -41,7 +41,7 @@ extern "C" {
 /* dtype codes for entry points that accept more than one element type */
 #define FRESCO_F16 0
 #define FRESCO_F32 1
-#define FRESCO_BF16 2 /* bfloat16: the *_dt entry points below, fresco_adain, fresco_chan_mean_std, fresco_ddpm_*, fresco_freeu_*, fresco_hed_fuse */
+#define FRESCO_BF16 2 /* bfloat16: the entry points below that take a `dtype`, fresco_adain, fresco_chan_mean_std, fresco_ddpm_*, fresco_freeu_*, fresco_hed_fuse */
 
 /* library / build identification: "fresco_hip <version> gfx950" */
 const char* fresco_version(void);
@@ -92,53 +92,53 @@ int fresco_prof_read(int max_records, int* tags, int* dims, float* ms);
  *                         "every frame uses frame 0" (former_frame_index, DH:227).
  *           spatial     : n_groups = B, group_rows = HW, kv_rows = NULL, M = HW,
  *                         q = to_q(ref), k = to_k(ref), v = current query, scale = 0.2/sqrt(D).
- *   out : (B, Lq, H*D) half.
- *   D must be a multiple of 8, 8 <= D <= 128.  Softmax in fp32, P and V in half, accumulation fp32.
- *   Numerics: the exponent scale  scale*log2(e)  is folded into the fp16 query (one rounding) only for
+ *   out : (B, Lq, H*D) half, always dense.
+ *   Row strides (in elements, multiples of 8, >= H*D): q row r starts at q + r*q_ld, k / v row r at k + r*kv_ld -- dense
+ *   callers pass H*D; q, k, v may be column slices of one fused projection output (B, HW, 3*H*D).
+ *   dtype = FRESCO_F16 or FRESCO_BF16 for q, k, v and out (any other code: FRESCO_EINVAL before any HIP call; "half" above
+ *   reads as the element type).  Elements are 2 bytes either way: same workspace, same packed key image geometry.
+ *   D in {8, 16, 32, 40, 64, 80, 96, 128}, both element types.  Softmax in fp32, P and V in the element type, accumulation
+ *   fp32.
+ *   Numerics, fp16: the exponent scale  scale*log2(e)  is folded into the fp16 query (one rounding) only for
  *   queries whose logits are provably small (scale*log2e*|q|*max|k| <= 16, a per-wavefront decision from
  *   the key norms the pack pass records); otherwise scores are scaled in fp32.  Logits are assumed to stay
  *   below 6e4 in log2 units.
+ *   Numerics, bf16: scores and softmax in fp32, P and O^T products on the bf16 MFMA; the softmax scale is never folded into
+ *   the bf16 Q (one bf16 rounding of scale*q costs more than P's own rounding) but applied to the fp32 scores; the running
+ *   max is kept on the bf16 grid.
  *   Workspace: packed K / V^T images of every key group and head plus one float per 64-key tile.
  * ------------------------------------------------------------------------------------------ */
 size_t fresco_attn_workspace_bytes(int n_groups, int H, int M, int D);
+int fresco_attn_fwd(const void* q, const void* k, const void* v, const int32_t* kv_rows,
+                    void* out, void* workspace, size_t workspace_bytes,
+                    int B, int H, int Lq, int D,
+                    int n_groups, int M, int64_t group_rows,
+                    float scale, float diag_bias, int64_t q_ld, int64_t kv_ld, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a1)  Fused linear projections  attn.to_q / to_k / to_v (DH:201, 214-215, 260-261) and to_out[0] (DH:375):
  *           out_j = x W_j^T (+ b_j),   j = 0 .. nw-1,  nw <= 3
  *   x    : (M, K) half, row stride x_ld (elements);  read once for all nw outputs
+ *   x_rows : NULL, or int32 (M): problem row m reads x row x_rows[m] (each inside the x buffer -- the caller's contract).
+ *          Used for the K / V projection of the tokens the efficient cross-frame pass selects (DH:225-247) when nothing
+ *          else reads K and V: project only what is gathered.
  *   W_j  : (N, K) half row-major = the weight of nn.Linear j, read where it lives (nothing is stacked or cached:
  *          in-place updates of a module's weight are seen by the next call);  W1 / W2 unused beyond nw
  *   b_j  : (N) half or NULL
  *   out_j: (M, N) half, row stride ld_j (elements); unused outputs NULL
- *   fp32 accumulation, one rounding to half at the end (what the library GEMM behind nn.Linear does).
+ *   dtype = FRESCO_F16 or FRESCO_BF16 for ALL operands (x, W_j, b_j, out_j; strides stay in elements of 2 bytes; "half"
+ *   above reads as the element type).  Any other dtype code: FRESCO_EINVAL, before any HIP call.
+ *   fp32 accumulation, one rounding to nearest even at the store (what the library GEMM behind nn.Linear does); bf16 runs
+ *   the same kernel on v_mfma_f32_32x32x16_bf16.
  *   Supported: K in {320, 640} (SD-1.5 up_blocks.3 / up_blocks.2), N % 64 == 0, nw * N <= 2048 (fresco_linear_plan
  *   answers without a launch); anything else returns FRESCO_EUNSUPPORTED and the caller keeps its own GEMM.
  * ------------------------------------------------------------------------------------------ */
-int fresco_linear(const void* x, int64_t x_ld, const void* W0, const void* W1, const void* W2, const void* b0,
-                  const void* b1, const void* b2, void* out0, void* out1, void* out2, int64_t ld0, int64_t ld1,
-                  int64_t ld2, int nw, int M, int N, int K, void* stream);
+int fresco_linear(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1, const void* W2,
+                  const void* b0, const void* b1, const void* b2, void* out0, void* out1, void* out2, int64_t ld0,
+                  int64_t ld1, int64_t ld2, int nw, int M, int N, int K, int dtype, void* stream);
 
-/* The same with gathered input rows: problem row m reads x row x_rows[m] (int32, M entries, each inside the x buffer --
- * the caller's contract).  Used for the K / V projection of the tokens the efficient cross-frame pass selects
- * (DH:225-247) when nothing else reads K and V: project only what is gathered. */
-int fresco_linear_rows(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1,
-                       const void* W2, const void* b0, const void* b1, const void* b2, void* out0, void* out1,
-                       void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, void* stream);
-
-/* fresco_linear / fresco_linear_rows with an element type: dtype = FRESCO_F16 or FRESCO_BF16 for ALL operands (x, W_j,
- * b_j, out_j; strides stay in elements of 2 bytes).  bf16 runs the same kernel on v_mfma_f32_32x32x16_bf16: fp32
- * accumulation, one rounding to nearest even at the store.  Any other dtype code: FRESCO_EINVAL, before any HIP call. */
-int fresco_linear_dt(const void* x, int64_t x_ld, const void* W0, const void* W1, const void* W2, const void* b0,
-                     const void* b1, const void* b2, void* out0, void* out1, void* out2, int64_t ld0, int64_t ld1,
-                     int64_t ld2, int nw, int M, int N, int K, int dtype, void* stream);
-int fresco_linear_rows_dt(const void* x, int64_t x_ld, const int32_t* x_rows, const void* W0, const void* W1,
-                          const void* W2, const void* b0, const void* b1, const void* b2, void* out0, void* out1,
-                          void* out2, int64_t ld0, int64_t ld1, int64_t ld2, int nw, int M, int N, int K, int dtype,
-                          void* stream);
-
-
-/* The launch fresco_linear* would make for (nw, M, N, K), decided on the host alone (no launch, no HIP call, no GPU needed):
- * returns what those entry points return for the same four arguments -- FRESCO_EINVAL for nw outside 1..3 or a size <= 0,
+/* The launch fresco_linear would make for (nw, M, N, K), decided on the host alone (no launch, no HIP call, no GPU needed):
+ * returns what that entry point returns for the same four arguments -- FRESCO_EINVAL for nw outside 1..3 or a size <= 0,
  * FRESCO_EUNSUPPORTED for N % 64 != 0, K outside {320, 640} or an LDS plan beyond 160 KiB (ring + x staging + an nw * N
  * bias image, charged with or without biases: nw * N <= 2048) -- and, on FRESCO_OK, writes the grid (row_blocks =
  * ceil(M / 256), splits) and the number of 64-feature tiles of the nw * N / 64 a workgroup walks (the last split may get
@@ -148,58 +148,28 @@ int fresco_linear_rows_dt(const void* x, int64_t x_ld, const int32_t* x_rows, co
 int fresco_linear_plan(int nw, int M, int N, int K, int* row_blocks, int* splits, int* tiles_per_split);
 
 
-int fresco_attn_fwd(const void* q, const void* k, const void* v, const int32_t* kv_rows,
-                    void* out, void* workspace, size_t workspace_bytes,
-                    int B, int H, int Lq, int D,
-                    int n_groups, int M, int64_t group_rows,
-                    float scale, float diag_bias, void* stream);
-
-/* Same with explicit row strides (in halfs, multiples of 8, >= H*D): q row r starts at q + r*q_ld,
- * k / v row r at k + r*kv_ld -- for q, k, v that are column slices of one fused projection output
- * (B, HW, 3*H*D).  `out` is always dense (B, Lq, H*D). */
-int fresco_attn_fwd_ld(const void* q, const void* k, const void* v, const int32_t* kv_rows,
-                       void* out, void* workspace, size_t workspace_bytes,
-                       int B, int H, int Lq, int D,
-                       int n_groups, int M, int64_t group_rows,
-                       float scale, float diag_bias, int64_t q_ld, int64_t kv_ld, void* stream);
-
-/* fresco_attn_fwd_ld with an element type: dtype = FRESCO_F16 or FRESCO_BF16 for q, k, v and out (any other code:
- * FRESCO_EINVAL before any HIP call).  Elements are 2 bytes either way: same workspace (fresco_attn_workspace_bytes),
- * same packed key image geometry.  bf16: scores and softmax in fp32, P and O^T products on the bf16 MFMA; the softmax
- * scale is never folded into the bf16 Q (one bf16 rounding of scale*q costs more than P's own rounding) but applied to
- * the fp32 scores; the running max is kept on the bf16 grid.  All eight head dims. */
-int fresco_attn_fwd_dt(const void* q, const void* k, const void* v, const int32_t* kv_rows,
-                       void* out, void* workspace, size_t workspace_bytes,
-                       int B, int H, int Lq, int D,
-                       int n_groups, int M, int64_t group_rows,
-                       float scale, float diag_bias, int64_t q_ld, int64_t kv_ld, int dtype, void* stream);
-
-/* Cross-frame pass with the K | V projection of the selected rows FUSED into the key pack (round 6) -- for layer calls
+/* Cross-frame pass with the K | V projection of the selected rows FUSED into the key pack -- for layer calls
  * whose only reader of K and V is the cross-frame pass (DH:201-247 on the cross-frame-only steps): replaces
  * attn.to_k / attn.to_v on the gathered rows (DH:214-215 restricted to the tokens DH:239-247 keep) + the pack.
- *   x      : hidden states, fp16 rows of K_in features, row r at x + r*x_ld
+ *   x      : hidden states, rows of K_in features, row r at x + r*x_ld
  *   x_rows : int32 (n_groups * M): key m of group g is row x_rows[g*M + m] of x (rows may repeat; must be in range --
  *            the table is not checked on the device)
- *   Wk, Wv : (H*D, K_in) row-major fp16 weights of the bias-free projections (read where they live, every call)
+ *   Wk, Wv : (H*D, K_in) row-major weights of the bias-free projections (read where they live, every call)
  *   q, out, workspace (fresco_attn_workspace_bytes(n_groups, H, M, D)), B, H, Lq, D, n_groups, M, scale, q_ld: as
- *   fresco_attn_fwd_ld; batch element b uses key group b / (B / n_groups).
- * K = x[rows] Wk^T and V = x[rows] Wv^T are rounded to fp16 exactly once (as the two-launch path rounds them) and go
- * straight into the packed key image: they never exist in HBM.  Supported: (D, K_in) = (40, 320), (80, 640) with
- * H*D == K_in (SD-1.5's decoder self-attentions); fresco_attn_kvproj_supported says so, anything else returns
- * FRESCO_EUNSUPPORTED and the caller uses fresco_linear_rows + fresco_attn_fwd_ld. */
+ *   fresco_attn_fwd; batch element b uses key group b / (B / n_groups).
+ *   dtype = FRESCO_F16 or FRESCO_BF16 for q, x, Wk, Wv and out (any other code: FRESCO_EINVAL; every argument check
+ *   answers before any HIP call).
+ * K = x[rows] Wk^T and V = x[rows] Wv^T are rounded to the element type exactly once (as the two-launch path rounds them)
+ * and go straight into the packed key image: they never exist in HBM.  bf16: the projection on the bf16 MFMA with the
+ * same contraction order and one fp32 chain per output, the ones column / row of the image in bf16, max |k|^2 over the
+ * rounded K; then the bf16 flash kernels of fresco_attn_fwd (scale never folded).
+ * Supported: (D, K_in) = (40, 320), (80, 640) with H*D == K_in (SD-1.5's decoder self-attentions);
+ * fresco_attn_kvproj_supported says so, anything else returns FRESCO_EUNSUPPORTED and the caller uses fresco_linear with
+ * x_rows + fresco_attn_fwd. */
 int fresco_attn_kvproj_supported(int H, int D, int K_in);
 int fresco_attn_fwd_kvproj(const void* q, const void* x, int64_t x_ld, const int32_t* x_rows, const void* Wk,
                            const void* Wv, void* out, void* workspace, size_t workspace_bytes, int B, int H, int Lq,
-                           int D, int n_groups, int M, int K_in, float scale, int64_t q_ld, void* stream);
-
-/* fresco_attn_fwd_kvproj with an element type: dtype = FRESCO_F16 or FRESCO_BF16 for q, x, Wk, Wv and out (any other
- * code: FRESCO_EINVAL; every argument check answers before any HIP call).  bf16: the projection on the bf16 MFMA with
- * the same contraction order and one fp32 chain per output, K and V rounded to bf16 once, the ones column / row of the
- * image in bf16, max |k|^2 over the rounded K; then the bf16 flash kernels of fresco_attn_fwd_dt (scale never folded).
- * fresco_attn_fwd_kvproj is this with FRESCO_F16. */
-int fresco_attn_fwd_kvproj_dt(const void* q, const void* x, int64_t x_ld, const int32_t* x_rows, const void* Wk,
-                              const void* Wv, void* out, void* workspace, size_t workspace_bytes, int B, int H, int Lq,
-                              int D, int n_groups, int M, int K_in, float scale, int64_t q_ld, int dtype, void* stream);
+                           int D, int n_groups, int M, int K_in, float scale, int64_t q_ld, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a4)  Temporal-guided (FLATTEN) attention -- replaces DH:309-367: 3 rearrange+gather round
@@ -209,31 +179,21 @@ int fresco_attn_fwd_kvproj_dt(const void* q, const void* x, int64_t x_ld, const 
  *     row(f) = fwd_map[f*HW + p]
  *     out[c*N+f, row(f), h, :] = sum_g softmax_g( scale*<q[c*N+f,row(f),h,:], k[c*N+g,row(g),h,:]>
  *                                                 | mask[p,f,g] ) * v[c*N+g,row(g),h,:]
- *   q,k,v,out : (chunk*N, HW, H*D) half;  fwd_map : (N, HW) int64 (a permutation per frame);
+ *   q,k,v,out : (chunk*N, HW, H*D) half;  q, k, v rows start every q_ld / k_ld / v_ld elements (multiples of 8, >= H*D;
+ *   dense callers pass H*D), out is dense;  fwd_map : (N, HW) int64 (a permutation per frame);
  *   mask : (HW, N, N) uint8/bool, non-zero = may attend (diagonal always set, FU:120-131).
  *   D in {8, 16, 32, 40, 64, 80}; chunk*N*HW < 2^31.  N <= 32: MFMA kernel (needs N * (6*(H*D + 8) + 4 + N) bytes
  *   <= 160 KiB of LDS for 16 < N <= 32: every SD-1.5 shape fits); N > 32: vector-ALU kernel while 6*N*H*D + 4*N + N*N
  *   bytes <= 160 KiB; otherwise FRESCO_EUNSUPPORTED.  Row-table entries outside [0, HW) are skipped (no row is read or
  *   written for them; a table that is not a permutation is the caller's bug).  A query whose mask row is all zero
  *   yields NaN, like the reference's softmax over an all -inf row.
+ *   dtype = FRESCO_F16 or FRESCO_BF16 for q, k, v and out (any other code: FRESCO_EINVAL before any HIP call).  The scale
+ *   (the reference's 0.2 key factor included) stays an fp32 factor of the scores.
  * ------------------------------------------------------------------------------------------ */
 int fresco_temporal_attn(const void* q, const void* k, const void* v, const int64_t* fwd_map,
                          const uint8_t* mask, void* out,
-                         int chunk, int N, int HW, int H, int D, float scale, void* stream);
-
-/* Row-strided form (q, k, v rows start every q_ld / k_ld / v_ld halfs; out dense). */
-int fresco_temporal_attn_ld(const void* q, const void* k, const void* v, const int64_t* fwd_map,
-                            const uint8_t* mask, void* out,
-                            int chunk, int N, int HW, int H, int D, float scale,
-                            int64_t q_ld, int64_t k_ld, int64_t v_ld, void* stream);
-
-/* The row-strided form with an element type: dtype = FRESCO_F16 or FRESCO_BF16 for q, k, v and out (any other code:
- * FRESCO_EINVAL before any HIP call).  The scale (the reference's 0.2 key factor included) stays an fp32 factor of the
- * scores.  The packed form has its own: fresco_temporal_attn_packed_dt below. */
-int fresco_temporal_attn_dt(const void* q, const void* k, const void* v, const int64_t* fwd_map,
-                            const uint8_t* mask, void* out,
-                            int chunk, int N, int HW, int H, int D, float scale,
-                            int64_t q_ld, int64_t k_ld, int64_t v_ld, int dtype, void* stream);
+                         int chunk, int N, int HW, int H, int D, float scale,
+                         int64_t q_ld, int64_t k_ld, int64_t v_ld, int dtype, void* stream);
 
 /* Multi-GPU: frames are sharded over ranks, the temporal pass is sharded by TRAJECTORY, so that
  * every byte crosses the fabric once and the kernel's HBM traffic shrinks with the world size.  Rank r owns the
@@ -243,22 +203,19 @@ int fresco_temporal_attn_dt(const void* q, const void* k, const void* v, const i
  *                           the leading `world` dimension then leaves on rank r the rows of ALL N frames of its range as
  *                           (N, chunk, P, 3C);
  *   fresco_temporal_attn_packed : the attention on such rows, no row table: qkv (N, chunk, P, 3C), mask (P, N, N) = the
- *                           mask rows of the range, out (N, chunk, P, C);
+ *                           mask rows of the range, out (N, chunk, P, C); dtype = FRESCO_F16 or FRESCO_BF16 for qkv and
+ *                           out (any other code: FRESCO_EINVAL before any HIP call);
  *   fresco_temporal_unpack: after the all-to-all back, buf (world, n_loc, chunk, P, C) holds this rank's frames' result rows
  *                           per range:  out[c*n_loc + fl][fwd_map[f0+fl][d*P + pl]] = buf[(d*n_loc + fl)*chunk + c][pl]. */
 int fresco_temporal_pack(const void* q, const void* k, const void* v, const int64_t* fwd_map, void* buf, int chunk,
                          int n_loc, int f0, int HW, int C, int world, int64_t q_ld, int64_t k_ld, int64_t v_ld,
                          void* stream);
 int fresco_temporal_attn_packed(const void* qkv, const uint8_t* mask, void* out, int chunk, int N, int P, int H, int D,
-                                float scale, void* stream);
+                                float scale, int dtype, void* stream);
 int fresco_temporal_unpack(const void* buf, const int64_t* fwd_map, void* out, int chunk, int n_loc, int f0, int HW,
                            int C, int world, void* stream);
-/* fresco_temporal_attn_packed with an element type: dtype = FRESCO_F16 or FRESCO_BF16 for qkv and out (any other code:
- * FRESCO_EINVAL before any HIP call); fresco_temporal_attn_packed is this with FRESCO_F16.
- * fresco_temporal_pack / fresco_temporal_unpack move 16-byte pieces of 16-bit words and do no arithmetic: they are
+/* fresco_temporal_pack / fresco_temporal_unpack move 16-byte pieces of 16-bit words and do no arithmetic: they are
  * element-type agnostic for 2-byte types (fp16 and bf16 alike) and need no dtype. */
-int fresco_temporal_attn_packed_dt(const void* qkv, const uint8_t* mask, void* out, int chunk, int N, int P, int H,
-                                   int D, float scale, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (a8)  flow_warp / bilinear_sample  (GEO:41-72): bilinear, zeros padding, align_corners=True.
@@ -283,35 +240,29 @@ int fresco_max_pool(const float* x, float* out, int BC, int H, int W, int k, voi
  *   (gmflow/transformer.py:356-372: v = flow, Dv = 2).
  *   q (B,Lq,D), k (B,Lk,D), v (B,Lk,Dv), out (B,Lq,Dv): fp32 row-major, dense.  D in {32, 64, 128}, Dv <= 128.
  *   fp32-class accuracy on the fp16 matrix pipe: operands split into fp16 pieces (33-bit logits, 22-bit P V products),
- *   fp32 softmax (the flows feed integer decisions downstream).  |q scale|, |k|, |v| < 1000. */
-int fresco_attn_f32(const float* q, const float* k, const float* v, float* out, int B, int Lq, int Lk, int D, int Dv,
-                    float scale, void* stream);
-
-/* The same with a caller-provided workspace (fresco_attn_f32_workspace_bytes(B, Lk, D, Dv) bytes, 16-byte aligned): K and
- * V are converted to the kernel's split-fp16 LDS images ONCE per launch instead of once per 128-query workgroup (what
- * pays as soon as two workgroups share a key set: Lq >= 256).  Same results as fresco_attn_f32, bit for bit. */
-size_t fresco_attn_f32_workspace_bytes(int B, int Lk, int D, int Dv);
-int fresco_attn_f32_ws(const float* q, const float* k, const float* v, float* out, void* workspace,
-                       size_t workspace_bytes, int B, int Lq, int Lk, int D, int Dv, float scale, void* stream);
-
-/* The same WITHOUT the range limit: a range pass over q, k, v raises *flag (one int32 of device memory the caller lends
- * for the call) when any operand is beyond what the fp16 pieces can hold (|q scale log2 e|, |k|, |v| >= 1000) or not
- * finite, and an exact-fp32 MFMA kernel behind the split-fp16 one then recomputes the launch (it returns at once when the
- * flag is clear: in range the results are fresco_attn_f32's bit for bit).  workspace may be NULL (per-workgroup staging
- * form).  This is the entry fresco_amd.ops.attention_f32 -- and with it the flow network -- uses. */
-int fresco_attn_f32_guarded(const float* q, const float* k, const float* v, float* out, void* workspace,
-                            size_t workspace_bytes, int* flag, int B, int Lq, int Lk, int D, int Dv, float scale,
-                            void* stream);
-
-/* The guarded workspace form without the separate range pass and flag memset (round 6): the k / v range test runs inside the
- * split pass, the q test inside the attention kernel's prologue.  zero_flag: one int32 of device memory that the CALLER
- * guarantees to be ZERO in stream order when the call is issued, and untouched by anyone else until the call's kernels are
- * done (fresco_amd.ops hands out the words of a zero-filled pool, each once).  workspace as fresco_attn_f32_ws (not NULL).
- * Results: fresco_attn_f32_guarded's with a workspace, bit for bit, in range and out of range.  fresco_amd.ops.attention_f32
- * uses it whenever it takes the workspace form (Lq >= 256: every attention call of the flow network). */
-int fresco_attn_f32_guarded_ws(const float* q, const float* k, const float* v, float* out, void* workspace,
-                               size_t workspace_bytes, int* zero_flag, int B, int Lq, int Lk, int D, int Dv, float scale,
-                               void* stream);
+ *   fp32 softmax (the flows feed integer decisions downstream).
+ *   workspace: NULL -- every 128-query workgroup stages and splits its own K / V tiles -- or
+ *     fresco_attn_f32_workspace_bytes(B, Lk, D, Dv) bytes, 16-byte aligned: K and V are converted to the kernel's split-fp16
+ *     LDS images ONCE per launch instead of once per workgroup (what pays as soon as two workgroups share a key set:
+ *     Lq >= 256).  Same results either way, bit for bit.
+ *   flag: NULL -- the operands must stay in the range the fp16 pieces can hold, |q scale log2 e|, |k|, |v| < 1000 (the
+ *     caller's duty; nothing is checked on the device) -- or one int32 of device memory the caller lends for the call, which
+ *     lifts the limit: *flag is raised when any operand is beyond that range or not finite, and an exact-fp32 MFMA kernel
+ *     behind the split-fp16 one then recomputes the launch (it returns at once when the flag is clear: in range the results
+ *     are those without a flag, bit for bit).  How the flag gets raised:
+ *       flag_is_zero == 0: the call clears *flag and runs a range pass over q, k, v in front of the attention;
+ *       flag_is_zero != 0: no memset, no range pass -- the k / v test runs inside the split pass, the q test in the
+ *         attention kernel's prologue.  The CALLER guarantees *flag to be ZERO in stream order when the call is issued, and
+ *         untouched by anyone else until the call's kernels are done (fresco_amd.ops hands out the words of a zero-filled
+ *         pool, each once).  Only the workspace kernels carry the in-kernel test: workspace == NULL is FRESCO_EINVAL, and
+ *         so is flag == NULL.  Results: those of flag_is_zero == 0 with a workspace, bit for bit, in range and out of range.
+ *   fresco_amd.ops.attention_f32 -- and with it the flow network -- always passes a flag: workspace + flag_is_zero for
+ *   Lq >= 256 (every attention call of the flow network), neither below.
+ *   Every argument check answers before any HIP call: FRESCO_EINVAL (null q / k / v / out, non-positive size or scale, the
+ *   flag_is_zero rule), FRESCO_EUNSUPPORTED (B > 65535, a (D, Dv) outside the list), FRESCO_EWORKSPACE. */
+size_t fresco_attn_f32_workspace_bytes(int B, int Lk, int D, int Dv); /* 0 for an unsupported (D, Dv) */
+int fresco_attn_f32(const float* q, const float* k, const float* v, float* out, void* workspace, size_t workspace_bytes,
+                    int* flag, int flag_is_zero, int B, int Lq, int Lk, int D, int Dv, float scale, void* stream);
 
 /* ---- the flow network's dense layers (f3): GMFlow's CNN encoder, transformer projections / FFN / LayerNorms, upsampler head
  * (gmflow/backbone.py:7-117, transformer.py:111-237, gmflow.py:44-90).  fp32 in, fp32 out, fp32-class accuracy on the fp16
@@ -434,14 +385,14 @@ int fresco_chan_mean_std(const void* x, float* mean, float* stdv, int rows, int 
  *   iters Adam steps (lr, beta1, beta2, eps as torch.optim.Adam); no autograd: analytic
  *   gradients.  The adjoint of the bilinear warp is evaluated as a deterministic gather over a
  *   per-call CSR of the tap matrix (no atomics), so results are run-to-run reproducible.
- *   fresco_opt_run keeps everything on `stream` and touches no state outside its arguments.
- *   fresco_opt_run_ctx(ctx, ...) -- the same call with a context (fresco_ctx_create / _destroy: a side stream + events,
- *   created on first use on the device current then, owned by the CALLER; round 6: the library keeps no process-wide
- *   stream table any more) -- runs, with chunk == 2 and N * h * w >= 2048, the two CFG halves (independent problems) as two
- *   pipelines: one on `stream`, one on the context's side stream, forked from and joined back into `stream` by events
- *   inside the call -- the caller sees ordinary stream order (FRESCO_OPT_SPLIT=0 keeps everything on `stream`; the
- *   results are bit-identical either way).  One call at a time per context (a second concurrent call on the same context,
- *   or a call on another device than the context's, runs on one stream); use one context per host thread / stream.
+ *   ctx == NULL: fresco_opt_run keeps everything on `stream` and touches no state outside its arguments.
+ *   ctx = a context (fresco_ctx_create / _destroy: a side stream + events, created on first use on the device current
+ *   then, owned by the CALLER; the library keeps no process-wide stream table): with chunk == 2 and N * h * w >= 2048, the
+ *   two CFG halves (independent problems) run as two pipelines: one on `stream`, one on the context's side stream, forked
+ *   from and joined back into `stream` by events inside the call -- the caller sees ordinary stream order
+ *   (FRESCO_OPT_SPLIT=0 keeps everything on `stream`; the results are bit-identical either way).  One call at a time per
+ *   context (a second concurrent call on the same context, or a call on another device than the context's, runs on one
+ *   stream); use one context per host thread / stream.
  *
  *   fresco_opt_loss_grad evaluates the closure once: grad (same shape as cs) and, if loss != NULL,
  *   loss[0] = temporal term, loss[1] = spatial term (device floats).  Test / debugging entry.
@@ -449,21 +400,14 @@ int fresco_chan_mean_std(const void* x, float* mean, float* stdv, int rows, int 
 size_t fresco_opt_workspace_bytes(int chunk, int N, int C, int h, int w, int has_temporal,
                                   int has_target);
 
-int fresco_opt_run(float* cs, const float* fwd_flow, const float* bwd_flow,
+int fresco_ctx_create(void** ctx);
+int fresco_ctx_destroy(void* ctx); /* waits for the context's stream; FRESCO_EINVAL while a call is using it */
+int fresco_opt_run(void* ctx, float* cs, const float* fwd_flow, const float* bwd_flow,
                    const float* fwd_occ, const float* bwd_occ, const float* target,
                    void* workspace, size_t workspace_bytes,
                    int chunk, int N, int C, int h, int w,
                    float intra_weight, int iters, float lr, float beta1, float beta2, float eps,
                    void* stream);
-
-int fresco_ctx_create(void** ctx);
-int fresco_ctx_destroy(void* ctx); /* waits for the context's stream; FRESCO_EINVAL while a call is using it */
-int fresco_opt_run_ctx(void* ctx, float* cs, const float* fwd_flow, const float* bwd_flow,
-                       const float* fwd_occ, const float* bwd_occ, const float* target,
-                       void* workspace, size_t workspace_bytes,
-                       int chunk, int N, int C, int h, int w,
-                       float intra_weight, int iters, float lr, float beta1, float beta2, float eps,
-                       void* stream);
 
 int fresco_opt_loss_grad(const float* cs, const float* fwd_flow, const float* bwd_flow,
                          const float* fwd_occ, const float* bwd_occ, const float* target,
@@ -477,7 +421,14 @@ int fresco_opt_loss_grad(const float* cs, const float* fwd_flow, const float* bw
  * fwd_flow, bwd_flow : (n_loc+1, 2, h, w), fwd_occ, bwd_occ : (n_loc+1, h, w) -- entry j belongs to the
  * frame pair (f0-1+j, f0+j) mod N_total; both loss terms are normalised by the GLOBAL batch 2*N_total.
  * begin: zero the Adam state, build the warp-adjoint CSRs; step `it` = 1..iters: one Adam iteration.
- * With n_loc = N_total and halos = own last / first frame this reproduces fresco_opt_run. */
+ * With n_loc = N_total and halos = own last / first frame this reproduces fresco_opt_run.
+ * part: the step as one host call (3) or as two, so that the neighbour exchange of the halo frames can run UNDER the
+ * launches that do not read them.  part = 1: normalisation, the residual signs of the interior pairs, Gram and S V
+ * products (halo_l / halo_r are not read and may be NULL); part = 2: the residual signs of the two pairs that touch a halo
+ * frame, then Adam (halos required); part = 3: both, the undivided step.  Part 1 followed by part 2 performs, per element,
+ * exactly the operations of the undivided step: results are identical bit for bit.  Typical loop of a rank:
+ * start the (asynchronous) exchange of the frames Adam(it-1) produced -> part 1 of step it -> wait for the halos ->
+ * part 2 of step it. */
 size_t fresco_opt_sharded_workspace_bytes(int chunk, int n_loc, int C, int h, int w, int has_temporal,
                                           int has_target);
 int fresco_opt_sharded_begin(const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
@@ -489,24 +440,12 @@ int fresco_opt_sharded_step(float* cs, const float* halo_l, const float* halo_r,
                             const float* bwd_occ, const float* target, void* workspace,
                             size_t workspace_bytes, int chunk, int n_loc, int N_total, int C, int h, int w,
                             float intra_weight, int it, float lr, float beta1, float beta2, float eps,
-                            void* stream);
-/* The same step in two host calls, so that the neighbour exchange of the halo frames can run UNDER the launches that do
- * not read them.  part = 1: normalisation, the residual signs of the interior pairs, Gram and S V products (halo_l /
- * halo_r are not read and may be NULL); part = 2: the residual signs of the two pairs that touch a halo frame, then
- * Adam (halos required); part = 3: both = fresco_opt_sharded_step.  Part 1 followed by part 2 performs, per element,
- * exactly the operations of the undivided step: results are identical bit for bit.  Typical loop of a rank:
- * start the (asynchronous) exchange of the frames Adam(it-1) produced -> part 1 of step it -> wait for the halos ->
- * part 2 of step it. */
-int fresco_opt_sharded_step_part(float* cs, const float* halo_l, const float* halo_r,
-                                 const float* fwd_flow, const float* bwd_flow, const float* fwd_occ,
-                                 const float* bwd_occ, const float* target, void* workspace,
-                                 size_t workspace_bytes, int chunk, int n_loc, int N_total, int C, int h, int w,
-                                 float intra_weight, int it, float lr, float beta1, float beta2, float eps,
-                                 int part, void* stream);
+                            int part, void* stream);
 
 /* Gram target of get_intraframe_paras (DH:889-895): T[b] = V V^T, V = rows of x (B,C,h,w)
- * viewed as (B, hw, C) and L2-normalised; fp32 (B,hw,hw).  workspace: B*C*hw + 33*B*hw floats
- * (each block rounded up to 256 bytes). */
+ * viewed as (B, hw, C) and L2-normalised; fp32 (B,hw,hw).  workspace: fresco_gram_target_workspace_bytes(B, C, hw) bytes
+ * (B*C*hw + 33*B*hw floats, each block rounded up to 256 bytes; 0 for a non-positive size). */
+size_t fresco_gram_target_workspace_bytes(int B, int C, int hw);
 int fresco_gram_target(const float* x, float* target, void* workspace, size_t workspace_bytes,
                        int B, int C, int hw, void* stream);
 

@@ -38,22 +38,21 @@ def _buf():
 
 
 def _calls(lib, p, dtype, null):
-    """every new dtype-carrying entry point with valid shapes; `null`: the first operand is NULL"""
+    """every dtype-carrying entry point with valid shapes; `null`: the first operand is NULL"""
     x = None if null else p
     return {
-        "fresco_linear_dt": lambda: lib.fresco_linear_dt(x, 320, p, None, None, None, None, None, p, None, None, 320, 0, 0,
-                                                         1, 4, 320, 320, dtype, None),
-        "fresco_linear_rows_dt": lambda: lib.fresco_linear_rows_dt(x, 320, p, p, None, None, None, None, None, p, None,
-                                                                   None, 320, 0, 0, 1, 4, 320, 320, dtype, None),
-        "fresco_attn_fwd_dt": lambda: lib.fresco_attn_fwd_dt(x, p, p, None, p, p, 1 << 30, 1, 8, 64, 40, 1, 64, 64, 0.158,
-                                                             0.0, 320, 320, dtype, None),
-        "fresco_temporal_attn_dt": lambda: lib.fresco_temporal_attn_dt(x, p, p, p, p, p, 2, 4, 64, 8, 40, 0.03, 320, 320,
-                                                                       320, dtype, None),
+        "fresco_linear": lambda: lib.fresco_linear(x, 320, None, p, None, None, None, None, None, p, None, None, 320, 0, 0,
+                                                   1, 4, 320, 320, dtype, None),
+        "fresco_linear-x_rows": lambda: lib.fresco_linear(x, 320, p, p, None, None, None, None, None, p, None, None, 320, 0,
+                                                          0, 1, 4, 320, 320, dtype, None),
+        "fresco_attn_fwd": lambda: lib.fresco_attn_fwd(x, p, p, None, p, p, 1 << 30, 1, 8, 64, 40, 1, 64, 64, 0.158, 0.0, 320,
+                                                       320, dtype, None),
+        "fresco_temporal_attn": lambda: lib.fresco_temporal_attn(x, p, p, p, p, p, 2, 4, 64, 8, 40, 0.03, 320, 320, 320,
+                                                                 dtype, None),
     }
 
 
-@pytest.mark.parametrize("name", ["fresco_linear_dt", "fresco_linear_rows_dt", "fresco_attn_fwd_dt",
-                                  "fresco_temporal_attn_dt"])
+@pytest.mark.parametrize("name", ["fresco_linear", "fresco_linear-x_rows", "fresco_attn_fwd", "fresco_temporal_attn"])
 def test_new_entry_points_reject_bad_dtype_and_null_without_a_device(lib, name):
     from fresco_amd import _lib
     p, keep = _buf()

@@ -496,7 +496,7 @@ def test_processor_attention_mask_fully_masked_rows(C, heads):
 def test_fused_kv_projection_pack(layer, N, R, masked):
     """Round 6: on cross-frame-only calls the K | V projection of the selected rows runs INSIDE the key pack
     (fresco_attn_fwd_kvproj: K and V never reach HBM).  Against the fp32 oracle at the usual bar, and against the two-launch
-    path (fresco_linear_rows + kv_pack): the fp16 K / V values may differ in the last place (one accumulation chain in
+    path (fresco_linear with x_rows + kv_pack): the fp16 K / V values may differ in the last place (one accumulation chain in
     natural k order vs two chains in permuted order), so the outputs agree to fp16 rounding, not bit for bit.
     masked=False: controller.attn_mask None -> every frame attends to frame 0's HW keys."""
     import fresco_amd

@@ -50,8 +50,8 @@ def test_attention_f32_peaked_logits_and_validation():
 
 
 def test_attention_f32_workspace_form_is_bit_identical():
-    """fresco_attn_f32_ws (K / V split once per launch, operand images by LDS-DMA) runs the arithmetic of fresco_attn_f32 on the
-    same numbers: the results must be equal bit for bit (ragged last key tile, Lq not a multiple of 128, Dv 128 / 2)."""
+    """fresco_attn_f32 with a workspace (K / V split once per launch, operand images by LDS-DMA) runs the arithmetic of the
+    per-workgroup staging form (workspace = NULL, here without a flag) on the same numbers: the results must be equal bit for bit (ragged last key tile, Lq not a multiple of 128, Dv 128 / 2)."""
     import fresco_amd.ops as ops
     from fresco_amd import _lib
     lib = _lib.load()
@@ -62,7 +62,7 @@ def test_attention_f32_workspace_form_is_bit_identical():
         v = torch.randn(B, Lk, Dv, generator=g).to(DEV)
         a = ops.attention_f32(q, k, v, 1.0 / math.sqrt(D))          # Lq >= 256: the workspace form
         b = torch.empty_like(a)
-        rc = lib.fresco_attn_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), b.data_ptr(), B, Lq, Lk, D, Dv,
+        rc = lib.fresco_attn_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), b.data_ptr(), None, 0, None, 0, B, Lq, Lk, D, Dv,
                                  1.0 / math.sqrt(D), None)
         assert rc == 0
         torch.cuda.synchronize()
@@ -98,4 +98,57 @@ def test_attention_f32_operands_beyond_fp16_range(what, Lq):
     ref = _ref(q, k, v, scale)
     assert bool(torch.isfinite(out).all())
     err = float((out.cpu().double() - ref).abs().max())
+    assert err < 2e-5 * max(1.0, float(ref.abs().max())), err
+
+
+def test_attention_f32_four_modes_are_one_computation():
+    """fresco_attn_f32's (workspace x flag) modes: per-workgroup staging or a workspace; no flag, or a flag the call clears
+    and a range pass raises (workspace or not), or a zero word and the in-kernel range tests (workspace only).  In range all
+    four are equal bit for bit; out of range (v = 2000 x + 5000) the two guarded workspace-or-not forms and the zero-word form
+    agree bit for bit, are finite and meet the fp64 reference at the bar of test_attention_f32_operands_beyond_fp16_range.
+    Lq = 300: not a multiple of 128, >= 256; Lk = 70: a ragged last 32-key tile; Dv = 5 < 32."""
+    from fresco_amd import _lib
+    lib = _lib.load()
+    B, Lq, Lk, D, Dv = 2, 300, 70, 32, 5
+    scale = 1.0 / math.sqrt(D)
+    g = synth.gen(31)
+    q = (torch.randn(B, Lq, D, generator=g) * 1.5).to(DEV)
+    k = (torch.randn(B, Lk, D, generator=g) * 1.5).to(DEV)
+    v = (torch.randn(B, Lk, Dv, generator=g) * 1.5).to(DEV)
+    need = lib.fresco_attn_f32_workspace_bytes(B, Lk, D, Dv)
+    assert need > 0
+    st = torch.cuda.current_stream().cuda_stream
+
+    def run(v, with_ws, flag_mode):  # flag_mode: None, "cleared" (by the call), "zero" (by the caller)
+        out = torch.empty(B, Lq, Dv, dtype=torch.float32, device=DEV)
+        ws = torch.empty(need, dtype=torch.uint8, device=DEV) if with_ws else None
+        flag = None
+        if flag_mode == "cleared":
+            flag = torch.full((1,), 7, dtype=torch.int32, device=DEV)
+        elif flag_mode == "zero":
+            flag = torch.zeros(1, dtype=torch.int32, device=DEV)
+        rc = lib.fresco_attn_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), ws.data_ptr() if with_ws else None,
+                                 need if with_ws else 0, flag.data_ptr() if flag is not None else None,
+                                 1 if flag_mode == "zero" else 0, B, Lq, Lk, D, Dv, scale, st)
+        assert rc == 0, (with_ws, flag_mode, rc)
+        torch.cuda.synchronize()
+        return out, flag
+
+    plain, _ = run(v, False, None)
+    for with_ws, mode in ((True, None), (False, "cleared"), (True, "cleared"), (True, "zero")):
+        out, flag = run(v, with_ws, mode)
+        assert torch.equal(out, plain), (with_ws, mode, float((out - plain).abs().max()))
+        assert flag is None or int(flag) == 0
+    ref = _ref(q.cpu(), k.cpu(), v.cpu(), scale)
+    assert float((plain.cpu().double() - ref).abs().max()) < 2e-5 * max(1.0, float(ref.abs().max()))
+
+    big = v * 2000.0 + 5000.0
+    a, fa = run(big, False, "cleared")
+    b, fb = run(big, True, "cleared")
+    c, fc = run(big, True, "zero")
+    assert int(fa) == 1 and int(fb) == 1 and int(fc) == 1
+    assert torch.equal(a, b) and torch.equal(b, c)
+    assert bool(torch.isfinite(c).all())
+    ref = _ref(q.cpu(), k.cpu(), big.cpu(), scale)
+    err = float((c.cpu().double() - ref).abs().max())
     assert err < 2e-5 * max(1.0, float(ref.abs().max())), err

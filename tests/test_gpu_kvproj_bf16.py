@@ -1,4 +1,4 @@
-"""The fused K | V projection + key pack in bf16 (fresco_attn_fwd_kvproj_dt with FRESCO_BF16) and its use by the processor
+"""The fused K | V projection + key pack in bf16 (fresco_attn_fwd_kvproj with FRESCO_BF16) and its use by the processor
 under FRESCOAttnProcessor2_0.fuse_kv_pack_bf16.
 
 Kernel level: ops.attention_kvproj on bf16 tensors at key counts around every edge of the tiling (as

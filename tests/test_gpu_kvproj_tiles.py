@@ -1,7 +1,7 @@
 """The fused K | V projection + key pack (fresco_attn_fwd_kvproj) with a RANGE of key tiles per workgroup, and its use on
 every layer call that runs the cross-frame pass.
 
-Kernel level: ops.attention_kvproj against the two-launch path (fresco_linear_rows, then kv_pack inside ops.attention) and
+Kernel level: ops.attention_kvproj against the two-launch path (fresco_linear with x_rows, then kv_pack inside ops.attention) and
 against an fp32 torch evaluation, at key counts around every edge of the tiling: one partial tile, the exact 64-key tile
 edge, the first tile of a second range, a range shorter than the others, a last range that is short AND ends in a partial
 tile.  T, the tiles per workgroup, is read from the kernel source so that the edges move with it.

@@ -151,7 +151,7 @@ def test_processor_fuses_only_plain_linears_and_tracks_weight_updates():
 
 
 def test_linear_gathered_rows():
-    """fresco_linear_rows: output row m = projection of input row x_rows[m] (the K / V projection of the selected
+    """fresco_linear with x_rows: output row m = projection of input row x_rows[m] (the K / V projection of the selected
     cross-frame tokens); out-of-range tables are refused."""
     import fresco_amd.ops as ops
     g = torch.Generator().manual_seed(3)

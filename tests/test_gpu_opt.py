@@ -314,7 +314,7 @@ def test_cooperative_gram_staging_is_bit_identical(N, C, h, w, monkeypatch):
 
 def test_opt_context_owns_the_side_stream():
     """Round 6 (no global state): the two-pipeline form of the Adam loop runs on a side stream that belongs to a
-    caller-owned context (fresco_ctx_create / fresco_opt_run_ctx); the context-free entry fresco_opt_run keeps everything on
+    caller-owned context (fresco_ctx_create, handed to fresco_opt_run); fresco_opt_run without one keeps everything on
     the caller's stream.  Same bits either way, and two host threads with a context each run side by side."""
     import threading
     import fresco_amd.ops as ops
@@ -331,7 +331,7 @@ def test_opt_context_owns_the_side_stream():
     b = x.clone()
     nbytes = lib.fresco_opt_workspace_bytes(2, 4, 128, 32, 32, 1, 1)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
-    rc = lib.fresco_opt_run(b.data_ptr(), prep[0].data_ptr(), prep[1].data_ptr(), prep[2].data_ptr(), prep[3].data_ptr(),
+    rc = lib.fresco_opt_run(None, b.data_ptr(), prep[0].data_ptr(), prep[1].data_ptr(), prep[2].data_ptr(), prep[3].data_ptr(),
                             tgt.data_ptr(), ws.data_ptr(), ws.numel(), 2, 4, 128, 32, 32, 100.0, 6, 0.2, 0.9, 0.999, 1e-8,
                             torch.cuda.current_stream().cuda_stream)
     assert rc == 0

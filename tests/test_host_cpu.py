@@ -141,23 +141,24 @@ def test_capi_argument_validation_without_gpu():
     lib = _lib.load()
     p = 4096  # fake, aligned, never touched
     EINVAL, EUNSUP, EWS = -1, -2, -3
+    F16 = _lib.F16
     ws = lib.fresco_attn_workspace_bytes(2, 8, 100, 40)
     ok_args = dict(B=4, H=8, Lq=64, D=40, G=2, M=100, rows=200)
 
     def attn(q=p, k=p, v=p, out=p, w=p, wsb=ws, B=4, H=8, Lq=64, D=40, G=2, M=100, rows=200, scale=0.1):
-        return lib.fresco_attn_fwd(q, k, v, None, out, w, wsb, B, H, Lq, D, G, M, rows, scale, 0.0, None)
+        return lib.fresco_attn_fwd(q, k, v, None, out, w, wsb, B, H, Lq, D, G, M, rows, scale, 0.0, H * D, H * D, F16, None)
 
     assert attn(q=None) == EINVAL and attn(out=None) == EINVAL and attn(w=None) == EINVAL
     assert attn(B=5) == EINVAL            # batch not divisible by the number of key groups
     assert attn(scale=0.0) == EINVAL and attn(M=0) == EINVAL and attn(Lq=0) == EINVAL
     assert attn(wsb=ws - 1) == EWS
     assert attn(D=24, wsb=1 << 30) == EUNSUP    # head dims are instantiated for 8,16,32,40,64,80,96,128
-    assert lib.fresco_attn_fwd_ld(p, p, p, None, p, p, ws, 4, 8, 64, 40, 2, 100, 200, 0.1, 0.0, 300, 320, None) == EINVAL
+    assert lib.fresco_attn_fwd(p, p, p, None, p, p, ws, 4, 8, 64, 40, 2, 100, 200, 0.1, 0.0, 300, 320, F16, None) == EINVAL
     # temporal pass: a trajectory's rows beyond the LDS, head dim without an instantiation, bad sharding
-    assert lib.fresco_temporal_attn(p, p, p, p, p, p, 2, 2000, 64, 8, 40, 0.1, None) == EUNSUP
-    assert lib.fresco_temporal_attn(p, p, p, p, p, p, 2, 8, 64, 8, 24, 0.1, None) == EUNSUP
-    assert lib.fresco_temporal_attn(p, p, p, None, p, p, 2, 8, 64, 8, 40, 0.1, None) == EINVAL
-    assert lib.fresco_temporal_attn_packed(None, p, p, 2, 8, 64, 8, 40, 0.1, None) == EINVAL
+    assert lib.fresco_temporal_attn(p, p, p, p, p, p, 2, 2000, 64, 8, 40, 0.1, 320, 320, 320, F16, None) == EUNSUP
+    assert lib.fresco_temporal_attn(p, p, p, p, p, p, 2, 8, 64, 8, 24, 0.1, 192, 192, 192, F16, None) == EUNSUP
+    assert lib.fresco_temporal_attn(p, p, p, None, p, p, 2, 8, 64, 8, 40, 0.1, 320, 320, 320, F16, None) == EINVAL
+    assert lib.fresco_temporal_attn_packed(None, p, p, 2, 8, 64, 8, 40, 0.1, F16, None) == EINVAL
     assert lib.fresco_temporal_pack(p, p, p, p, p, 2, 4, 0, 64, 320, 3, 320, 320, 320, None) == EINVAL  # 64 % 3
     assert lib.fresco_temporal_unpack(p, p, None, 2, 4, 0, 64, 320, 2, None) == EINVAL
     # warp chain needs two frames; dilate needs an odd kernel; AdaIN needs >= 2 elements per row and a known dtype
@@ -169,7 +170,7 @@ def test_capi_argument_validation_without_gpu():
     # feature optimisation: flows without occlusions, no active term, workspace too small
     need = lib.fresco_opt_workspace_bytes(2, 4, 16, 8, 8, 1, 1)
     run = lambda fwd_flow=p, bwd_flow=p, fwd_occ=p, bwd_occ=p, target=p, wsb=need, iw=100.0: lib.fresco_opt_run(
-        p, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, p, wsb, 2, 4, 16, 8, 8, iw, 3, 0.2, 0.9, 0.999, 1e-8, None)
+        None, p, fwd_flow, bwd_flow, fwd_occ, bwd_occ, target, p, wsb, 2, 4, 16, 8, 8, iw, 3, 0.2, 0.9, 0.999, 1e-8, None)
     assert run(fwd_occ=None) == EINVAL
     assert run(fwd_flow=None, bwd_flow=None, fwd_occ=None, bwd_occ=None, target=None) == EINVAL
     assert run(fwd_flow=None, bwd_flow=None, fwd_occ=None, bwd_occ=None, iw=0.0) == EINVAL

@@ -1,4 +1,4 @@
-"""The element-type entry points of the fused K | V projection-pack and of the packed temporal pass at the C ABI, without a
+"""The entry points of the fused K | V projection-pack and of the packed temporal pass at the C ABI, without a
 GPU: declared, bound, and every argument check answers before any HIP call."""
 import ctypes
 import os
@@ -8,7 +8,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, EUNSUPPORTED = -1, -2
-NAMES = ["fresco_attn_fwd_kvproj_dt", "fresco_temporal_attn_packed_dt"]
+NAMES = ["fresco_attn_fwd_kvproj", "fresco_temporal_attn_packed"]
 
 
 @pytest.fixture(scope="module")
@@ -37,10 +37,9 @@ def _calls(lib, p, dtype, null, hdk=(8, 40, 320)):
     x = None if null else p
     H, D, K = hdk
     return {
-        "fresco_attn_fwd_kvproj_dt": lambda: lib.fresco_attn_fwd_kvproj_dt(x, p, K, p, p, p, p, p, 1 << 30, 2, H, 64, D, 2, 64,
-                                                                           K, 0.158, H * D, dtype, None),
-        "fresco_temporal_attn_packed_dt": lambda: lib.fresco_temporal_attn_packed_dt(x, p, p, 2, 4, 64, 8, 40, 0.03, dtype,
-                                                                                     None),
+        "fresco_attn_fwd_kvproj": lambda: lib.fresco_attn_fwd_kvproj(x, p, K, p, p, p, p, p, 1 << 30, 2, H, 64, D, 2, 64, K,
+                                                                     0.158, H * D, dtype, None),
+        "fresco_temporal_attn_packed": lambda: lib.fresco_temporal_attn_packed(x, p, p, 2, 4, 64, 8, 40, 0.03, dtype, None),
     }
 
 
@@ -59,10 +58,10 @@ def test_kvproj_dt_unsupported_shape_without_a_device(lib):
     from fresco_amd import _lib
     p, keep = _buf()
     for dt in (_lib.F16, _lib.BF16):
-        assert _calls(lib, p, dt, False, hdk=(8, 64, 512))["fresco_attn_fwd_kvproj_dt"]() == EUNSUPPORTED
+        assert _calls(lib, p, dt, False, hdk=(8, 64, 512))["fresco_attn_fwd_kvproj"]() == EUNSUPPORTED
     del keep
 
 
-def test_version_is_0_4_0(lib):
-    """(0.3.0 added the bf16 K | V pack entry points; 0.4.0, fresco_linear_plan)"""
-    assert "0.4.0" in lib.fresco_version().decode()
+def test_version_is_0_5_0(lib):
+    """(0.3.0 added the bf16 K | V pack entry points; 0.4.0, fresco_linear_plan; 0.5.0 left one entry point per operation)"""
+    assert "0.5.0" in lib.fresco_version().decode()

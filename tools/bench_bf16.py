@@ -2,8 +2,8 @@
 L3 = up_blocks.3 (16, 4096, 320) and L2 = up_blocks.2 (16, 1024, 640), Bernoulli(0.1) occlusions, modes cf / cf_temporal /
 full.  Variants, per shape and mode:
   (a) bf16 native   : bf16 module and activations, FRESCOAttnProcessor2_0.native_bf16 = True (the bf16 kernels), the default
-                      two-launch K | V path (fresco_linear_rows + kv_pack)
-  (a') bf16 fused   : the same with fuse_kv_pack_bf16 = True (K | V projected inside the key pack, fresco_attn_fwd_kvproj_dt)
+                      two-launch K | V path (fresco_linear with x_rows + kv_pack)
+  (a') bf16 fused   : the same with fuse_kv_pack_bf16 = True (K | V projected inside the key pack, fresco_attn_fwd_kvproj)
   (b) bf16 rounding : the same with native_bf16 = False (library GEMMs, q / k / v rounded to fp16, cast back)
   (c) fp16          : fp16 module and activations (the headline path, fused K | V pack included)
   (d) torch bf16    : oracle/torch_path.processor_call on bf16 cuda tensors = the reference's op sequence
