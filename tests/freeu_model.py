@@ -21,8 +21,19 @@ FOURIER_SCALES = [0.0, 0.2, 0.9]
 # fp32 records of the reference are kept for planes up to 32 x 32 (the float64 ones for every shape)
 FOURIER_F32_MAX_HW = 1024
 
+# Shapes past the golden file, held to fourier_model alone (test_freeu_cpu.py pins it to a float64 torch.fft restatement of
+# the reference there).  The filter kernels switch at 1024 and 4096 elements per plane and between 16-byte packs and single
+# elements: one workgroup per plane with single elements (1155 elements, odd); single elements for fp16 / bf16 but packs
+# for fp32 (1156 = 4 * 289); packs with a partly filled last row of packs (4000); the two-pass kernel with single elements
+# (4355, odd); the first plane size past 4096 (4160)
+FOURIER_TILED_SHAPES = [(1, 2, 33, 35), (2, 3, 34, 34), (1, 2, 40, 100), (1, 1, 65, 67), (1, 1, 64, 65)]
+
 BACKBONE_CASES = [(2, 8, 4, 4, 4), (1, 6, 3, 5, 7), (3, 1280, 640, 8, 8), (2, 640, 320, 32, 32)]  # B, C, n_scaled, H, W
 BACKBONE_BS = [1.0, 1.2, 1.5]
+# Planes of more than one pixel tile (a tile is 2048 elements for fp16 / bf16, 1024 for fp32, 256 on the single-element
+# path): the last site of a 512 x 512 run (64 x 64: 2 / 4 tiles); 2304 elements, a nearly empty tail tile; channel splits of
+# 3 channels with a 1-channel last split; odd planes of 323 (2 tiles) and 1023 (4 tiles) single elements
+BACKBONE_TILED_CASES = [(2, 24, 12, 64, 64), (1, 12, 6, 48, 48), (1, 100, 50, 48, 48), (1, 6, 3, 17, 19), (3, 40, 20, 33, 31)]
 
 SKIP_CH = 5
 # name -> (hidden channels, output channels of each resnet, upsampler)

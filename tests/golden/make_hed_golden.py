@@ -1,7 +1,9 @@
-"""Generate tests/golden/hed_golden.npz: records of the UNMODIFIED reference src/ControlNet/annotator/hed/__init__.py on
+"""Generate tests/golden/hed_golden.npz (hed_model.CASES) and tests/golden/hed_wide_golden.npz (hed_model.WIDE_CASES): records of the UNMODIFIED reference src/ControlNet/annotator/hed/__init__.py on
 the CPU.
 
-Run (build container, where the reference tree is present):  python tests/golden/make_hed_golden.py
+Run (build container, where the reference tree is present):  python tests/golden/make_hed_golden.py [file name ...]
+(no argument: both files; `hed_wide_golden.npz`: that one alone -- an .npz carries the time it was written, so a file that is
+not named keeps its bytes).
 
 The reference module imports cv2 (absent) and annotator.util; stubs for exactly what it touches are registered here:
 `cv2.resize` / `cv2.INTER_LINEAR` (hed_model.resize_standin, see its docstring for what the stand-in is) and
@@ -9,7 +11,7 @@ The reference module imports cv2 (absent) and annotator.util; stubs for exactly 
 bypassed with object.__new__, the network gets the stand-in weights of tests/hed_model.py, and Tensor.cuda is the identity
 while the detector runs.
 
-Recorded per case of hed_model.CASES and frame f < hed_model.GOLDEN_FRAMES[case]:
+Recorded per case and frame f < hed_model.GOLDEN_FRAMES[case]:
   *_p{1..5}_f32   the five projections of ControlNetHED_Apache2 in float32
   *_p{1..5}_d64   (the projections of the same network run in float64) - (the float32 record), as float32
   *_logit_f32     the float32 mean of the five resized maps inside HEDdetector.__call__ (recomputed the same way; the uint8
@@ -32,7 +34,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 import hed_model as M  # noqa: E402
 
 REF = "/root/reference/src/ControlNet/annotator/hed/__init__.py"
-OUT = os.path.join(HERE, "hed_golden.npz")
+SETS = dict(zip(M.GOLDEN_FILES, (M.CASES, M.WIDE_CASES)))
 
 
 def load_reference():
@@ -52,8 +54,13 @@ def load_reference():
     return mod
 
 
-def main():
+def main(names):
     ref = load_reference()
+    for name in names:
+        record(ref, SETS[name], os.path.join(HERE, name))
+
+
+def record(ref, cases, path):
     net = ref.ControlNetHED_Apache2().float().eval()
     net.load_state_dict(M.standin_state_dict())
     net64 = copy.deepcopy(net).double()  # the same weight VALUES: the distance between the runs is arithmetic alone
@@ -67,7 +74,7 @@ def main():
            "weights_sha256": np.array(M.weights_digest())}
     torch.Tensor.cuda, saved = (lambda self, *a, **k: self), torch.Tensor.cuda
     try:
-        for case in M.CASES:
+        for case in cases:
             fr = M.frames(case)
             out[M.case_key(case) + "_sha256"] = np.array(M.digest(fr))
             n, H, W = case
@@ -99,9 +106,9 @@ def main():
         torch.Tensor.cuda = saved
         for h in hooks:
             h.remove()
-    np.savez_compressed(OUT, **out)
-    print("wrote %s (%d bytes, %d arrays)" % (OUT, os.path.getsize(OUT), len(out)))
+    np.savez_compressed(path, **out)
+    print("wrote %s (%d bytes, %d arrays)" % (path, os.path.getsize(path), len(out)))
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:] or list(M.GOLDEN_FILES))

@@ -28,12 +28,26 @@ import torch.nn.functional as F
 # pooling down to 6 x 5; pooling that floors (9 -> 4, 11 -> 5) with resize scales that are no powers of two
 CASES = [(2, 64, 64), (1, 64, 128), (2, 96, 80), (1, 72, 88)]
 # frames of each case whose reference records are kept in the golden file (the others are covered by the batch tests)
-GOLDEN_FRAMES = {(2, 64, 64): 2, (1, 64, 128): 1, (2, 96, 80): 1, (1, 72, 88): 1}
+GOLDEN_FRAMES = {(2, 64, 64): 2, (1, 64, 128): 1, (2, 96, 80): 1, (1, 72, 88): 1, (1, 128, 128): 1}
+# recorded in a file of its own (tests/golden/hed_wide_golden.npz): levels of 128, 64, 32, 16 and 8 pixels, so blocks 1 to 4
+# run their convolutions in the window-in-LDS form (maps of whole 16 x 16 patches, up to 512 channels) and block 5 in the
+# im2col form -- the CASES above reach that form on 16 x 16 maps of at most 256 channels
+WIDE_CASES = [(1, 128, 128)]
+GOLDEN_FILES = ("hed_golden.npz", "hed_wide_golden.npz")  # under tests/golden: CASES, WIDE_CASES
 BLOCKS = ((3, 64, 2), (64, 128, 2), (128, 256, 3), (256, 512, 3), (512, 512, 3))  # cin, cout, convolutions
 NORM = (123.7, 116.3, 103.5)
 CONV_GAIN, PROJ_GAIN, BIAS_STD, NOISE = 0.9, 0.03, 0.1, 0.08
 GUARD = 0.02   # |255 sigmoid(logit) - nearest integer| below which a uint8 value may differ by one
 GUARD_CAP = 0.06  # share of a case's pixels that may lie in the guard band
+
+
+def load_golden(golden_dir):
+    """the records of CASES and WIDE_CASES as one dict (the entries the two files share are equal)"""
+    import os
+    gold = {}
+    for name in GOLDEN_FILES:
+        gold.update(np.load(os.path.join(golden_dir, name)))
+    return gold
 
 
 def case_key(case):

@@ -50,6 +50,29 @@ def test_closed_form_matches_the_reference_filter(freeu_golden, shape):
     assert np.array_equal(M.fourier_model(x, 1.0), x)
 
 
+def _fft_filter64(x, scale):
+    """free_lunch_utils.py:25-52 with threshold = 1 restated on float64 tensors (the reference itself would cast a plane
+    whose sides are not powers of two to float32 first); the mask holds `scale` in fp32, as the reference's does"""
+    xf = torch.fft.fftshift(torch.fft.fftn(torch.from_numpy(x), dim=(-2, -1)), dim=(-2, -1))
+    H, W = x.shape[2:]
+    mask = torch.ones(x.shape, dtype=torch.float32)
+    mask[..., H // 2 - 1:H // 2 + 1, W // 2 - 1:W // 2 + 1] = scale
+    xf = torch.fft.ifftshift(xf * mask.double(), dim=(-2, -1))
+    return torch.fft.ifftn(xf, dim=(-2, -1)).real.numpy()
+
+
+@pytest.mark.parametrize("shape", M.FOURIER_TILED_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_closed_form_matches_a_float64_fft_past_the_golden_shapes(shape):
+    """the shapes the GPU tests hold to fourier_model alone: 1e-12 max|x|, the bar of the golden's float64 records"""
+    x = M.fourier_input(shape)
+    assert np.array_equal(x.astype(np.float16).astype(np.float64), x)
+    assert np.array_equal(torch.from_numpy(x).bfloat16().double().numpy(), x)
+    for s in M.FOURIER_SCALES + [1.0]:
+        err = np.abs(M.fourier_model(x, s) - _fft_filter64(x, s)).max()
+        print("%s s=%g: |model - fft64| = %.3g" % (shape, s, err))
+        assert err <= 1e-12 * np.abs(x).max(), (shape, s, err)
+
+
 @pytest.mark.parametrize("size", M.BLOCK_SIZES, ids=lambda s: "x".join(map(str, s)))
 @pytest.mark.parametrize("name", list(M.BLOCK_CONFIGS))
 def test_model_blocks_match_the_reference_forwards(freeu_golden, name, size):
@@ -73,7 +96,7 @@ def test_model_blocks_match_the_reference_forwards(freeu_golden, name, size):
 
 
 def test_backbone_inputs_bound_the_cancellation():
-    for case in M.BACKBONE_CASES:
+    for case in M.BACKBONE_CASES + M.BACKBONE_TILED_CASES:
         x = M.backbone_input(case)
         assert M.mean_map_condition(x), case
         m = x.mean(axis=1)

@@ -310,6 +310,17 @@ _, as_ = ops.fn_prep(a.to(dev))
 _, bs = ops.fn_prep(b.to(dev), scale=ops.FN_W_SCALE)
 lin, lsp = ops.fn_gemm(as_, bs, N, K, act=2, want_split=True)
 res["lin"], res["lin_hi"], res["lin_lo"] = lin.cpu(), lsp[0].cpu(), lsp[1].cpu()
+# ... and the HED detector's widest convolution, 512 -> 512 channels on 16 x 16 maps: 16 channel chunks in the window form,
+# four column blocks over nine row blocks (the XCD-aware order's main branch and its tail)
+n, c = 9, 512
+x = torch.randn(n * 256, c, generator=g)
+w = torch.randn(c, 9 * c, generator=g) * 0.01
+_, xs = ops.fn_prep(x.to(dev))
+_, ws = ops.fn_prep(w.to(dev), scale=ops.FN_W_SCALE)
+out, sp = ops.fn_gemm(xs, ws, c, 9 * c, conv=(n, 16, 16, 3, 3, 1, 1), want_split=True)
+res["wide"], res["wide_hi"], res["wide_lo"] = out.cpu(), sp[0].cpu(), sp[1].cpu()
+res["wide_sum_abs"] = torch.nn.functional.conv2d(x.abs().double().view(n, 16, 16, c).permute(0, 3, 1, 2),
+                                                 w.abs().double().view(c, 3, 3, c).permute(0, 3, 1, 2), padding=1).max()
 torch.save(res, sys.argv[2])
 """
 
@@ -343,3 +354,10 @@ def test_fn_gemm_forms_agree(tmp_path):
     for o in (d, q):
         rec = (o["conv_hi"].float() + o["conv_lo"].float()) / ops.FN_A_SCALE
         assert float((rec - o["conv"]).abs().max()) <= 2 ** -21 * scale + 1e-7
+    # the 512-channel convolution: each form is within the product bar of the exact result, so within twice that of the other
+    dist = float((d["wide"] - q["wide"]).abs().max())
+    print("512 -> 512: window form vs im2col form %.3g, bar %.3g" % (dist, 2 * _bar(d["wide_sum_abs"])))
+    assert dist < 2 * _bar(d["wide_sum_abs"]) and not torch.equal(d["wide"], q["wide"])
+    for o in (d, q):
+        rec = (o["wide_hi"].float() + o["wide_lo"].float()) / ops.FN_A_SCALE
+        assert float((rec - o["wide"]).abs().max()) <= 2 ** -21 * float(o["wide"].abs().max()) + 1e-7

@@ -91,6 +91,113 @@ def test_fourier_filter_writes_only_its_slices(shape, dtype_name):
     assert torch.equal(ops.freeu_fourier(xt, 0.2), ops.freeu_fourier(xt.contiguous(), 0.2))
 
 
+_fourier_refs = {}
+
+
+def _fourier_ref(shape, s):
+    """fourier_model in float64, computed once per (shape, scale) and shared by the dtypes"""
+    if (shape, s) not in _fourier_refs:
+        _fourier_refs[shape, s] = M.fourier_model(M.fourier_input(shape), s)
+    return _fourier_refs[shape, s]
+
+
+@pytest.mark.parametrize("dtype_name", list(DTYPES))
+@pytest.mark.parametrize("shape", M.FOURIER_TILED_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_fourier_filter_on_every_kernel_form(shape, dtype_name):
+    """planes past 1024 and 4096 elements, with packs and with single elements (freeu_model.FOURIER_TILED_SHAPES),
+    against the float64 model; the output goes into a slice of a canary-filled buffer"""
+    import fresco_amd
+    from fresco_amd import ops
+    B, C, H, W = shape
+    dt = DTYPES[dtype_name]
+    x = M.fourier_input(shape)
+    xg = _gpu(x, dt)
+    assert np.array_equal(_np64(xg), x)
+    for s in M.FOURIER_SCALES:
+        ref = _fourier_ref(shape, s)
+        y = fresco_amd.Fourier_filter(xg, 1, s)
+        assert y.dtype == xg.dtype and y.shape == xg.shape
+        _assert_within(_np64(y), ref, _fourier_bound(ref, x, dtype_name), "%s %s s=%g" % (shape, dtype_name, s))
+        assert torch.equal(y, fresco_amd.Fourier_filter(xg, 1, s))  # same bits on every run
+        buf = torch.full((B, 2 * C * H * W), CANARY, dtype=dt, device=DEV)
+        out = buf[:, :C * H * W].view(B, C, H, W)
+        assert ops.freeu_fourier(xg, s, out=out) is out
+        assert torch.equal(out, y) and bool((buf[:, C * H * W:] == CANARY).all())
+    assert torch.equal(fresco_amd.Fourier_filter(xg, 1, 1.0), xg)
+    assert torch.equal(xg, _gpu(x, DTYPES[dtype_name]))  # the input is left alone
+
+
+def _views(B, chw, dt):
+    """-> [(name, buffer, the (B, chw) view of it a test writes through)]: a view that starts one element into its buffer
+    (no 16-byte alignment), and one whose batch stride is odd; canaries before, between and after the samples"""
+    flat = torch.full((B * chw + 16,), CANARY, dtype=dt, device=DEV)
+    rows = torch.full((B, chw + 3), CANARY, dtype=dt, device=DEV)
+    return [("one element in", flat, flat[1:1 + B * chw].view(B, chw)), ("odd batch stride", rows, rows[:, :chw])]
+
+
+def _canaries_intact(name, buf, B, chw):
+    if name == "one element in":
+        return bool((buf[:1] == CANARY).all()) and bool((buf[1 + B * chw:] == CANARY).all())
+    return bool((buf[:, chw:] == CANARY).all())
+
+
+@pytest.mark.parametrize("dtype_name", list(DTYPES))
+@pytest.mark.parametrize("shape", [(2, 3, 8, 8), (2, 2, 48, 48), (2, 1, 72, 64)], ids=lambda s: "x".join(map(str, s)))
+def test_fourier_filter_into_unaligned_and_odd_strided_views(shape, dtype_name):
+    """H W is a multiple of the pack, the destination is not: the pointer half and the stride half of the `wide`
+    predicate each send the call down the single-element path (planes of 64, 2304 and 4608 elements: all three kernels)"""
+    from fresco_amd import ops
+    B, C, H, W = shape
+    dt = DTYPES[dtype_name]
+    chw = C * H * W
+    assert (H * W) % 8 == 0 and chw % 2 == 0
+    x = M.fourier_input(shape)
+    xg = _gpu(x, dt)
+    for s in (0.2, 1.0):
+        ref = _fourier_ref(shape, s)
+        for name, buf, view in _views(B, chw, dt):
+            out = view.view(B, C, H, W)
+            if name == "one element in":
+                assert out.data_ptr() % 16 == xg.element_size() and out.stride(0) == chw
+            else:
+                assert out.data_ptr() % 16 == 0 and out.stride(0) % 2 == 1
+            assert ops.freeu_fourier(xg, s, out=out) is out
+            _assert_within(_np64(out), ref, _fourier_bound(ref, x, dtype_name), "%s %s s=%g %s" % (shape, dtype_name, s, name))
+            assert _canaries_intact(name, buf, B, chw), name
+            if s == 1.0:
+                assert torch.equal(out, xg)
+            first = out.clone()
+            ops.freeu_fourier(xg, s, out=out)
+            assert torch.equal(out, first)
+
+
+def test_copy_takes_a_second_grid_stride_trip():
+    """scale = 1 on 129 x 128 x 256 fp16 elements: 2064 blocks' worth of 16-byte packs against the grid cap of 2048"""
+    from fresco_amd import ops
+    B, C, H, W = 1, 129, 128, 256
+    chw = C * H * W
+    x = (torch.arange(chw, device=DEV) % 2039).to(torch.float16).view(B, C, H, W)  # integers below 2048: exact in fp16
+    buf = torch.full((chw + 64,), CANARY, dtype=torch.float16, device=DEV)
+    out = buf[:chw].view(B, C, H, W)
+    assert ops.freeu_fourier(x, 1.0, out=out) is out
+    assert torch.equal(out, x) and bool((buf[chw:] == CANARY).all())
+
+
+@pytest.mark.parametrize("dtype_name", list(DTYPES))
+def test_copy_of_an_odd_sample_size(dtype_name):
+    """scale = 1 with C H W = 3465: the single-element copy kernel, 14 blocks per sample, into both kinds of view"""
+    from fresco_amd import ops
+    shape = (2, 3, 33, 35)
+    B, chw = 2, 3 * 33 * 35
+    dt = DTYPES[dtype_name]
+    xg = _gpu(M.fourier_input(shape), dt)
+    assert torch.equal(ops.freeu_fourier(xg, 1.0), xg)
+    for name, buf, view in _views(B, chw, dt):
+        out = view.view(shape)
+        ops.freeu_fourier(xg, 1.0, out=out)
+        assert torch.equal(out, xg) and _canaries_intact(name, buf, B, chw), name
+
+
 def test_fourier_filter_refuses_what_is_not_built():
     import fresco_amd
     from fresco_amd import ops
@@ -107,7 +214,7 @@ def test_fourier_filter_refuses_what_is_not_built():
 def backbone_refs():
     """float64 model outputs, computed once per (case, b)"""
     refs = {}
-    for case in M.BACKBONE_CASES:
+    for case in M.BACKBONE_CASES + M.BACKBONE_TILED_CASES:
         x = M.backbone_input(case)
         refs[case] = (x, {b: M.backbone_model(x, case[2], b) for b in M.BACKBONE_BS})
     return refs
@@ -116,6 +223,17 @@ def backbone_refs():
 @pytest.mark.parametrize("dtype_name", list(DTYPES))
 @pytest.mark.parametrize("case", M.BACKBONE_CASES, ids=lambda c: "x".join(map(str, c)))
 def test_backbone_scaling_and_concat(backbone_refs, case, dtype_name):
+    _check_backbone(backbone_refs, case, dtype_name)
+
+
+@pytest.mark.parametrize("dtype_name", list(DTYPES))
+@pytest.mark.parametrize("case", M.BACKBONE_TILED_CASES, ids=lambda c: "x".join(map(str, c)))
+def test_backbone_on_planes_of_several_tiles(backbone_refs, case, dtype_name):
+    """freeu_model.BACKBONE_TILED_CASES: every pixel tile must read its own slice of the mean map and of the channels"""
+    _check_backbone(backbone_refs, case, dtype_name)
+
+
+def _check_backbone(backbone_refs, case, dtype_name):
     from fresco_amd import ops
     B, C, n, H, W = case
     dt = DTYPES[dtype_name]

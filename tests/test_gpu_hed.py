@@ -1,6 +1,6 @@
 """The HED annotator on the GPU: the three kernels of csrc/hed.hip against float64 restatements, and the native detector
-end to end against records of the unmodified reference (tests/golden/hed_golden.npz, stand-in weights and frames of
-tests/hed_model.py).
+end to end against records of the unmodified reference (tests/golden/hed_golden.npz and hed_wide_golden.npz, stand-in
+weights and frames of tests/hed_model.py).  tests/test_gpu_hed_conv.py holds each convolution alone to a float64 one.
 
 Bounds.
   * Operand planes: hi + lo carries 22 bits, |hi + lo - v s| <= 2^-21 |v s|; lo is an fp16 whose spacing below 2^-14 is
@@ -17,6 +17,7 @@ Bounds.
 Measured on an MI355X, worst native distance / bar over a case's recorded frames (side maps 1-5, then the fused logit):
   2 x 64 x 64   0.16 0.20 0.42 0.65 0.67 | 0.46        1 x 64 x 128  0.16 0.24 0.27 0.33 0.32 | 0.32
   2 x 96 x 80   0.20 0.25 0.30 0.41 0.37 | 0.31        1 x 72 x 88   0.14 0.24 0.22 0.52 0.31 | 0.38
+  1 x 128 x 128 0.16 0.25 0.25 0.32 0.28 | 0.30        (hed_model.WIDE_CASES: blocks 1 to 4 in the window-in-LDS form)
 (test_native_detector_matches_the_reference_records prints them; DESIGN.md section 12 has the table.)
 """
 import copy
@@ -39,7 +40,7 @@ SCALE = 64.0
 
 @pytest.fixture(scope="module")
 def hed_golden():
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", "hed_golden.npz")))
+    return M.load_golden(os.path.join(ROOT, "tests", "golden"))
 
 
 @pytest.fixture(scope="module")
@@ -76,7 +77,7 @@ def _plane_bound(v_scaled):
 # kernels
 # ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", [(2, 7, 9), (1, 16, 12), (3, 5, 5)], ids=lambda s: "x".join(map(str, s)))
-@pytest.mark.parametrize("C", [64, 512])
+@pytest.mark.parametrize("C", [64, 128, 256, 512])
 def test_side_pool_matches_the_float64_restatement(C, shape):
     _check_side_pool(C, shape)
 
@@ -201,7 +202,7 @@ def test_fuse_past_the_grid_cap():
     assert tuple(cond.shape) == (1, 3, H, W) and all(torch.equal(cond[0, ch], c) for ch in range(3))
 
 
-@pytest.mark.parametrize("case", M.CASES, ids=M.case_key)
+@pytest.mark.parametrize("case", M.CASES + M.WIDE_CASES, ids=M.case_key)
 def test_fuse_on_the_reference_side_maps(hed_golden, case):
     from fresco_amd import ops
     n, H, W = case
@@ -227,7 +228,7 @@ def test_fuse_on_the_reference_side_maps(hed_golden, case):
 # ---------------------------------------------------------------------------------------------------------------
 # end to end
 # ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", M.CASES, ids=M.case_key)
+@pytest.mark.parametrize("case", M.CASES + M.WIDE_CASES, ids=M.case_key)
 def test_native_detector_matches_the_reference_records(hed_golden, net, case):
     n, H, W = case
     frames = _gpu(M.frames(case))

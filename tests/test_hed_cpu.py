@@ -1,5 +1,5 @@
 """The HED annotator without a GPU: parameter names against the reference's, the helper's restatement of the detector's
-post-processing against records of the unmodified reference (tests/golden/hed_golden.npz), the host-side logic of the
+post-processing against records of the unmodified reference (tests/golden/hed_golden.npz, hed_wide_golden.npz), the host-side logic of the
 public interface, the C ABI, and argument checks that must raise before anything is launched."""
 import os
 import re
@@ -17,7 +17,15 @@ SYMBOLS = ("fresco_hed_input", "fresco_hed_side_pool", "fresco_hed_fuse")
 
 @pytest.fixture(scope="module")
 def hed_golden():
-    return dict(np.load(os.path.join(ROOT, "tests", "golden", "hed_golden.npz")))
+    return M.load_golden(os.path.join(ROOT, "tests", "golden"))
+
+
+def test_both_golden_files_record_one_network():
+    """the state-dict names, shapes and the weights' sha256 of the two files are the same"""
+    a, b = (np.load(os.path.join(ROOT, "tests", "golden", name)) for name in M.GOLDEN_FILES)
+    for k in ("param_names", "param_shapes", "weights_sha256"):
+        assert np.array_equal(a[k], b[k]), k
+    assert not (set(a.files) & set(b.files)) - {"param_names", "param_shapes", "weights_sha256"}
 
 
 def test_state_dict_names_are_the_references(hed_golden):
@@ -31,14 +39,14 @@ def test_state_dict_names_are_the_references(hed_golden):
     assert M.weights_digest() == str(hed_golden["weights_sha256"])
 
 
-@pytest.mark.parametrize("case", M.CASES, ids=M.case_key)
+@pytest.mark.parametrize("case", M.CASES + M.WIDE_CASES, ids=M.case_key)
 def test_inputs_are_the_ones_the_reference_saw(hed_golden, case):
     fr = M.frames(case)
     assert fr.dtype == np.uint8 and fr.shape == case + (3,)
     assert M.digest(fr) == str(hed_golden[M.case_key(case) + "_sha256"])
 
 
-@pytest.mark.parametrize("case", M.CASES, ids=M.case_key)
+@pytest.mark.parametrize("case", M.CASES + M.WIDE_CASES, ids=M.case_key)
 def test_fuse_restatement_reproduces_the_reference_map(hed_golden, case):
     n, H, W = case
     for f in range(M.GOLDEN_FRAMES[case]):
