@@ -30,6 +30,7 @@ namespace fresco {
 struct FnConv {  // implicit-GEMM view of an NHWC tensor; kh == 0: A is a plain row-major matrix
     int kh, kw, stride, pad, H, W, OH, OW, cin;  // cin = channels per pixel of the (padded) input rows
     int tiled;                                   // 1: a workgroup's 256 rows are a 16 x 16 patch of output pixels
+    int dilation;                                // tap (ky, kx) reads pixel (oy stride - pad + ky dilation, ox .. + kx dilation)
 };
 
 constexpr int FN_BM = 256, FN_BK = 32, FN_NS = 3;
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(512, 1) void fn_gemm_kernel(const half_t* __restric
                 if (cv.kh == 0) {
                     off = a_base[i] + k0 + a_pc[i] * 8;
                 } else {
-                    const int iy = a_iy[i] + ky, ix = a_ix[i] + kx;
+                    const int iy = a_iy[i] + ky * cv.dilation, ix = a_ix[i] + kx * cv.dilation;
                     ok = ok && iy >= 0 && iy < cv.H && ix >= 0 && ix < cv.W;
                     off = (a_base[i] + (int64_t)iy * cv.W + ix) * lda + c0 + a_pc[i] * 8;
                 }
@@ -826,8 +827,8 @@ using namespace fresco;
 extern "C" int fresco_fn_gemm(const void* a_hi, const void* a_lo, int64_t lda, const void* w_hi, const void* w_lo,
                               const float* bias, float* out, void* out_hi, void* out_lo, int64_t ldc, int64_t ldo, int M,
                               int N, int K, int act, float acc_scale, float split_scale, int n_img, int H, int W, int kh,
-                              int kw, int stride, int pad, void* stats, const void* zeros, const int32_t* a_rows,
-                              const int32_t* out_rows, int32_t* range_flag, int out_col_block, int64_t out_block_stride,
+                              int kw, int stride, int pad, int dilation, void* stats, const void* zeros,
+                              const int32_t* a_rows, const int32_t* out_rows, int32_t* range_flag, int out_col_block, int64_t out_block_stride,
                               void* stream) {
     if (!zeros) return FRESCO_EINVAL;
     if ((a_rows || out_rows) && (kh > 0 || stats)) return FRESCO_EUNSUPPORTED;
@@ -838,14 +839,17 @@ extern "C" int fresco_fn_gemm(const void* a_hi, const void* a_lo, int64_t lda, c
         return FRESCO_EINVAL;
     if ((out && out_col_block == 0 && ldc < N) || (out_hi && ldo < N)) return FRESCO_EINVAL;
     if (out_hi && (N % 8 != 0 || ldo % 8 != 0)) return FRESCO_EUNSUPPORTED;
-    FnConv cv = {0, 0, 1, 0, 0, 0, 0, 0, 0, 0};
+    FnConv cv = {0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 1};
     if (kh > 0) {
-        if (kw <= 0 || stride <= 0 || pad < 0 || n_img <= 0 || H <= 0 || W <= 0) return FRESCO_EINVAL;
+        if (kw <= 0 || stride <= 0 || pad < 0 || dilation <= 0 || n_img <= 0 || H <= 0 || W <= 0) return FRESCO_EINVAL;
         const int cin = K / (kh * kw);
         if (cin * kh * kw != K || cin % 32 != 0 || lda < cin) return FRESCO_EUNSUPPORTED;
-        const int OH = (H + 2 * pad - kh) / stride + 1, OW = (W + 2 * pad - kw) / stride + 1;
+        // (a window wider than the padded map has no output pixel: C division would round the negative extent towards zero)
+        const int eh = H + 2 * pad - dilation * (kh - 1) - 1, ew = W + 2 * pad - dilation * (kw - 1) - 1;
+        if (eh < 0 || ew < 0) return FRESCO_EINVAL;
+        const int OH = eh / stride + 1, OW = ew / stride + 1;
         if ((int64_t)n_img * OH * OW != M) return FRESCO_EINVAL;
-        cv = FnConv{kh, kw, stride, pad, H, W, OH, OW, cin, (OH % 16 == 0 && OW % 16 == 0) ? 1 : 0};
+        cv = FnConv{kh, kw, stride, pad, H, W, OH, OW, cin, (OH % 16 == 0 && OW % 16 == 0) ? 1 : 0, dilation};
         // fused InstanceNorm partial sums: a row block must not straddle two images
         if (stats && ((int64_t)OH * OW) % FN_BM != 0) return FRESCO_EUNSUPPORTED;
     } else if (stats) {
@@ -863,7 +867,7 @@ extern "C" int fresco_fn_gemm(const void* a_hi, const void* a_lo, int64_t lda, c
     half_t* ol = static_cast<half_t*>(out_lo);
     double* sp = static_cast<double*>(stats);
     const int rb = (M + FN_BM - 1) / FN_BM;
-    // 3 x 3 / stride 1 / pad 1 on whole 16 x 16 patches: the window-in-LDS form (FRESCO_FN_CONV_PATCH=0: the im2col form)
+    // 3 x 3 / stride 1 / pad 1 / dilation 1 on whole 16 x 16 patches: the window-in-LDS form (FRESCO_FN_CONV_PATCH=0: the im2col form)
     static const bool patch_on = [] {
         const char* e = getenv("FRESCO_FN_CONV_PATCH");
         return !(e && e[0] == '0');
@@ -872,7 +876,7 @@ extern "C" int fresco_fn_gemm(const void* a_hi, const void* a_lo, int64_t lda, c
         const char* e = getenv("FRESCO_FN_XCD_MAP");
         return !(e && e[0] == '0');
     }();
-    const bool patch = patch_on && cv.tiled && kh == 3 && kw == 3 && stride == 1 && pad == 1;
+    const bool patch = patch_on && cv.tiled && kh == 3 && kw == 3 && stride == 1 && pad == 1 && dilation == 1;
 #define FN_LAUNCH(BN_, PATCH_)                                                                                                \
     do {                                                                                                                      \
         const int lds = (PATCH_) ? 2 * 2 * 24 * 1024 + FN_NS * 2 * (BN_) * 64 : FN_NS * (2 * FN_BM * 64 + 2 * (BN_) * 64);    \

@@ -1,5 +1,5 @@
 """Weight operands of the split-fp16 dense layers (csrc/flownet.hip), cached per parameter version: what the flow network
-(gmflow.py) and the HED annotator (hed.py) hand to ops.fn_gemm."""
+(gmflow.py), the HED annotator (hed.py) and the EGNet saliency detector (egnet.py) hand to ops.fn_gemm."""
 import torch
 import torch.nn.functional as F
 
@@ -49,6 +49,32 @@ class WeightPlanes:
         bad = g.tripped()  # (one host sync per parameter version)
         self.out_of_range |= bad
         self.cache[key] = (stamp, val, bad)
+        return val
+
+    def get_folded(self, p, bn, kind):
+        """planes of a bias-free convolution's weight with the eval-mode BatchNorm `bn` that follows it folded in, and the
+        bias that leaves: rows x gamma / sqrt(running_var + eps), bias = beta - running_mean gamma / sqrt(running_var + eps),
+        both formed in float64 -> ((hi, lo), bias fp32).  kind: "conv" or "stem" as in get().  The cache entry is stamped with
+        the weight AND the four BatchNorm tensors: an update of any of them makes new planes."""
+        members = (p, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+        key = (id(p), id(bn), kind, "folded")
+        stamps = tuple(self._stamp(t) for t in members) + (float(bn.eps),)
+        hit = self.cache.get(key)
+        if hit is not None and None not in stamps and hit[0] == stamps:
+            self.out_of_range |= hit[2]
+            return hit[1]
+        g = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + float(bn.eps))
+        bias = (bn.bias.detach().double() - bn.running_mean.detach().double() * g).float().contiguous()
+        w = (p.detach().double() * g.view(-1, 1, 1, 1)).float()
+        with ops.fn_range_guard(w.device) as guard:
+            if kind == "stem":
+                planes = ops.fn_conv7_weight(w)
+            else:
+                _, planes = ops.fn_prep(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous(), scale=ops.FN_W_SCALE)
+        bad = guard.tripped()  # (one host sync per parameter version)
+        self.out_of_range |= bad
+        val = (planes, bias)
+        self.cache[key] = (stamps, val, bad)
         return val
 
     def get_stacked(self, params):

@@ -486,12 +486,17 @@ def fn_colstats(x, n_img, eps=1e-5):
     return mean, rstd
 
 
+def conv_out_size(H, W, kh, kw, stride, pad, dilation=1):
+    """nn.Conv2d's output size (floor)"""
+    return ((H + 2 * pad - dilation * (kh - 1) - 1) // stride + 1, (W + 2 * pad - dilation * (kw - 1) - 1) // stride + 1)
+
+
 def fn_gemm(a, w, N, K, bias=None, act=0, conv=None, M=None, want_f32=True, want_split=False, out_split=None,
             instance_norm_eps=None, a_rows=None, out_rows=None, out_f32=None, out_blocks=0, a_scale=FN_A_SCALE,
             out_scale=FN_A_SCALE):
     """act(A W^T + bias) (fresco_fn_gemm).  a = (hi, lo) planes, (rows, lda); w = (hi, lo) planes (N, K).
     a_scale / out_scale: the power of two the planes of `a` were written with / the output planes are written with.
-    conv = (n_img, H, W, kh, kw, stride, pad): implicit im2col of the NHWC tensor behind `a` (K = kh kw cin).
+    conv = (n_img, H, W, kh, kw, stride, pad[, dilation = 1]): implicit im2col of the NHWC tensor behind `a` (K = kh kw cin).
     a_rows / out_rows (linear layers): int32 (M) tables -- problem row m reads input row a_rows[m], writes output row
     out_rows[m] (the rows of `out` not named by the table keep whatever they held: pass a full permutation).
     instance_norm_eps (convolutions): also return InstanceNorm2d statistics (mean, rstd) of the result, from partial sums
@@ -503,12 +508,17 @@ def fn_gemm(a, w, N, K, bias=None, act=0, conv=None, M=None, want_f32=True, want
     lda = ah.stride(0)
     if conv is None:
         M = (ah.shape[0] if a_rows is None else a_rows.numel()) if M is None else M
-        cargs = (0, 0, 0, 0, 0, 1, 0)
+        cargs = (0, 0, 0, 0, 0, 1, 0, 1)
     else:
-        n_img, H, W, kh, kw, stride, pad = conv
-        OH, OW = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+        if len(conv) not in (7, 8):
+            raise ValueError("fn_gemm: conv = (n_img, H, W, kh, kw, stride, pad[, dilation]), got %r" % (conv,))
+        n_img, H, W, kh, kw, stride, pad = conv[:7]
+        dilation = int(conv[7]) if len(conv) == 8 else 1
+        if dilation < 1:
+            raise ValueError("fn_gemm: dilation %r" % (conv[7],))
+        OH, OW = conv_out_size(H, W, kh, kw, stride, pad, dilation)
         M = n_img * OH * OW
-        cargs = (n_img, H, W, kh, kw, stride, pad)
+        cargs = (n_img, H, W, kh, kw, stride, pad, dilation)
     dev = ah.device
     bias = _fn_f32_operand(bias, "bias", ah)
     a_rows = _fn_rows_table(a_rows, "a_rows", ah, M)
@@ -1066,6 +1076,104 @@ def hed_fuse(sides, want_logit=False, cond_dtype=None):
                                      _ELEMWISE_DTYPES.get(cond_dtype, _lib.F32), n, H, W, _stream())
     _lib.check(rc, "fresco_hed_fuse(n=%d,H=%d,W=%d)" % (n, H, W))
     return out, logit, cond
+
+
+# ---------------------------------------------------------------------------------------------
+# EGNet saliency detector (src/EGNet/model.py, src/utils.py::get_saliency): the pieces around the fn_gemm convolutions
+# (csrc/egnet.hip, libfresco_egnet.so)
+# ---------------------------------------------------------------------------------------------
+EGNET_MAX_K = 15
+
+
+def egnet_input(frames):
+    """frames (n, H, W, 3) uint8 -> cv2sod's tensor as (n, H // 2, W // 2, 3) fp32 NHWC: channel means subtracted, each
+    2 x 2 block averaged (fresco_egnet_input)"""
+    _hed_dense(frames, "egnet_input: frames", torch.uint8)
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0 or frames.shape[1] < 2 or frames.shape[2] < 2:
+        raise ValueError("egnet_input: frames must be (n, H >= 2, W >= 2, 3), got %s" % (tuple(frames.shape),))
+    _need_gpu(frames)
+    n, H, W, _ = frames.shape
+    out = torch.empty(n, H // 2, W // 2, 3, dtype=torch.float32, device=frames.device)
+    rc = _lib.load_egnet().fresco_egnet_input(frames.data_ptr(), out.data_ptr(), n, H, W, _stream())
+    _lib.check_egnet(rc, "fresco_egnet_input(n=%d,H=%d,W=%d)" % (n, H, W))
+    return out
+
+
+def egnet_pool_size(size):
+    """MaxPool2d(3, stride 2, padding 1, ceil_mode=True): the output size of one axis (PyTorch's rule: the last window
+    starts inside the input or its left padding)"""
+    o = (size + 2 - 3 + 1) // 2 + 1
+    return o - 1 if (o - 1) * 2 >= size + 1 else o
+
+
+def egnet_pool(x, want_f32=False, scale=FN_A_SCALE):
+    """x (n, H, W, 64) fp32 NHWC -> (pooled fp32 (n, OH, OW, 64) or None, (hi, lo) planes (n OH OW, 64)) of
+    MaxPool2d(3, 2, 1, ceil_mode=True) (fresco_egnet_pool)"""
+    _hed_dense(x, "egnet_pool: x", torch.float32, align=16)
+    if x.dim() != 4 or x.shape[3] != 64 or x.numel() == 0:
+        raise ValueError("egnet_pool: x must be (n, H, W, 64), got %s" % (tuple(x.shape),))
+    scale = _hed_scale(scale)
+    _need_gpu(x)
+    n, H, W, C = x.shape
+    OH, OW = egnet_pool_size(H), egnet_pool_size(W)
+    out = torch.empty(n, OH, OW, C, dtype=torch.float32, device=x.device) if want_f32 else None
+    hi = torch.empty(n * OH * OW, C, dtype=torch.float16, device=x.device)
+    lo = torch.empty_like(hi)
+    rc = _lib.load_egnet().fresco_egnet_pool(x.data_ptr(), _ptr(out), hi.data_ptr(), lo.data_ptr(), n, H, W, C, scale,
+                                       _fn_flag_ptr(x.device), _stream())
+    _lib.check_egnet(rc, "fresco_egnet_pool(n=%d,H=%d,W=%d,C=%d)" % (n, H, W, C))
+    return out, (hi, lo)
+
+
+def egnet_resize_add(x, size, addend=None, relu=False, want_f32=True, want_split=False, scale=FN_A_SCALE):
+    """[relu](F.interpolate(x, size, bilinear, align_corners=True) [+ addend]) on NHWC fp32: x (n, h, w, C), addend
+    (n, H, W, C) -> (fp32 (n, H, W, C) or None, (hi, lo) planes (n H W, C) or None) (fresco_egnet_resize_add)"""
+    _hed_dense(x, "egnet_resize_add: x", torch.float32, align=16)
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError("egnet_resize_add: x must be (n, h, w, C), got %s" % (tuple(x.shape),))
+    n, h, w, C = x.shape
+    H, W = int(size[0]), int(size[1])
+    if H <= 0 or W <= 0:
+        raise ValueError("egnet_resize_add: size %r" % (size,))
+    if C % 32 or C > 512:
+        raise ValueError("egnet_resize_add: C = %d (a multiple of 32 up to 512)" % C)
+    if addend is not None:
+        _hed_dense(addend, "egnet_resize_add: addend", torch.float32, (n, H, W, C), align=16)
+        if addend.device != x.device:
+            raise ValueError("egnet_resize_add: addend on another device")
+    if not (want_f32 or want_split):
+        raise ValueError("egnet_resize_add: nothing asked for")
+    scale = _hed_scale(scale)
+    _need_gpu(x)
+    out = torch.empty(n, H, W, C, dtype=torch.float32, device=x.device) if want_f32 else None
+    hi = lo = None
+    if want_split:
+        hi = torch.empty(n * H * W, C, dtype=torch.float16, device=x.device)
+        lo = torch.empty_like(hi)
+    rc = _lib.load_egnet().fresco_egnet_resize_add(x.data_ptr(), _ptr(addend), _ptr(out), _ptr(hi), _ptr(lo), n, h, w, H, W, C,
+                                             int(bool(relu)), scale, _fn_flag_ptr(x.device), _stream())
+    _lib.check_egnet(rc, "fresco_egnet_resize_add(n=%d,%dx%d->%dx%d,C=%d)" % (n, h, w, H, W, C))
+    return out, ((hi, lo) if want_split else None)
+
+
+def egnet_saliency(logit, size, k=7, want_logit=False):
+    """logit (n, h, w) fp32 -> (1 - clamp(box_k(sigmoid(resize(logit, size))), 0, 1) as (n, 1, Hs, Ws) fp32, the resized logit
+    (n, Hs, Ws) or None): align_corners=True resize, k x k box sum with replicate padding (fresco_egnet_saliency)"""
+    _hed_dense(logit, "egnet_saliency: logit", torch.float32)
+    if logit.dim() != 3 or logit.numel() == 0:
+        raise ValueError("egnet_saliency: logit must be (n, h, w), got %s" % (tuple(logit.shape),))
+    Hs, Ws, k = int(size[0]), int(size[1]), int(k)
+    if Hs <= 0 or Ws <= 0:
+        raise ValueError("egnet_saliency: size %r" % (size,))
+    if k < 1 or k % 2 == 0 or k > EGNET_MAX_K:
+        raise ValueError("egnet_saliency: k = %d (odd, at most %d)" % (k, EGNET_MAX_K))
+    _need_gpu(logit)
+    n, h, w = logit.shape
+    out = torch.empty(n, 1, Hs, Ws, dtype=torch.float32, device=logit.device)
+    lg = torch.empty(n, Hs, Ws, dtype=torch.float32, device=logit.device) if want_logit else None
+    rc = _lib.load_egnet().fresco_egnet_saliency(logit.data_ptr(), out.data_ptr(), _ptr(lg), n, h, w, Hs, Ws, k, _stream())
+    _lib.check_egnet(rc, "fresco_egnet_saliency(n=%d,%dx%d->%dx%d,k=%d)" % (n, h, w, Hs, Ws, k))
+    return out, lg
 
 
 # ---------------------------------------------------------------------------------------------

@@ -278,7 +278,9 @@ int fresco_attn_f32(const float* q, const float* k, const float* v, float* out, 
 /* out[m][n] = act( sum_k A(m, k) W[n][k] + bias[n] ),  m < M, n < N, K % 32 == 0.
  *   kh == 0: A = a_hi + a_lo, (M, K) row-major with row stride lda (halfs)               -- nn.Linear / 1 x 1 conv
  *   kh  > 0: implicit im2col of an NHWC tensor (n_img, H, W, cin = K / (kh kw)), pixel stride lda >= cin, cin % 32 == 0,
- *            k = (ky, kx, ci), zero padding `pad`, stride `stride`; M must be n_img * OH * OW    -- nn.Conv2d
+ *            k = (ky, kx, ci), zero padding `pad`, stride `stride`, dilation `dilation` >= 1: tap (ky, kx) of output pixel
+ *            (oy, ox) reads pixel (oy stride - pad + ky dilation, ox stride - pad + kx dilation); M must be
+ *            n_img * OH * OW, OH = (H + 2 pad - dilation (kh - 1) - 1) / stride + 1                 -- nn.Conv2d
  *   w_hi / w_lo: (N, K) row-major fp16 planes; bias (N) fp32 or NULL; act 0 none, 1 ReLU, 2 GELU (erf form).
  *   out (M, ldc) fp32 and / or out_hi / out_lo (M, ldo) fp16 planes of the result (either may be NULL, not both; planes need
  *   N % 8 == 0).  zeros: 16 bytes of zeros in device memory (the source of every row outside the problem and of a
@@ -290,8 +292,8 @@ int fresco_attn_f32(const float* q, const float* k, const float* v, float* out, 
 int fresco_fn_gemm(const void* a_hi, const void* a_lo, int64_t lda, const void* w_hi, const void* w_lo, const float* bias,
                    float* out, void* out_hi, void* out_lo, int64_t ldc, int64_t ldo, int M, int N, int K, int act,
                    float acc_scale, float split_scale, int n_img, int H, int W, int kh, int kw, int stride, int pad,
-                   void* stats, const void* zeros, const int32_t* a_rows, const int32_t* out_rows, int32_t* range_flag,
-                   int out_col_block, int64_t out_block_stride, void* stream);
+                   int dilation, void* stats, const void* zeros, const int32_t* a_rows, const int32_t* out_rows,
+                   int32_t* range_flag, int out_col_block, int64_t out_block_stride, void* stream);
 /* out_col_block > 0 (fp32 output only, N % out_col_block == 0): column n of the product goes to matrix n / out_col_block of
  * out_col_block columns (row stride ldc >= out_col_block), the matrices out_block_stride floats apart -- several projections of
  * one input as ONE product (W = their weight rows stacked), every projection's rows contiguous (round 6: q | k | v and k | v of the
