@@ -20,6 +20,7 @@ from .freeu import (Fourier_filter, apply_freeu, patch_free_lunch, register_free
                     register_free_upblock2d)
 from .hed import ControlNetHED_Apache2, DoubleConvBlock, HEDdetector, patch_hed
 from .egnet import TUN_bone, build_model, get_saliency, patch_saliency
+from .canny import CannyDetector, patch_canny
 from .paras import (correlation_matrices, forward_backward_consistency_check, get_flow_and_interframe_paras,
                     get_intraframe_paras, interframe_paras_from_flows)
 
@@ -33,4 +34,5 @@ __all__ = [
     "Fourier_filter", "register_free_upblock2d", "register_free_crossattn_upblock2d", "apply_freeu", "patch_free_lunch",
     "HEDdetector", "ControlNetHED_Apache2", "DoubleConvBlock", "patch_hed",
     "TUN_bone", "build_model", "get_saliency", "patch_saliency",
+    "CannyDetector", "patch_canny",
 ]

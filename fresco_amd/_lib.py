@@ -121,8 +121,19 @@ EGNET_SIGNATURES = {
     "fresco_egnet_saliency": (_i, [_vp, _vp, _vp] + [_i] * 6 + [_vp]),
 }
 
+# libfresco_canny.so (include/fresco_canny.h): the Canny detector's kernels, a library of their own
+CANNY_LIB_PATH = os.environ.get("FRESCO_CANNY_LIB") or os.path.join(_HERE, "lib", "libfresco_canny.so")
+CANNY_SIGNATURES = {
+    "fresco_version": (_c.c_char_p, []),
+    "fresco_last_error": (_c.c_char_p, []),
+    "fresco_canny_workspace_bytes": (_sz, [_i, _i, _i]),
+    "fresco_canny_classify": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fresco_canny_hysteresis": (_i, [_vp, _vp, _vp, _i, _vp, _sz, _i, _i, _i, _vp]),
+}
+
 _lib = None
 _egnet = None
+_canny = None
 
 
 def load():
@@ -185,6 +196,41 @@ def check_egnet(rc, what):
         detail = ""
         if rc == -4:
             detail = ": " + load_egnet().fresco_last_error().decode()
+        raise FrescoHipError("%s failed: %s%s" % (what, ERRORS.get(rc, "error %d" % rc), detail))
+
+
+def load_canny():
+    """Load libfresco_canny.so (once) and return the ctypes handle; raises FrescoHipError if it cannot."""
+    global _canny
+    if _canny is not None:
+        return _canny
+    if not os.path.exists(CANNY_LIB_PATH):
+        raise FrescoHipError("fresco_amd: %s is missing -- build it with `make -C fresco_amd/csrc`. There is no CPU / eager "
+                             "fallback." % CANNY_LIB_PATH)
+    try:
+        lib = ctypes.CDLL(CANNY_LIB_PATH)
+    except OSError as e:
+        raise FrescoHipError("fresco_amd: cannot load %s: %s" % (CANNY_LIB_PATH, e))
+    for name, (res, args) in CANNY_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise FrescoHipError("fresco_amd: %s does not export %s (stale build?)" % (CANNY_LIB_PATH, name))
+        fn.restype = res
+        fn.argtypes = args
+    built = lib.fresco_version().decode().split()
+    if built[1:2] != [VERSION]:
+        raise FrescoHipError("fresco_amd: %s is version %s, this package binds %s (stale build?)"
+                             % (CANNY_LIB_PATH, " ".join(built[1:2]) or "?", VERSION))
+    _canny = lib
+    return lib
+
+
+def check_canny(rc, what):
+    if rc != OK:
+        detail = ""
+        if rc == -4:
+            detail = ": " + load_canny().fresco_last_error().decode()
         raise FrescoHipError("%s failed: %s%s" % (what, ERRORS.get(rc, "error %d" % rc), detail))
 
 

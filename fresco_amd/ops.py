@@ -1177,6 +1177,48 @@ def egnet_saliency(logit, size, k=7, want_logit=False):
 
 
 # ---------------------------------------------------------------------------------------------
+# Canny edge detector (src/ControlNet/annotator/canny: cv2.Canny per frame) (csrc/canny.hip, libfresco_canny.so)
+# ---------------------------------------------------------------------------------------------
+def canny_classify(frames, low, high):
+    """frames (n, H, W, 3) uint8 RGB -> the class map (n, H, W) uint8 of OpenCV's Canny at aperture 3 with the L1 magnitude:
+    0 no edge, 1 weak (a local maximum above `low`), 2 strong (above `high` too); integer thresholds, low > high swapped
+    (fresco_canny_classify)"""
+    _hed_dense(frames, "canny_classify: frames", torch.uint8)
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise ValueError("canny_classify: frames must be (n, H, W, 3), got %s" % (tuple(frames.shape),))
+    low, high = int(low), int(high)
+    _need_gpu(frames)
+    n, H, W, _ = frames.shape
+    cls = torch.empty(n, H, W, dtype=torch.uint8, device=frames.device)
+    rc = _lib.load_canny().fresco_canny_classify(frames.data_ptr(), cls.data_ptr(), n, H, W, low, high, _stream())
+    _lib.check_canny(rc, "fresco_canny_classify(n=%d,H=%d,W=%d)" % (n, H, W))
+    return cls
+
+
+def canny_hysteresis(cls, cond_dtype=None):
+    """class map (n, H, W) uint8 -> (edge map (n, H, W) uint8: 255 on the weak and strong pixels of every 8-connected
+    component that holds a strong one, ControlNet condition (n, 3, H, W) of cond_dtype or None) (fresco_canny_hysteresis)"""
+    _hed_dense(cls, "canny_hysteresis: cls", torch.uint8)
+    if cls.dim() != 3 or cls.numel() == 0:
+        raise ValueError("canny_hysteresis: the class map is (n, H, W), got %s" % (tuple(cls.shape),))
+    if cond_dtype is not None and cond_dtype not in _ELEMWISE_DTYPES:
+        raise TypeError("canny_hysteresis: cond_dtype %s (fp16, bf16 or fp32)" % (cond_dtype,))
+    _need_gpu(cls)
+    n, H, W = cls.shape
+    lib = _lib.load_canny()
+    need = lib.fresco_canny_workspace_bytes(n, H, W)
+    if need == 0:
+        raise FrescoHipError("canny_hysteresis: n H W = %d x %d x %d is beyond what the kernels index (2^31)" % (n, H, W))
+    ws = torch.empty(need, dtype=torch.uint8, device=cls.device)
+    out = torch.empty(n, H, W, dtype=torch.uint8, device=cls.device)
+    cond = torch.empty(n, 3, H, W, dtype=cond_dtype, device=cls.device) if cond_dtype is not None else None
+    rc = lib.fresco_canny_hysteresis(cls.data_ptr(), out.data_ptr(), _ptr(cond), _ELEMWISE_DTYPES.get(cond_dtype, _lib.F32),
+                                     ws.data_ptr(), need, n, H, W, _stream())
+    _lib.check_canny(rc, "fresco_canny_hysteresis(n=%d,H=%d,W=%d)" % (n, H, W))
+    return out, cond
+
+
+# ---------------------------------------------------------------------------------------------
 # feature optimisation (fp32)
 # ---------------------------------------------------------------------------------------------
 def _opt_args(cs, prep, target, chunk):

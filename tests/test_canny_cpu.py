@@ -1,0 +1,237 @@
+"""fresco_amd's Canny detector without a GPU: the numpy restatement of the rules (tests/canny_model.py) on the hand cases and
+its threshold handling, the proof that the shared inputs can tell the rules apart, the C entry points on the header /
+binding surface of their own library and their argument checks (fake pointers: every check answers before any HIP call),
+the Python surface, and -- only where cv2 can be imported -- the restatement against a real OpenCV."""
+import ctypes
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import canny_model as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ("fresco_canny_workspace_bytes", "fresco_canny_classify", "fresco_canny_hysteresis")
+EINVAL, EUNSUPPORTED, EWORKSPACE = -1, -2, -3
+NATURAL = [(case, setting) for case in M.NATURAL_CASES for setting in M.NATURAL_SETTINGS]
+NATURAL_IDS = ["%s-%d-%d" % (M.case_id(c), s[1], s[2]) for c, s in NATURAL]
+
+
+# ---- the model
+def test_hand_cases():
+    e = M.canny(M.step_columns(6, 8, 4, 100), 50, 100)
+    want = np.zeros((6, 8), np.uint8)
+    want[:, 3] = 255
+    assert np.array_equal(e, want)
+    e = M.canny(M.step_rows(6, 8, 3, 100), 50, 100)
+    want = np.zeros((6, 8), np.uint8)
+    want[2] = 255
+    assert np.array_equal(e, want)
+    row = np.zeros((1, 7, 3), np.uint8)
+    row[:, 3:] = 100
+    assert M.canny(row, 50, 100).tolist() == [[0, 0, 255, 0, 0, 0, 0]]
+    for v in (0, 77, 255):
+        assert M.canny(np.full((1, 1, 3), v, np.uint8), 50, 100).tolist() == [[0]]
+
+
+def test_threshold_handling():
+    img = M.natural_case(M.NATURAL_CASES[0], 10.0)[0]
+    base = M.classify(img, 50, 100)
+    assert (base == 1).any() and (base == 2).any()
+    assert np.array_equal(M.classify(img, 100, 50), base)
+    assert np.array_equal(M.classify(img, 50.9, 100.9), base)
+    assert not np.array_equal(M.classify(img, 60, 120), base)  # (the thresholds do matter on this image)
+
+
+def test_hysteresis_model_on_the_constructed_maps():
+    s = M.serpentine()
+    assert int((s > 0).sum()) == 2660 and int((M.hysteresis(s) == 255).sum()) == 2660
+    assert not M.hysteresis(M.serpentine(seed=False)).any()
+    st = M.staircase()
+    assert np.array_equal(M.hysteresis(st) == 255, st > 0)  # 8-connected
+    cb = M.checkerboard()
+    assert np.array_equal(M.hysteresis(cb) == 255, cb > 0)
+    b = M.hysteresis(M.two_blobs())
+    assert b[:, :36].sum() == 255 * 30 * 33 and not b[:, 36:].any()
+    three = np.stack([np.full((9, 11), 2), np.ones((9, 11)), np.ones((9, 11))]).astype(np.uint8)
+    assert M.hysteresis(three)[0].all() and not M.hysteresis(three)[1:].any()
+    odd = np.array([[2, 3, 1], [255, 0, 0], [0, 0, 0]], np.uint8)  # 3 and 255 count as 0: the 1 is cut off
+    assert M.hysteresis(odd).tolist() == [[255, 0, 0], [0, 0, 0], [0, 0, 0]]
+
+
+@pytest.mark.parametrize("case,setting", NATURAL, ids=NATURAL_IDS)
+def test_the_inputs_can_tell_the_rules_apart(case, setting):
+    """on every frame of the natural batches each rule variant changes at least one pixel of the class map, and hysteresis
+    has both work to do and something to refuse: at least 2 % of all pixels are weak and end kept, 2 % weak and dropped"""
+    std, low, high = setting
+    for f in M.natural_case(case, std):
+        base = M.classify(f, low, high)
+        for name in M.VARIANT_NAMES:
+            d = int((M.classify(f, low, high, name) != base).sum())
+            assert d >= 1, (name, d)
+        kept, dropped = M.weak_fate(f, low, high)
+        print("%s std %g: weak kept %.1f %%, weak dropped %.1f %%" % (M.case_id(case), std, 100 * kept, 100 * dropped))
+        assert kept >= 0.02 and dropped >= 0.02
+
+
+def test_uniform_noise_would_not_do():
+    """the reason for the filtered field: on uniform uint8 noise hardly a survivor is weak"""
+    img = np.random.RandomState(0).randint(0, 256, (64, 64, 3)).astype(np.uint8)
+    c = M.classify(img, 50, 100)
+    assert (c == 2).mean() > 0.05 and (c == 1).mean() < 0.01
+
+
+# ---- the C surface
+def _canny_prototypes(surface):
+    """the prototypes of include/fresco_canny.h, parsed as the existing surface test parses fresco_hip.h"""
+    header = open(os.path.join(ROOT, "include", "fresco_canny.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    header = re.sub(r"^\s*#.*$", "", header, flags=re.M)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(fresco_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header):
+        assert name not in protos, name
+        protos[name] = (surface.SCALARS[ret.split()[-1]], [surface._ctype(a) for a in params.split(",")])
+    return protos
+
+
+def test_entry_points_are_on_the_c_abi_surface():
+    """header prototypes == binding == exported functions, argument lists included; libfresco_hip.so keeps its surface"""
+    import test_capi_surface_cpu as surface
+    from fresco_amd import _lib
+    protos = _canny_prototypes(surface)
+    assert set(protos) == set(NEW_SYMBOLS)
+    exported = surface._exported_fresco_functions(_lib.CANNY_LIB_PATH)
+    assert {n for n in exported if "canny" in n} == set(NEW_SYMBOLS)
+    assert {"fresco_version", "fresco_last_error"} <= exported
+    assert set(_lib.CANNY_SIGNATURES) == set(NEW_SYMBOLS) | {"fresco_version", "fresco_last_error"}
+    for name in NEW_SYMBOLS:
+        res, args = _lib.CANNY_SIGNATURES[name]
+        assert res is protos[name][0] and list(args) == protos[name][1], name
+        assert name not in _lib.SIGNATURES and name not in _lib.EGNET_SIGNATURES
+    assert _lib.CANNY_SIGNATURES["fresco_canny_workspace_bytes"][0] is ctypes.c_size_t
+    assert _lib.CANNY_SIGNATURES["fresco_canny_classify"][0] is ctypes.c_int
+    assert _lib.load_canny().fresco_version() == _lib.load().fresco_version()
+    assert not [n for n in surface._exported_fresco_functions(_lib.LIB_PATH) if "canny" in n]
+    surface.test_binding_matches_the_header_prototypes()
+
+
+def test_a_stale_canny_library_is_refused(monkeypatch):
+    from fresco_amd import _lib
+    lib = _lib.load_canny()
+
+    class Stale:
+        def __getattr__(self, name):
+            return getattr(lib, name)
+
+        @staticmethod
+        def fresco_version():
+            return b"fresco_hip 0.5.0 gfx950"
+
+    monkeypatch.setattr(_lib, "_canny", None)
+    monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: Stale())
+    with pytest.raises(_lib.FrescoHipError, match="stale build"):
+        _lib.load_canny()
+    assert _lib._canny is None
+
+
+def test_entry_points_check_their_arguments_before_any_launch():
+    from fresco_amd import _lib
+    lib = _lib.load_canny()
+    p = 4096  # fake, aligned, never touched
+    n, H, W = 2, 70, 75
+    need = lib.fresco_canny_workspace_bytes(n, H, W)
+    assert need >= 4 * n * H * W
+    assert lib.fresco_canny_workspace_bytes(1, 1, 1) >= 4
+    for bad in ((0, H, W), (n, 0, W), (n, H, -1), (2, 32768, 32768), (1, 1 << 30, 2)):
+        assert lib.fresco_canny_workspace_bytes(*bad) == 0
+    assert lib.fresco_canny_workspace_bytes(1, 32768, 65535) >= 4 * 32768 * 65535  # just below 2^31
+
+    def classify(frames=p, cls=p, n=n, H=H, W=W):
+        return lib.fresco_canny_classify(frames, cls, n, H, W, 50, 100, None)
+
+    assert classify(frames=None) == EINVAL
+    assert classify(cls=None) == EINVAL
+    for k in ("n", "H", "W"):
+        assert classify(**{k: 0}) == EINVAL
+        assert classify(**{k: -3}) == EINVAL
+    assert classify(n=2, H=32768, W=32768) == EUNSUPPORTED
+
+    def hyst(cls=p, out=p, cond=None, dt=_lib.F16, ws=p, wsb=need, n=n, H=H, W=W):
+        return lib.fresco_canny_hysteresis(cls, out, cond, dt, ws, wsb, n, H, W, None)
+
+    assert hyst(cls=None) == EINVAL
+    assert hyst(out=None) == EINVAL
+    assert hyst(ws=None) == EINVAL
+    for k in ("n", "H", "W"):
+        assert hyst(**{k: 0}) == EINVAL
+    assert hyst(cond=p, dt=7) == EINVAL
+    assert hyst(cond=p, dt=-1) == EINVAL
+    assert hyst(ws=p + 2) == EINVAL                 # parent is read as 32-bit words
+    assert hyst(cond=p + 2, dt=_lib.F32) == EINVAL
+    assert hyst(wsb=need - 1) == EWORKSPACE
+    assert hyst(wsb=0) == EWORKSPACE
+    assert hyst(cond=p, dt=_lib.BF16, wsb=need - 1) == EWORKSPACE
+    assert hyst(n=2, H=32768, W=32768, wsb=1 << 40) == EUNSUPPORTED
+    assert hyst(dt=7, wsb=need - 1) == EWORKSPACE   # an unknown dtype matters only with a condition
+
+
+# ---- the Python surface
+def test_exports_and_patch_canny(monkeypatch):
+    import sys
+    import fresco_amd
+    from fresco_amd import canny
+    assert fresco_amd.CannyDetector is canny.CannyDetector and fresco_amd.patch_canny is canny.patch_canny
+    assert "CannyDetector" in fresco_amd.__all__ and "patch_canny" in fresco_amd.__all__
+    star = types.ModuleType("run_fresco_standin")  # a module that imported the name
+    star.CannyDetector = object
+    assert canny.patch_canny(star) is star and star.CannyDetector is canny.CannyDetector
+    annotator, mod = types.ModuleType("annotator"), types.ModuleType("annotator.canny")
+    annotator.canny = mod
+    mod.CannyDetector = object
+    monkeypatch.setitem(sys.modules, "annotator", annotator)
+    monkeypatch.setitem(sys.modules, "annotator.canny", mod)
+    assert canny.patch_canny() is mod and mod.CannyDetector is canny.CannyDetector
+
+
+def test_python_side_refusals():
+    from fresco_amd import canny, FrescoHipError
+    det = canny.CannyDetector()
+    ok = np.zeros((8, 9, 3), np.uint8)
+    for bad in (np.zeros((8, 9), np.uint8), np.zeros((8, 9, 1), np.uint8)):
+        with pytest.raises((TypeError, ValueError), match="Canny"):
+            det(bad, 50, 100)
+        with pytest.raises((TypeError, ValueError), match="Canny"):
+            det.detect_batch([bad])
+    with pytest.raises((TypeError, ValueError), match="Canny"):
+        det.detect_batch(torch.zeros(2, 8, 9, 1, dtype=torch.uint8))
+    with pytest.raises(TypeError, match="Canny"):
+        det(ok.astype(np.float32), 50, 100)
+    with pytest.raises(TypeError, match="Canny"):
+        det.detect_batch(torch.zeros(1, 8, 9, 3))
+    with pytest.raises(ValueError, match="Canny.*share a size"):
+        det.detect_batch([ok, np.zeros((8, 10, 3), np.uint8)])
+    with pytest.raises(ValueError, match="Canny"):
+        det.detect_batch([])
+    for low, high in ((float("nan"), 100), (50, float("inf")), (float("-inf"), 100)):
+        with pytest.raises(ValueError, match="Canny"):
+            det.detect_batch([ok], low, high)
+    with pytest.raises(TypeError, match="Canny"):
+        det.detect_batch([ok], "50", 100)
+    with pytest.raises(TypeError, match="Canny"):
+        det.control_image([ok], torch.float64)
+    # a tensor batch stays where it is: on the CPU the operators refuse it
+    with pytest.raises(FrescoHipError, match="GPU only"):
+        det.detect_batch(torch.zeros(1, 8, 9, 3, dtype=torch.uint8))
+    assert canny.check_thresholds(50.9, 100.9) == (50, 100) and canny.check_thresholds(np.float32(7.5), 3) == (7, 3)
+
+
+# ---- against a real OpenCV, where there is one
+@pytest.mark.parametrize("case,setting", NATURAL, ids=NATURAL_IDS)
+def test_model_equals_cv2_where_cv2_exists(case, setting):
+    cv2 = pytest.importorskip("cv2")
+    std, low, high = setting
+    for f in M.natural_case(case, std):
+        assert np.array_equal(M.canny(f, low, high), cv2.Canny(f, low, high))
