@@ -21,7 +21,7 @@ ERRORS = {
 F16, F32, BF16 = 0, 1, 2
 # what fresco_version() of the library these SIGNATURES describe reports: an older build exports the same names with other
 # argument lists
-VERSION = "0.5.0.1"  # (0.5.0.1: fresco_fn_gemm took its dilation argument)
+VERSION = "0.5.0.2"  # (0.5.0.2: the fresco_egnet_* and fresco_canny_* entry points moved into this library)
 
 
 class FrescoHipError(RuntimeError):
@@ -108,32 +108,16 @@ SIGNATURES = {
     "fresco_hed_input": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp]),
     "fresco_hed_side_pool": (_i, [_vp] * 6 + [_i, _i, _i, _i, _f, _vp, _vp]),
     "fresco_hed_fuse": (_i, [_vp] * 8 + [_i, _i, _i, _i, _vp]),
-}
-
-# libfresco_egnet.so (include/fresco_egnet.h): the EGNet detector's kernels, a library of their own
-EGNET_LIB_PATH = os.environ.get("FRESCO_EGNET_LIB") or os.path.join(_HERE, "lib", "libfresco_egnet.so")
-EGNET_SIGNATURES = {
-    "fresco_version": (_c.c_char_p, []),
-    "fresco_last_error": (_c.c_char_p, []),
     "fresco_egnet_input": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "fresco_egnet_pool": (_i, [_vp] * 4 + [_i, _i, _i, _i, _f, _vp, _vp]),
     "fresco_egnet_resize_add": (_i, [_vp] * 5 + [_i] * 7 + [_f, _vp, _vp]),
     "fresco_egnet_saliency": (_i, [_vp, _vp, _vp] + [_i] * 6 + [_vp]),
-}
-
-# libfresco_canny.so (include/fresco_canny.h): the Canny detector's kernels, a library of their own
-CANNY_LIB_PATH = os.environ.get("FRESCO_CANNY_LIB") or os.path.join(_HERE, "lib", "libfresco_canny.so")
-CANNY_SIGNATURES = {
-    "fresco_version": (_c.c_char_p, []),
-    "fresco_last_error": (_c.c_char_p, []),
     "fresco_canny_workspace_bytes": (_sz, [_i, _i, _i]),
     "fresco_canny_classify": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fresco_canny_hysteresis": (_i, [_vp, _vp, _vp, _i, _vp, _sz, _i, _i, _i, _vp]),
 }
 
 _lib = None
-_egnet = None
-_canny = None
 
 
 def load():
@@ -162,76 +146,6 @@ def load():
                              % (LIB_PATH, " ".join(built[1:2]) or "?", VERSION))
     _lib = lib
     return lib
-
-
-def load_egnet():
-    """Load libfresco_egnet.so (once) and return the ctypes handle; raises FrescoHipError if it cannot."""
-    global _egnet
-    if _egnet is not None:
-        return _egnet
-    if not os.path.exists(EGNET_LIB_PATH):
-        raise FrescoHipError("fresco_amd: %s is missing -- build it with `make -C fresco_amd/csrc`. There is no CPU / eager "
-                             "fallback." % EGNET_LIB_PATH)
-    try:
-        lib = ctypes.CDLL(EGNET_LIB_PATH)
-    except OSError as e:
-        raise FrescoHipError("fresco_amd: cannot load %s: %s" % (EGNET_LIB_PATH, e))
-    for name, (res, args) in EGNET_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise FrescoHipError("fresco_amd: %s does not export %s (stale build?)" % (EGNET_LIB_PATH, name))
-        fn.restype = res
-        fn.argtypes = args
-    built = lib.fresco_version().decode().split()
-    if built[1:2] != [VERSION]:
-        raise FrescoHipError("fresco_amd: %s is version %s, this package binds %s (stale build?)"
-                             % (EGNET_LIB_PATH, " ".join(built[1:2]) or "?", VERSION))
-    _egnet = lib
-    return lib
-
-
-def check_egnet(rc, what):
-    if rc != OK:
-        detail = ""
-        if rc == -4:
-            detail = ": " + load_egnet().fresco_last_error().decode()
-        raise FrescoHipError("%s failed: %s%s" % (what, ERRORS.get(rc, "error %d" % rc), detail))
-
-
-def load_canny():
-    """Load libfresco_canny.so (once) and return the ctypes handle; raises FrescoHipError if it cannot."""
-    global _canny
-    if _canny is not None:
-        return _canny
-    if not os.path.exists(CANNY_LIB_PATH):
-        raise FrescoHipError("fresco_amd: %s is missing -- build it with `make -C fresco_amd/csrc`. There is no CPU / eager "
-                             "fallback." % CANNY_LIB_PATH)
-    try:
-        lib = ctypes.CDLL(CANNY_LIB_PATH)
-    except OSError as e:
-        raise FrescoHipError("fresco_amd: cannot load %s: %s" % (CANNY_LIB_PATH, e))
-    for name, (res, args) in CANNY_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise FrescoHipError("fresco_amd: %s does not export %s (stale build?)" % (CANNY_LIB_PATH, name))
-        fn.restype = res
-        fn.argtypes = args
-    built = lib.fresco_version().decode().split()
-    if built[1:2] != [VERSION]:
-        raise FrescoHipError("fresco_amd: %s is version %s, this package binds %s (stale build?)"
-                             % (CANNY_LIB_PATH, " ".join(built[1:2]) or "?", VERSION))
-    _canny = lib
-    return lib
-
-
-def check_canny(rc, what):
-    if rc != OK:
-        detail = ""
-        if rc == -4:
-            detail = ": " + load_canny().fresco_last_error().decode()
-        raise FrescoHipError("%s failed: %s%s" % (what, ERRORS.get(rc, "error %d" % rc), detail))
 
 
 def check(rc, what):

@@ -17,7 +17,6 @@
 // not return.
 // Built with -ffp-contract=off: the condition follows the torch operation order, as in hed.hip.
 #include "common.h"
-#include "../../include/fresco_canny.h"
 
 namespace fresco {
 
@@ -307,8 +306,7 @@ __global__ __launch_bounds__(256) void canny_emit_kernel(const uint8_t* __restri
     }
 }
 
-static inline bool canny_aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
+// (not common.h's stream_blocks: this caps a count of blocks at 2^20, that one a count of threads at 2048 blocks)
 static inline int canny_blocks(int64_t want) { return (int)(want < CANNY_MAX_BLOCKS ? want : CANNY_MAX_BLOCKS); }
 
 // n H W when the calls take the size, else 0
@@ -347,7 +345,7 @@ extern "C" int fresco_canny_hysteresis(const uint8_t* cls, uint8_t* out, void* c
                                        size_t workspace_bytes, int n, int H, int W, void* stream) {
     if (!cls || !out || !workspace || n <= 0 || H <= 0 || W <= 0) return FRESCO_EINVAL;
     if (cond && cond_dtype != FRESCO_F16 && cond_dtype != FRESCO_BF16 && cond_dtype != FRESCO_F32) return FRESCO_EINVAL;
-    if (!canny_aligned(workspace, 4) || !canny_aligned(cond, cond_dtype == FRESCO_F32 ? 4 : 2)) return FRESCO_EINVAL;
+    if (!aligned_to(workspace, 4) || !aligned_to(cond, cond_dtype == FRESCO_F32 ? 4 : 2)) return FRESCO_EINVAL;
     const int64_t npix = canny_pixels(n, H, W);
     if (!npix) return FRESCO_EUNSUPPORTED;
     if (workspace_bytes < fresco_canny_workspace_bytes(n, H, W)) return FRESCO_EWORKSPACE;

@@ -54,6 +54,16 @@ static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+static inline bool aligned_to(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
+// Grid of a streaming kernel of 256-thread blocks that walks `threads` items with a grid-stride loop: capped at 2048 blocks
+// (256 CUs x 8 blocks)
+constexpr int STREAM_MAX_BLOCKS = 2048;
+static inline int stream_blocks(int64_t threads) {
+    const int64_t b = (threads + 255) / 256;
+    return (int)(b < STREAM_MAX_BLOCKS ? b : STREAM_MAX_BLOCKS);
+}
+
 template <typename T>
 static inline T* carve(char*& p, size_t count) {
     T* r = reinterpret_cast<T*>(p);

@@ -12,11 +12,9 @@
 // All four are bound by memory traffic; no float atomics anywhere: same inputs, same bits.
 #include "common.h"
 #include "fn_split.h"
-#include "../../include/fresco_egnet.h"
 
 namespace fresco {
 
-constexpr int EG_MAX_BLOCKS = 2048;  // grid cap of the streaming kernels (256 CUs x 8 blocks); the rest is a grid-stride loop
 constexpr int EG_MAX_K = 15;         // widest box of the tail
 constexpr int EG_TILE = 16;          // the tail's output tile (one pixel per thread)
 constexpr int EG_MAX_SIDE = 32768;   // map sides of the resizes: destination index * (source side - 1) stays an int
@@ -192,13 +190,6 @@ __global__ __launch_bounds__(256) void egnet_saliency_kernel(const float* __rest
     if (logit_out) logit_out[o] = egnet_logit_at(m, y, x, h, w, Hs, Ws);
 }
 
-static inline bool eg_aligned(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
-static inline int eg_blocks(int64_t threads) {
-    const int64_t b = (threads + 255) / 256;
-    return (int)(b < EG_MAX_BLOCKS ? b : EG_MAX_BLOCKS);
-}
-
 // MaxPool2d(3, 2, 1, ceil_mode=True): ceil((size + 2 pad - k) / stride) + 1, minus one where the last window would start
 // beyond the input and its left padding
 static inline int eg_pool_size(int size) {
@@ -213,12 +204,12 @@ using namespace fresco;
 
 extern "C" int fresco_egnet_input(const uint8_t* frames, float* out, int n, int H, int W, void* stream) {
     if (!frames || !out || n <= 0 || H <= 0 || W <= 0) return FRESCO_EINVAL;
-    if (!eg_aligned(out, 4)) return FRESCO_EINVAL;
+    if (!aligned_to(out, 4)) return FRESCO_EINVAL;
     if (H < 2 || W < 2) return FRESCO_EUNSUPPORTED;  // (no halved pixel)
     if ((int64_t)n * H * W >= (int64_t)1 << 31) return FRESCO_EUNSUPPORTED;
     const int OH = H / 2, OW = W / 2;
     const int64_t total = (int64_t)n * OH * OW * 3;
-    hipLaunchKernelGGL(egnet_input_kernel, dim3(eg_blocks(total)), dim3(256), 0, as_stream(stream), frames, out, total, H, W,
+    hipLaunchKernelGGL(egnet_input_kernel, dim3(stream_blocks(total)), dim3(256), 0, as_stream(stream), frames, out, total, H, W,
                        OH, OW);
     return check_launch();
 }
@@ -228,10 +219,10 @@ extern "C" int fresco_egnet_pool(const float* x, float* out, void* out_hi, void*
     if (!x || !out_hi || !out_lo || n <= 0 || H <= 0 || W <= 0 || C <= 0 || !(split_scale > 0.f)) return FRESCO_EINVAL;
     if (C != 64) return FRESCO_EUNSUPPORTED;
     if ((int64_t)n * H * W >= (int64_t)1 << 31) return FRESCO_EUNSUPPORTED;
-    if (!eg_aligned(x, 16) || !eg_aligned(out, 16) || !eg_aligned(out_hi, 8) || !eg_aligned(out_lo, 8)) return FRESCO_EINVAL;
+    if (!aligned_to(x, 16) || !aligned_to(out, 16) || !aligned_to(out_hi, 8) || !aligned_to(out_lo, 8)) return FRESCO_EINVAL;
     const int OH = eg_pool_size(H), OW = eg_pool_size(W);
     const int64_t total = (int64_t)n * OH * OW * (C / 4);
-    hipLaunchKernelGGL(egnet_pool_kernel, dim3(eg_blocks(total)), dim3(256), 0, as_stream(stream), x, out,
+    hipLaunchKernelGGL(egnet_pool_kernel, dim3(stream_blocks(total)), dim3(256), 0, as_stream(stream), x, out,
                        static_cast<half_t*>(out_hi), static_cast<half_t*>(out_lo), total, H, W, OH, OW, split_scale, range_flag);
     return check_launch();
 }
@@ -246,10 +237,10 @@ extern "C" int fresco_egnet_resize_add(const float* x, const float* addend, floa
     if (C % 32 != 0 || C > 512) return FRESCO_EUNSUPPORTED;
     if (h > EG_MAX_SIDE || w > EG_MAX_SIDE || H > EG_MAX_SIDE || W > EG_MAX_SIDE) return FRESCO_EUNSUPPORTED;
     if ((int64_t)n * H * W >= (int64_t)1 << 31 || (int64_t)n * h * w >= (int64_t)1 << 31) return FRESCO_EUNSUPPORTED;
-    if (!eg_aligned(x, 16) || !eg_aligned(addend, 16) || !eg_aligned(out, 16) || !eg_aligned(out_hi, 8) || !eg_aligned(out_lo, 8))
+    if (!aligned_to(x, 16) || !aligned_to(addend, 16) || !aligned_to(out, 16) || !aligned_to(out_hi, 8) || !aligned_to(out_lo, 8))
         return FRESCO_EINVAL;
     const int64_t total = (int64_t)n * H * W * (C / 4);
-    hipLaunchKernelGGL(egnet_resize_add_kernel, dim3(eg_blocks(total)), dim3(256), 0, as_stream(stream), x, addend, out,
+    hipLaunchKernelGGL(egnet_resize_add_kernel, dim3(stream_blocks(total)), dim3(256), 0, as_stream(stream), x, addend, out,
                        static_cast<half_t*>(out_hi), static_cast<half_t*>(out_lo), total, h, w, H, W, C, relu ? 1 : 0,
                        split_scale, range_flag);
     return check_launch();
@@ -262,7 +253,7 @@ extern "C" int fresco_egnet_saliency(const float* logit, float* out, float* logi
     if (h > EG_MAX_SIDE || w > EG_MAX_SIDE || Hs > EG_MAX_SIDE || Ws > EG_MAX_SIDE) return FRESCO_EUNSUPPORTED;
     if (n > 65535 || (Hs + EG_TILE - 1) / EG_TILE > 65535) return FRESCO_EUNSUPPORTED;
     if ((int64_t)n * Hs * Ws >= (int64_t)1 << 31 || (int64_t)h * w >= (int64_t)1 << 31) return FRESCO_EUNSUPPORTED;
-    if (!eg_aligned(logit, 4) || !eg_aligned(out, 4) || !eg_aligned(logit_out, 4)) return FRESCO_EINVAL;
+    if (!aligned_to(logit, 4) || !aligned_to(out, 4) || !aligned_to(logit_out, 4)) return FRESCO_EINVAL;
     hipLaunchKernelGGL(egnet_saliency_kernel, dim3((Ws + EG_TILE - 1) / EG_TILE, (Hs + EG_TILE - 1) / EG_TILE, n), dim3(256), 0,
                        as_stream(stream), logit, out, logit_out, h, w, Hs, Ws, k);
     return check_launch();

@@ -337,7 +337,6 @@ __global__ __launch_bounds__(256) void freeu_scale_cat_kernel(T* __restrict__ hi
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static inline bool aligned_to(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 // smallest l <= 8 with (V << l) >= HW
 static inline int freeu_lpx_log2(int HW, int V) {

@@ -17,7 +17,6 @@
 
 namespace fresco {
 
-constexpr int HED_MAX_BLOCKS = 2048;  // grid cap of the streaming kernels (256 CUs x 8 blocks); the rest is a grid-stride loop
 constexpr int HED_LEVELS = 5;
 
 // One thread per (pixel, 16-byte piece of its 64-byte plane row): piece 0 carries the three channels, pieces 1-3 are zeros.
@@ -179,13 +178,6 @@ __global__ __launch_bounds__(256) void hed_fuse_kernel(HedSides s, uint8_t* __re
     }
 }
 
-static inline bool aligned_to(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
-static inline int hed_blocks(int64_t threads) {
-    const int64_t b = (threads + 255) / 256;
-    return (int)(b < HED_MAX_BLOCKS ? b : HED_MAX_BLOCKS);
-}
-
 }  // namespace fresco
 
 using namespace fresco;
@@ -196,7 +188,7 @@ extern "C" int fresco_hed_input(const uint8_t* frames, const float* norm, void* 
     if (!aligned_to(norm, 4) || !aligned_to(out_hi, 16) || !aligned_to(out_lo, 16)) return FRESCO_EINVAL;
     const int64_t npix = (int64_t)n * H * W;
     if (npix >= (int64_t)1 << 31) return FRESCO_EUNSUPPORTED;
-    hipLaunchKernelGGL(hed_input_kernel, dim3(hed_blocks(npix * 4)), dim3(256), 0, as_stream(stream), frames,
+    hipLaunchKernelGGL(hed_input_kernel, dim3(stream_blocks(npix * 4)), dim3(256), 0, as_stream(stream), frames,
                        static_cast<half_t*>(out_hi), static_cast<half_t*>(out_lo), npix, norm, split_scale, range_flag);
     return check_launch();
 }
@@ -214,7 +206,7 @@ extern "C" int fresco_hed_side_pool(const float* h, const float* w, const float*
         !aligned_to(pool_lo, 16))
         return FRESCO_EINVAL;
     const int64_t nquads = (int64_t)n * ((H + 1) / 2) * ((W + 1) / 2);
-    const dim3 grid(hed_blocks(nquads * 16));
+    const dim3 grid(stream_blocks(nquads * 16));
     half_t* ph = static_cast<half_t*>(pool_hi);
     half_t* pl = static_cast<half_t*>(pool_lo);
     hipStream_t st = as_stream(stream);
@@ -244,7 +236,7 @@ extern "C" int fresco_hed_fuse(const float* s1, const float* s2, const float* s3
         !aligned_to(logit, 4) || !aligned_to(cond, cond_dtype == FRESCO_F32 ? 4 : 2))
         return FRESCO_EINVAL;
     const HedSides s = {{s1, s2, s3, s4, s5}};
-    const dim3 grid(hed_blocks(total));
+    const dim3 grid(stream_blocks(total));
     hipStream_t st = as_stream(stream);
     if (cond && cond_dtype == FRESCO_F16)
         hipLaunchKernelGGL(hed_fuse_kernel<half_t>, grid, dim3(256), 0, st, s, out, logit, static_cast<half_t*>(cond),

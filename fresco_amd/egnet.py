@@ -231,7 +231,7 @@ class TUN_bone(nn.Module):
         if int(max_frames) < 1:
             raise ValueError("TUN_bone: max_frames %r" % (max_frames,))
         self.base_model_cfg = base_model_cfg
-        self.split_scales = tuple(ops._hed_scale(s) for s in split_scales)
+        self.split_scales = tuple(ops._split_scale(s) for s in split_scales)
         self.library_ops = bool(library_ops)
         self.max_frames = int(max_frames)
         self.convert = ConvertLayer()

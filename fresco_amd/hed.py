@@ -59,7 +59,7 @@ class ControlNetHED_Apache2(nn.Module):
         super().__init__()
         if len(split_scales) != 5:
             raise ValueError("ControlNetHED_Apache2: one split scale per block (5), got %r" % (split_scales,))
-        self.split_scales = tuple(ops._hed_scale(s) for s in split_scales)
+        self.split_scales = tuple(ops._split_scale(s) for s in split_scales)
         if int(max_frames) < 1:
             raise ValueError("ControlNetHED_Apache2: max_frames %r" % (max_frames,))
         self.library_ops = bool(library_ops)

@@ -40,6 +40,30 @@ def _f32c(t):
     return t.to(torch.float32).contiguous()
 
 
+def _split_scale(scale):
+    """the power of two a pair of (hi, lo) operand planes is written with, as a float"""
+    scale = float(scale)
+    if not (scale > 0 and math.isfinite(scale) and math.frexp(scale)[0] == 0.5):
+        raise ValueError("split scale %r must be a power of two" % (scale,))
+    return scale
+
+
+def _dense(t, name, dtype, shape=None, align=1):
+    """the kernels read raw words: dtype, density and (where they move 16-byte pieces) alignment are checked here, on the
+    host; the caller ends its checks with _need_gpu"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: expected a tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != dtype:
+        raise TypeError("%s: dtype %s, expected %s" % (name, t.dtype, dtype))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s: must be contiguous" % name)
+    if t.data_ptr() % align:
+        raise ValueError("%s: must be %d-byte aligned" % (name, align))
+    return t
+
+
 def _rows(t):
     """(tensor, row stride in elements, rows) for a (..., C) tensor whose rows are uniformly strided
     (dense, or a column slice of a dense (..., k*C) tensor such as a fused projection output);
@@ -970,39 +994,16 @@ def freeu_site(hidden, skip, n_scaled, b, s, workspace=None):
 HED_CHANNELS = (64, 128, 256, 512)
 
 
-def _hed_scale(scale):
-    scale = float(scale)
-    if not (scale > 0 and math.isfinite(scale) and math.frexp(scale)[0] == 0.5):
-        raise ValueError("HED: split scale %r must be a power of two" % (scale,))
-    return scale
-
-
-def _hed_dense(t, name, dtype, shape=None, align=1):
-    """the kernels read raw words: dtype, density and (where they move 16-byte pieces) alignment are checked here, on the
-    host; the caller ends its checks with _need_gpu"""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s: expected a tensor, got %s" % (name, type(t).__name__))
-    if t.dtype != dtype:
-        raise TypeError("%s: dtype %s, expected %s" % (name, t.dtype, dtype))
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError("%s: shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
-    if not t.is_contiguous():
-        raise ValueError("%s: must be contiguous" % name)
-    if t.data_ptr() % align:
-        raise ValueError("%s: must be %d-byte aligned" % (name, align))
-    return t
-
-
 def hed_input(frames, norm, scale=FN_A_SCALE):
     """frames (n, H, W, 3) uint8 RGB, norm 3 fp32 values on the device -> (hi, lo) planes (n H W, 32) of
     (frames - norm) * scale, channels 3..31 zero (fresco_hed_input)"""
-    _hed_dense(frames, "hed_input: frames", torch.uint8)
+    _dense(frames, "hed_input: frames", torch.uint8)
     if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
         raise ValueError("hed_input: frames must be (n, H, W, 3), got %s" % (tuple(frames.shape),))
-    norm = _hed_dense(norm, "hed_input: norm", torch.float32)
+    norm = _dense(norm, "hed_input: norm", torch.float32)
     if norm.numel() != 3 or norm.device != frames.device:
         raise ValueError("hed_input: norm must hold 3 values on the frames' device")
-    scale = _hed_scale(scale)
+    scale = _split_scale(scale)
     _need_gpu(frames)
     n, H, W, _ = frames.shape
     hi = torch.empty(n * H * W, 32, dtype=torch.float16, device=frames.device)
@@ -1016,7 +1017,7 @@ def hed_input(frames, norm, scale=FN_A_SCALE):
 def hed_side_pool(h, n, H, W, weight, bias=None, want_proj=True, want_pool=True, scale=FN_A_SCALE):
     """h (n H W, C) fp32 NHWC rows (post-ReLU), weight (C) / bias (1) of the block's 1 x 1 projection -> (proj (n, H, W)
     fp32 or None, (hi, lo) planes (n (H//2) (W//2), C) of max_pool2d(h, 2, 2) * scale or None) (fresco_hed_side_pool)"""
-    _hed_dense(h, "hed_side_pool: h", torch.float32, align=16)
+    _dense(h, "hed_side_pool: h", torch.float32, align=16)
     if h.dim() != 2 or h.shape[0] != n * H * W or n <= 0 or H <= 0 or W <= 0:
         raise ValueError("hed_side_pool: h %s is not (n H W, C) rows for n, H, W = %d, %d, %d" % (tuple(h.shape), n, H, W))
     C = h.shape[1]
@@ -1026,14 +1027,14 @@ def hed_side_pool(h, n, H, W, weight, bias=None, want_proj=True, want_pool=True,
         raise ValueError("hed_side_pool: nothing asked for")
     if want_pool and (H < 2 or W < 2):
         raise ValueError("hed_side_pool: a %d x %d map has no pooled pixel" % (H, W))
-    weight = _hed_dense(weight, "hed_side_pool: weight", torch.float32, align=16)
+    weight = _dense(weight, "hed_side_pool: weight", torch.float32, align=16)
     if weight.numel() != C or weight.device != h.device:
         raise ValueError("hed_side_pool: weight must hold C = %d values on h's device" % C)
     if bias is not None:
-        bias = _hed_dense(bias, "hed_side_pool: bias", torch.float32)
+        bias = _dense(bias, "hed_side_pool: bias", torch.float32)
         if bias.numel() != 1 or bias.device != h.device:
             raise ValueError("hed_side_pool: bias must hold one value on h's device")
-    scale = _hed_scale(scale)
+    scale = _split_scale(scale)
     _need_gpu(h)
     proj = torch.empty(n, H, W, dtype=torch.float32, device=h.device) if want_proj else None
     hi = lo = None
@@ -1056,14 +1057,14 @@ def hed_fuse(sides, want_logit=False, cond_dtype=None):
     ControlNet condition (n, 3, H, W) of cond_dtype or None) (fresco_hed_fuse)"""
     if len(sides) != 5:
         raise ValueError("hed_fuse: five side maps, got %d" % len(sides))
-    s0 = _hed_dense(sides[0], "hed_fuse: side 1", torch.float32)
+    s0 = _dense(sides[0], "hed_fuse: side 1", torch.float32)
     if s0.dim() != 3 or s0.numel() == 0:
         raise ValueError("hed_fuse: side maps are (n, h, w), got %s" % (tuple(s0.shape),))
     n, H, W = s0.shape
     if H < 16 or W < 16:
         raise ValueError("hed_fuse: frames of at least 16 x 16 (level 5 is the size halved four times), got %d x %d" % (H, W))
     for k, (hk, wk) in enumerate(hed_level_sizes(H, W)):
-        _hed_dense(sides[k], "hed_fuse: side %d" % (k + 1), torch.float32, (n, hk, wk))
+        _dense(sides[k], "hed_fuse: side %d" % (k + 1), torch.float32, (n, hk, wk))
         if sides[k].device != s0.device:
             raise ValueError("hed_fuse: side maps on different devices")
     if cond_dtype is not None and cond_dtype not in _ELEMWISE_DTYPES:
@@ -1080,7 +1081,7 @@ def hed_fuse(sides, want_logit=False, cond_dtype=None):
 
 # ---------------------------------------------------------------------------------------------
 # EGNet saliency detector (src/EGNet/model.py, src/utils.py::get_saliency): the pieces around the fn_gemm convolutions
-# (csrc/egnet.hip, libfresco_egnet.so)
+# (csrc/egnet.hip)
 # ---------------------------------------------------------------------------------------------
 EGNET_MAX_K = 15
 
@@ -1088,14 +1089,14 @@ EGNET_MAX_K = 15
 def egnet_input(frames):
     """frames (n, H, W, 3) uint8 -> cv2sod's tensor as (n, H // 2, W // 2, 3) fp32 NHWC: channel means subtracted, each
     2 x 2 block averaged (fresco_egnet_input)"""
-    _hed_dense(frames, "egnet_input: frames", torch.uint8)
+    _dense(frames, "egnet_input: frames", torch.uint8)
     if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0 or frames.shape[1] < 2 or frames.shape[2] < 2:
         raise ValueError("egnet_input: frames must be (n, H >= 2, W >= 2, 3), got %s" % (tuple(frames.shape),))
     _need_gpu(frames)
     n, H, W, _ = frames.shape
     out = torch.empty(n, H // 2, W // 2, 3, dtype=torch.float32, device=frames.device)
-    rc = _lib.load_egnet().fresco_egnet_input(frames.data_ptr(), out.data_ptr(), n, H, W, _stream())
-    _lib.check_egnet(rc, "fresco_egnet_input(n=%d,H=%d,W=%d)" % (n, H, W))
+    rc = _lib.load().fresco_egnet_input(frames.data_ptr(), out.data_ptr(), n, H, W, _stream())
+    _lib.check(rc, "fresco_egnet_input(n=%d,H=%d,W=%d)" % (n, H, W))
     return out
 
 
@@ -1109,26 +1110,26 @@ def egnet_pool_size(size):
 def egnet_pool(x, want_f32=False, scale=FN_A_SCALE):
     """x (n, H, W, 64) fp32 NHWC -> (pooled fp32 (n, OH, OW, 64) or None, (hi, lo) planes (n OH OW, 64)) of
     MaxPool2d(3, 2, 1, ceil_mode=True) (fresco_egnet_pool)"""
-    _hed_dense(x, "egnet_pool: x", torch.float32, align=16)
+    _dense(x, "egnet_pool: x", torch.float32, align=16)
     if x.dim() != 4 or x.shape[3] != 64 or x.numel() == 0:
         raise ValueError("egnet_pool: x must be (n, H, W, 64), got %s" % (tuple(x.shape),))
-    scale = _hed_scale(scale)
+    scale = _split_scale(scale)
     _need_gpu(x)
     n, H, W, C = x.shape
     OH, OW = egnet_pool_size(H), egnet_pool_size(W)
     out = torch.empty(n, OH, OW, C, dtype=torch.float32, device=x.device) if want_f32 else None
     hi = torch.empty(n * OH * OW, C, dtype=torch.float16, device=x.device)
     lo = torch.empty_like(hi)
-    rc = _lib.load_egnet().fresco_egnet_pool(x.data_ptr(), _ptr(out), hi.data_ptr(), lo.data_ptr(), n, H, W, C, scale,
+    rc = _lib.load().fresco_egnet_pool(x.data_ptr(), _ptr(out), hi.data_ptr(), lo.data_ptr(), n, H, W, C, scale,
                                        _fn_flag_ptr(x.device), _stream())
-    _lib.check_egnet(rc, "fresco_egnet_pool(n=%d,H=%d,W=%d,C=%d)" % (n, H, W, C))
+    _lib.check(rc, "fresco_egnet_pool(n=%d,H=%d,W=%d,C=%d)" % (n, H, W, C))
     return out, (hi, lo)
 
 
 def egnet_resize_add(x, size, addend=None, relu=False, want_f32=True, want_split=False, scale=FN_A_SCALE):
     """[relu](F.interpolate(x, size, bilinear, align_corners=True) [+ addend]) on NHWC fp32: x (n, h, w, C), addend
     (n, H, W, C) -> (fp32 (n, H, W, C) or None, (hi, lo) planes (n H W, C) or None) (fresco_egnet_resize_add)"""
-    _hed_dense(x, "egnet_resize_add: x", torch.float32, align=16)
+    _dense(x, "egnet_resize_add: x", torch.float32, align=16)
     if x.dim() != 4 or x.numel() == 0:
         raise ValueError("egnet_resize_add: x must be (n, h, w, C), got %s" % (tuple(x.shape),))
     n, h, w, C = x.shape
@@ -1138,28 +1139,28 @@ def egnet_resize_add(x, size, addend=None, relu=False, want_f32=True, want_split
     if C % 32 or C > 512:
         raise ValueError("egnet_resize_add: C = %d (a multiple of 32 up to 512)" % C)
     if addend is not None:
-        _hed_dense(addend, "egnet_resize_add: addend", torch.float32, (n, H, W, C), align=16)
+        _dense(addend, "egnet_resize_add: addend", torch.float32, (n, H, W, C), align=16)
         if addend.device != x.device:
             raise ValueError("egnet_resize_add: addend on another device")
     if not (want_f32 or want_split):
         raise ValueError("egnet_resize_add: nothing asked for")
-    scale = _hed_scale(scale)
+    scale = _split_scale(scale)
     _need_gpu(x)
     out = torch.empty(n, H, W, C, dtype=torch.float32, device=x.device) if want_f32 else None
     hi = lo = None
     if want_split:
         hi = torch.empty(n * H * W, C, dtype=torch.float16, device=x.device)
         lo = torch.empty_like(hi)
-    rc = _lib.load_egnet().fresco_egnet_resize_add(x.data_ptr(), _ptr(addend), _ptr(out), _ptr(hi), _ptr(lo), n, h, w, H, W, C,
+    rc = _lib.load().fresco_egnet_resize_add(x.data_ptr(), _ptr(addend), _ptr(out), _ptr(hi), _ptr(lo), n, h, w, H, W, C,
                                              int(bool(relu)), scale, _fn_flag_ptr(x.device), _stream())
-    _lib.check_egnet(rc, "fresco_egnet_resize_add(n=%d,%dx%d->%dx%d,C=%d)" % (n, h, w, H, W, C))
+    _lib.check(rc, "fresco_egnet_resize_add(n=%d,%dx%d->%dx%d,C=%d)" % (n, h, w, H, W, C))
     return out, ((hi, lo) if want_split else None)
 
 
 def egnet_saliency(logit, size, k=7, want_logit=False):
     """logit (n, h, w) fp32 -> (1 - clamp(box_k(sigmoid(resize(logit, size))), 0, 1) as (n, 1, Hs, Ws) fp32, the resized logit
     (n, Hs, Ws) or None): align_corners=True resize, k x k box sum with replicate padding (fresco_egnet_saliency)"""
-    _hed_dense(logit, "egnet_saliency: logit", torch.float32)
+    _dense(logit, "egnet_saliency: logit", torch.float32)
     if logit.dim() != 3 or logit.numel() == 0:
         raise ValueError("egnet_saliency: logit must be (n, h, w), got %s" % (tuple(logit.shape),))
     Hs, Ws, k = int(size[0]), int(size[1]), int(k)
@@ -1171,41 +1172,41 @@ def egnet_saliency(logit, size, k=7, want_logit=False):
     n, h, w = logit.shape
     out = torch.empty(n, 1, Hs, Ws, dtype=torch.float32, device=logit.device)
     lg = torch.empty(n, Hs, Ws, dtype=torch.float32, device=logit.device) if want_logit else None
-    rc = _lib.load_egnet().fresco_egnet_saliency(logit.data_ptr(), out.data_ptr(), _ptr(lg), n, h, w, Hs, Ws, k, _stream())
-    _lib.check_egnet(rc, "fresco_egnet_saliency(n=%d,%dx%d->%dx%d,k=%d)" % (n, h, w, Hs, Ws, k))
+    rc = _lib.load().fresco_egnet_saliency(logit.data_ptr(), out.data_ptr(), _ptr(lg), n, h, w, Hs, Ws, k, _stream())
+    _lib.check(rc, "fresco_egnet_saliency(n=%d,%dx%d->%dx%d,k=%d)" % (n, h, w, Hs, Ws, k))
     return out, lg
 
 
 # ---------------------------------------------------------------------------------------------
-# Canny edge detector (src/ControlNet/annotator/canny: cv2.Canny per frame) (csrc/canny.hip, libfresco_canny.so)
+# Canny edge detector (src/ControlNet/annotator/canny: cv2.Canny per frame) (csrc/canny.hip)
 # ---------------------------------------------------------------------------------------------
 def canny_classify(frames, low, high):
     """frames (n, H, W, 3) uint8 RGB -> the class map (n, H, W) uint8 of OpenCV's Canny at aperture 3 with the L1 magnitude:
     0 no edge, 1 weak (a local maximum above `low`), 2 strong (above `high` too); integer thresholds, low > high swapped
     (fresco_canny_classify)"""
-    _hed_dense(frames, "canny_classify: frames", torch.uint8)
+    _dense(frames, "canny_classify: frames", torch.uint8)
     if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
         raise ValueError("canny_classify: frames must be (n, H, W, 3), got %s" % (tuple(frames.shape),))
     low, high = int(low), int(high)
     _need_gpu(frames)
     n, H, W, _ = frames.shape
     cls = torch.empty(n, H, W, dtype=torch.uint8, device=frames.device)
-    rc = _lib.load_canny().fresco_canny_classify(frames.data_ptr(), cls.data_ptr(), n, H, W, low, high, _stream())
-    _lib.check_canny(rc, "fresco_canny_classify(n=%d,H=%d,W=%d)" % (n, H, W))
+    rc = _lib.load().fresco_canny_classify(frames.data_ptr(), cls.data_ptr(), n, H, W, low, high, _stream())
+    _lib.check(rc, "fresco_canny_classify(n=%d,H=%d,W=%d)" % (n, H, W))
     return cls
 
 
 def canny_hysteresis(cls, cond_dtype=None):
     """class map (n, H, W) uint8 -> (edge map (n, H, W) uint8: 255 on the weak and strong pixels of every 8-connected
     component that holds a strong one, ControlNet condition (n, 3, H, W) of cond_dtype or None) (fresco_canny_hysteresis)"""
-    _hed_dense(cls, "canny_hysteresis: cls", torch.uint8)
+    _dense(cls, "canny_hysteresis: cls", torch.uint8)
     if cls.dim() != 3 or cls.numel() == 0:
         raise ValueError("canny_hysteresis: the class map is (n, H, W), got %s" % (tuple(cls.shape),))
     if cond_dtype is not None and cond_dtype not in _ELEMWISE_DTYPES:
         raise TypeError("canny_hysteresis: cond_dtype %s (fp16, bf16 or fp32)" % (cond_dtype,))
     _need_gpu(cls)
     n, H, W = cls.shape
-    lib = _lib.load_canny()
+    lib = _lib.load()
     need = lib.fresco_canny_workspace_bytes(n, H, W)
     if need == 0:
         raise FrescoHipError("canny_hysteresis: n H W = %d x %d x %d is beyond what the kernels index (2^31)" % (n, H, W))
@@ -1214,7 +1215,7 @@ def canny_hysteresis(cls, cond_dtype=None):
     cond = torch.empty(n, 3, H, W, dtype=cond_dtype, device=cls.device) if cond_dtype is not None else None
     rc = lib.fresco_canny_hysteresis(cls.data_ptr(), out.data_ptr(), _ptr(cond), _ELEMWISE_DTYPES.get(cond_dtype, _lib.F32),
                                      ws.data_ptr(), need, n, H, W, _stream())
-    _lib.check_canny(rc, "fresco_canny_hysteresis(n=%d,H=%d,W=%d)" % (n, H, W))
+    _lib.check(rc, "fresco_canny_hysteresis(n=%d,H=%d,W=%d)" % (n, H, W))
     return out, cond
 
 

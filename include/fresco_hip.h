@@ -41,7 +41,7 @@ extern "C" {
 /* dtype codes for entry points that accept more than one element type */
 #define FRESCO_F16 0
 #define FRESCO_F32 1
-#define FRESCO_BF16 2 /* bfloat16: the entry points below that take a `dtype`, fresco_adain, fresco_chan_mean_std, fresco_ddpm_*, fresco_freeu_*, fresco_hed_fuse */
+#define FRESCO_BF16 2 /* bfloat16: the entry points below that take a `dtype`, fresco_adain, fresco_chan_mean_std, fresco_ddpm_*, fresco_freeu_*, fresco_hed_fuse, fresco_canny_hysteresis */
 
 /* library / build identification: "fresco_hip <version> gfx950" */
 const char* fresco_version(void);
@@ -664,6 +664,60 @@ int fresco_hed_side_pool(const float* h, const float* w, const float* bias /* ma
 int fresco_hed_fuse(const float* s1, const float* s2, const float* s3, const float* s4, const float* s5, uint8_t* out,
                     float* logit /* may be NULL */, void* cond /* may be NULL */, int cond_dtype, int n, int H, int W,
                     void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (m)  The EGNet saliency detector behind the background smoothing (src/EGNet/model.py, resnet.py; called by
+ * src/utils.py::get_saliency).  DESIGN.md section 13.  The network's convolutions are fresco_fn_gemm / fresco_fn_conv7_rgb
+ * calls (BatchNorm folded into weights and bias); these are the pieces around them.  Planes and range_flag as in section (l).
+ * Same inputs give bit-identical outputs (no float atomics).
+ *   fresco_egnet_input     : frames (n, H, W, 3) uint8 -> cv2sod's tensor as NHWC fp32 rows (n, H / 2, W / 2, 3): channel c
+ *     minus (104.00699, 116.66877, 122.67892)[c], then the mean of each 2 x 2 block = F.interpolate(scale_factor=0.5,
+ *     bilinear); the block sum is exact and (sum / 4 - mean) is rounded to fp32 once; an odd last row / column is dropped.
+ *   fresco_egnet_pool      : MaxPool2d(3, stride 2, padding 1, ceil_mode=True) on x (n, H, W, 64) fp32 NHWC -> the planes
+ *     of the pooled map, (n, OH, OW, 64), and its fp32 values where `out` is given; OH follows PyTorch's rule (ceil, minus
+ *     one where the last window would start beyond the input and its left padding).
+ *   fresco_egnet_resize_add: F.interpolate(x, (H, W), bilinear, align_corners=True) on x (n, h, w, C) fp32 NHWC [+ addend
+ *     (n, H, W, C)] [ReLU] -> out fp32 and / or the planes, C % 32 == 0, C <= 512.  The source position d (h - 1) / (H - 1)
+ *     is a quotient and a remainder of integers (exact taps, the weight rounded once); h == H and w == W copies x exactly.
+ *   fresco_egnet_saliency  : logit (n, h, w) fp32 -> align_corners=True resize to (Hs, Ws), 1 / (1 + expf(-x)), k x k box
+ *     sum with replicate padding (added in row order), clamp to [0, 1], 1 - x: out (n, 1, Hs, Ws) fp32; logit_out
+ *     (n, Hs, Ws) (optional): the resized logit.  k odd, <= 15.
+ * FRESCO_EUNSUPPORTED: C outside the above, H or W < 2 (input), k even or > 15, n H W >= 2^31, a resized side > 32768.  FRESCO_EINVAL: null pointers,
+ * non-positive sizes or scale, fp32 rows read in 16-byte pieces not 16-byte aligned, planes not 8-byte aligned.  All before
+ * any launch.
+ * ------------------------------------------------------------------------------------------ */
+int fresco_egnet_input(const uint8_t* frames, float* out, int n, int H, int W, void* stream);
+int fresco_egnet_pool(const float* x, float* out /* may be NULL */, void* out_hi, void* out_lo, int n, int H, int W, int C,
+                      float split_scale, int32_t* range_flag, void* stream);
+int fresco_egnet_resize_add(const float* x, const float* addend /* may be NULL */, float* out /* may be NULL */,
+                            void* out_hi /* may be NULL */, void* out_lo, int n, int h, int w, int H, int W, int C, int relu,
+                            float split_scale, int32_t* range_flag, void* stream);
+int fresco_egnet_saliency(const float* logit, float* out, float* logit_out /* may be NULL */, int n, int h, int w, int Hs,
+                          int Ws, int k, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (n)  The Canny annotator of the ControlNet condition (`controlnet_type: canny`): OpenCV's generic
+ * Canny(src, low, high, apertureSize = 3, L2gradient = false) on 8-bit 3-channel frames, batched
+ * (reference: src/ControlNet/annotator/canny/__init__.py; DESIGN.md section 14 has the rules).  All integer: same inputs give
+ * the same bits.
+ *   fresco_canny_workspace_bytes: what fresco_canny_hysteresis needs for (n, H, W); 0 for sizes the calls refuse.
+ *   fresco_canny_classify  : frames (n, H, W, 3) uint8 -> cls (n, H, W) uint8: 0 (no edge), 1 (weak: a local maximum of
+ *     the gradient magnitude above `low`), 2 (strong: above `high` as well).  3 x 3 Sobel per channel with replicated
+ *     borders, |dx| + |dy|, the channel of the largest magnitude (the first on ties), zero magnitude outside the frame,
+ *     non-maximum suppression along the quantised gradient direction.  low > high: the two are swapped.  One launch.
+ *   fresco_canny_hysteresis: cls -> out (n, H, W) uint8: 255 on every class 1 / 2 pixel whose 8-connected component of
+ *     class 1 / 2 pixels holds a class 2 pixel, else 0 (a class byte >= 3 counts as 0; frames are independent).  cond,
+ *     when given: the ControlNet condition (n, 3, H, W) of cond_dtype (FRESCO_F16 / FRESCO_BF16 / FRESCO_F32),
+ *     ((out / 255) * 2 - 1) * 0.5 + 0.5 in fp32 in that order, rounded once -- what fresco_hed_fuse writes.  Union-find
+ *     labelling in four launches whatever the picture; no host loop, no read-back, no synchronisation.
+ * FRESCO_EINVAL: null frames / cls / out / workspace, non-positive n / H / W, a workspace not 4-byte aligned or a cond not
+ * aligned to its element, an unknown cond_dtype with a non-null cond.  FRESCO_EUNSUPPORTED: n H W >= 2^31.
+ * FRESCO_EWORKSPACE: a short workspace.  All before any launch.
+ * ------------------------------------------------------------------------------------------ */
+size_t fresco_canny_workspace_bytes(int n, int H, int W);
+int fresco_canny_classify(const uint8_t* frames, uint8_t* cls, int n, int H, int W, int low, int high, void* stream);
+int fresco_canny_hysteresis(const uint8_t* cls, uint8_t* out, void* cond /* may be NULL */, int cond_dtype, void* workspace,
+                            size_t workspace_bytes, int n, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

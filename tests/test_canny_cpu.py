@@ -1,10 +1,8 @@
 """fresco_amd's Canny detector without a GPU: the numpy restatement of the rules (tests/canny_model.py) on the hand cases and
 its threshold handling, the proof that the shared inputs can tell the rules apart, the C entry points on the header /
-binding surface of their own library and their argument checks (fake pointers: every check answers before any HIP call),
+binding surface of the library and their argument checks (fake pointers: every check answers before any HIP call),
 the Python surface, and -- only where cv2 can be imported -- the restatement against a real OpenCV."""
 import ctypes
-import os
-import re
 import types
 
 import numpy as np
@@ -13,7 +11,6 @@ import torch
 
 import canny_model as M
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("fresco_canny_workspace_bytes", "fresco_canny_classify", "fresco_canny_hysteresis")
 EINVAL, EUNSUPPORTED, EWORKSPACE = -1, -2, -3
 NATURAL = [(case, setting) for case in M.NATURAL_CASES for setting in M.NATURAL_SETTINGS]
@@ -85,61 +82,27 @@ def test_uniform_noise_would_not_do():
 
 
 # ---- the C surface
-def _canny_prototypes(surface):
-    """the prototypes of include/fresco_canny.h, parsed as the existing surface test parses fresco_hip.h"""
-    header = open(os.path.join(ROOT, "include", "fresco_canny.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    header = re.sub(r"^\s*#.*$", "", header, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(fresco_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header):
-        assert name not in protos, name
-        protos[name] = (surface.SCALARS[ret.split()[-1]], [surface._ctype(a) for a in params.split(",")])
-    return protos
-
-
 def test_entry_points_are_on_the_c_abi_surface():
-    """header prototypes == binding == exported functions, argument lists included; libfresco_hip.so keeps its surface"""
+    """per new symbol: the header's prototype (include/fresco_hip.h, section n) is the binding's, argument lists included, and
+    libfresco_hip.so exports it; tests/test_capi_surface_cpu.py compares header, binding and exports as whole sets"""
     import test_capi_surface_cpu as surface
     from fresco_amd import _lib
-    protos = _canny_prototypes(surface)
-    assert set(protos) == set(NEW_SYMBOLS)
-    exported = surface._exported_fresco_functions(_lib.CANNY_LIB_PATH)
+    protos = surface._prototypes()
+    exported = surface._exported_fresco_functions(_lib.LIB_PATH)
+    assert {n for n in protos if "canny" in n} == set(NEW_SYMBOLS)
     assert {n for n in exported if "canny" in n} == set(NEW_SYMBOLS)
-    assert {"fresco_version", "fresco_last_error"} <= exported
-    assert set(_lib.CANNY_SIGNATURES) == set(NEW_SYMBOLS) | {"fresco_version", "fresco_last_error"}
     for name in NEW_SYMBOLS:
-        res, args = _lib.CANNY_SIGNATURES[name]
+        res, args = _lib.SIGNATURES[name]
         assert res is protos[name][0] and list(args) == protos[name][1], name
-        assert name not in _lib.SIGNATURES and name not in _lib.EGNET_SIGNATURES
-    assert _lib.CANNY_SIGNATURES["fresco_canny_workspace_bytes"][0] is ctypes.c_size_t
-    assert _lib.CANNY_SIGNATURES["fresco_canny_classify"][0] is ctypes.c_int
-    assert _lib.load_canny().fresco_version() == _lib.load().fresco_version()
-    assert not [n for n in surface._exported_fresco_functions(_lib.LIB_PATH) if "canny" in n]
+    assert _lib.SIGNATURES["fresco_canny_workspace_bytes"][0] is ctypes.c_size_t
+    assert _lib.SIGNATURES["fresco_canny_classify"][0] is ctypes.c_int
+    assert _lib.SIGNATURES["fresco_canny_hysteresis"][0] is ctypes.c_int
     surface.test_binding_matches_the_header_prototypes()
-
-
-def test_a_stale_canny_library_is_refused(monkeypatch):
-    from fresco_amd import _lib
-    lib = _lib.load_canny()
-
-    class Stale:
-        def __getattr__(self, name):
-            return getattr(lib, name)
-
-        @staticmethod
-        def fresco_version():
-            return b"fresco_hip 0.5.0 gfx950"
-
-    monkeypatch.setattr(_lib, "_canny", None)
-    monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: Stale())
-    with pytest.raises(_lib.FrescoHipError, match="stale build"):
-        _lib.load_canny()
-    assert _lib._canny is None
 
 
 def test_entry_points_check_their_arguments_before_any_launch():
     from fresco_amd import _lib
-    lib = _lib.load_canny()
+    lib = _lib.load()
     p = 4096  # fake, aligned, never touched
     n, H, W = 2, 70, 75
     need = lib.fresco_canny_workspace_bytes(n, H, W)

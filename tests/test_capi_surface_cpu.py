@@ -83,7 +83,23 @@ def test_retired_names_are_gone(lib):
         assert name not in _lib.SIGNATURES
     exported = _exported_fresco_functions(fresco_amd.LIB_PATH)
     assert exported == set(_lib.SIGNATURES), exported ^ set(_lib.SIGNATURES)
-    assert len(exported) == 71  # 84 - 14 retired + fresco_gram_target_workspace_bytes
+    assert len(exported) == 78  # 84 - 14 retired + fresco_gram_target_workspace_bytes = 71, + 4 egnet + 3 canny
+
+
+def test_one_library_holds_the_process_wide_state():
+    """fresco_amd/lib holds one libfresco_*.so, and fresco_version / fresco_last_error are each exported once among its
+    files: a second library would carry its own last error, dynamic-LDS table, CU cache and fresco_prof_* recorder"""
+    import glob
+    lib_dir = os.path.join(ROOT, "fresco_amd", "lib")
+    assert glob.glob(os.path.join(lib_dir, "libfresco_*.so")) == [os.path.join(lib_dir, "libfresco_hip.so")]
+    exporters = {"fresco_version": [], "fresco_last_error": []}
+    for name in sorted(os.listdir(lib_dir)):
+        path = os.path.join(lib_dir, name)
+        if os.path.isfile(path) and open(path, "rb").read(6) == b"\x7fELF\x02\x01":
+            for symbol in exporters:
+                if symbol in _exported_fresco_functions(path):
+                    exporters[symbol].append(name)
+    assert exporters == {"fresco_version": ["libfresco_hip.so"], "fresco_last_error": ["libfresco_hip.so"]}
 
 
 def test_attn_f32_mode_checks_without_a_device(lib):

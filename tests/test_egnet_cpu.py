@@ -1,7 +1,7 @@
 """fresco_amd.egnet without a GPU: the module tree against the reference's recorded state dict, the library-ops forward and
 its live-graph restatement against the records of the unmodified reference network (tests/golden/egnet_golden.npz), the
 float64 BatchNorm folding, the argument checks of get_saliency, the rebinding of patch_saliency, and the new C entry
-points on the header / binding surface of their own library."""
+points on the header / binding surface of the library."""
 import os
 import sys
 import types
@@ -194,64 +194,29 @@ def test_patch_saliency_rebinds_the_names(monkeypatch):
     assert model.build_model is egnet.build_model
 
 
-def _egnet_prototypes(surface):
-    """the prototypes of include/fresco_egnet.h, parsed as the existing surface test parses fresco_hip.h"""
-    import re
-    header = open(os.path.join(ROOT, "include", "fresco_egnet.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
-    header = re.sub(r"^\s*#.*$", "", header, flags=re.M)
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w\s]*?\*?)\s*\b(fresco_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header):
-        assert ret.split()[-1] == "int" and name not in protos, name
-        protos[name] = [surface._ctype(a) for a in params.split(",")]
-    return protos
-
-
 def test_new_entry_points_are_on_the_c_abi_surface():
-    """The four kernels are a library of their own, libfresco_egnet.so with include/fresco_egnet.h: libfresco_hip.so keeps
-    the surface tests/test_capi_surface_cpu.py pins (that test, unedited, still compares fresco_hip.h, the binding and the
-    exports as whole sets -- and sees fresco_fn_gemm's dilation argument).  The same three-way comparison for the new
-    library: header prototypes == binding == exported functions, argument lists included."""
+    """The four entry points are part of libfresco_hip.so and include/fresco_hip.h (section m), which
+    tests/test_capi_surface_cpu.py compares as whole sets: header prototypes == binding == exported functions.  Per new
+    symbol here: the header's argument list is the binding's, the return type is int, the symbol is exported -- and
+    fresco_fn_gemm carries its dilation argument."""
     import ctypes
     import test_capi_surface_cpu as surface
     from fresco_amd import _lib
-    protos = _egnet_prototypes(surface)
-    assert set(protos) == set(NEW_SYMBOLS)
-    exported = surface._exported_fresco_functions(_lib.EGNET_LIB_PATH)
-    bound = set(_lib.EGNET_SIGNATURES)
-    assert set(NEW_SYMBOLS) <= exported and bound == set(NEW_SYMBOLS) | {"fresco_version", "fresco_last_error"}
-    assert not [n for n in exported if "egnet" in n and n not in NEW_SYMBOLS]
+    protos = surface._prototypes()
+    exported = surface._exported_fresco_functions(_lib.LIB_PATH)
+    assert {n for n in protos if "egnet" in n} == set(NEW_SYMBOLS)
+    assert {n for n in exported if "egnet" in n} == set(NEW_SYMBOLS)
     for name in NEW_SYMBOLS:
-        assert _lib.EGNET_SIGNATURES[name][0] is ctypes.c_int and list(_lib.EGNET_SIGNATURES[name][1]) == protos[name], name
-        assert name not in _lib.SIGNATURES
-    assert _lib.load_egnet().fresco_version() == _lib.load().fresco_version()
+        assert protos[name][0] is ctypes.c_int, name
+        assert _lib.SIGNATURES[name][0] is ctypes.c_int and list(_lib.SIGNATURES[name][1]) == protos[name][1], name
     surface.test_binding_matches_the_header_prototypes()
-    gemm = surface._prototypes()["fresco_fn_gemm"][1]
+    gemm = protos["fresco_fn_gemm"][1]
     assert len(gemm) == 33 and gemm[17:25] == [ctypes.c_int] * 8  # n_img, H, W, kh, kw, stride, pad, dilation
-
-
-def test_a_stale_egnet_library_is_refused(monkeypatch):
-    from fresco_amd import _lib
-    lib = _lib.load_egnet()
-
-    class Stale:
-        def __getattr__(self, name):
-            return getattr(lib, name)
-
-        @staticmethod
-        def fresco_version():
-            return b"fresco_hip 0.5.0 gfx950"
-
-    monkeypatch.setattr(_lib, "_egnet", None)
-    monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: Stale())
-    with pytest.raises(_lib.FrescoHipError, match="stale build"):
-        _lib.load_egnet()
-    assert _lib._egnet is None
 
 
 def test_entry_points_check_their_arguments_before_any_launch():
     from fresco_amd import _lib
-    lib, main = _lib.load_egnet(), _lib.load()
+    lib = _lib.load()
     p = 4096  # fake, aligned, never touched
     EINVAL, EUNSUPPORTED = -1, -2
     assert lib.fresco_egnet_input(None, p, 1, 64, 64, None) == EINVAL
@@ -271,8 +236,8 @@ def test_entry_points_check_their_arguments_before_any_launch():
     assert lib.fresco_egnet_saliency(p, p, None, 1, 8, 8, 32, 32, 17, None) == EUNSUPPORTED
     assert lib.fresco_egnet_saliency(p, p, None, 1, 8, 0, 32, 32, 7, None) == EINVAL
     # the GEMM's dilation: checked like stride and pad
-    gemm = lambda dil, M_=25: main.fresco_fn_gemm(p, p, 64, p, p, None, p, None, None, 64, 64, M_, 64, 9 * 64, 0, 1.0, 64.0,  # noqa: E731
-                                                 1, 5, 5, 3, 3, 1, 2, dil, None, p, None, None, None, 0, 0, None)
+    gemm = lambda dil, M_=25: lib.fresco_fn_gemm(p, p, 64, p, p, None, p, None, None, 64, 64, M_, 64, 9 * 64, 0, 1.0, 64.0,  # noqa: E731
+                                                1, 5, 5, 3, 3, 1, 2, dil, None, p, None, None, None, 0, 0, None)
     assert gemm(0) == EINVAL
     assert gemm(3) == EINVAL      # 5 + 4 - 6 - 1 + 1 = 3 x 3 outputs, not M = 25
     assert gemm(5) == EINVAL      # a window wider than the padded map

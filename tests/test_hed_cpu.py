@@ -182,4 +182,4 @@ def test_wrappers_raise_on_the_host():
     with pytest.raises(FrescoHipError):
         ops.hed_fuse([f32(1, 16 >> k, 16 >> k) for k in range(5)])
     with pytest.raises(ValueError):
-        ops._hed_scale(48.0)
+        ops._split_scale(48.0)
