@@ -1,5 +1,7 @@
 """fresco_amd's Canny detector without a GPU: the numpy restatement of the rules (tests/canny_model.py) on the hand cases and
-its threshold handling, the proof that the shared inputs can tell the rules apart, the C entry points on the header /
+its threshold handling, the proof that the shared inputs can tell the rules apart -- the eight rule variants of classify, and
+fourteen defects of the two union passes on the class maps the GPU tests use --, the flood fill against the union model and,
+where scipy can be imported, against scipy's labelling, the C entry points on the header /
 binding surface of the library and their argument checks (fake pointers: every check answers before any HIP call),
 the Python surface, and -- only where cv2 can be imported -- the restatement against a real OpenCV."""
 import ctypes
@@ -72,6 +74,131 @@ def test_the_inputs_can_tell_the_rules_apart(case, setting):
         kept, dropped = M.weak_fate(f, low, high)
         print("%s std %g: weak kept %.1f %%, weak dropped %.1f %%" % (M.case_id(case), std, 100 * kept, 100 * dropped))
         assert kept >= 0.02 and dropped >= 0.02
+
+
+def _gpu_class_maps():
+    """name -> class map, for every map the two GPU files hand to the hysteresis kernels by name"""
+    import test_gpu_canny as small
+    import test_gpu_canny_fullsize as full
+    maps = {name: make() for name, make in small.CLASS_MAPS.items()}
+    maps.update({"many_tiles_" + name: make() for name, make in full.MANY_TILES.items()})
+    maps["corner_patterns"] = M.corner_patterns()
+    maps["all_3x3"] = M.all_3x3_class_maps()
+    return maps
+
+
+def _seam_maps():
+    import test_gpu_canny as small
+    maps = {name: make() for name, make in small.SEAM_MAPS.items()}
+    maps["corner_patterns"] = M.corner_patterns()
+    return maps
+
+
+def test_union_model_equals_hysteresis_on_every_map():
+    """the two union passes as the kernels specify them label what the flood fill labels"""
+    for name, cls in _gpu_class_maps().items():
+        want = M.hysteresis(cls)
+        got = M.union_hysteresis(cls)
+        assert got.dtype == np.uint8 and got.shape == want.shape
+        assert np.array_equal(got, want), (name, int((got != want).sum()))
+    one = M.random_classes(1, 70, 75, 0.45, 0.004, seed=5)[0]
+    assert np.array_equal(M.union_hysteresis(one), M.hysteresis(one))  # (H, W) as well as (n, H, W)
+
+
+def test_the_maps_can_tell_the_union_defects_apart():
+    """each named defect of the union passes (one link or one group of border pixels left out) changes a pixel of some
+    small class map of the GPU tests -- and of some seam map (the anti-staircases, the sparse random map, the corner
+    patterns), which cover all of them by themselves; the sparse random map alone shows each one through 3 pixels or more"""
+    import test_gpu_canny as small
+    assert len(M.UNION_DEFECT_NAMES) == 14 and len(set(M.UNION_DEFECT_NAMES)) == 14
+    seam = _seam_maps()
+    maps = {name: make() for name, make in small.CLASS_MAPS.items()}
+    maps.update(seam)
+    base = {name: M.hysteresis(cls) for name, cls in maps.items()}
+    for defect in M.UNION_DEFECT_NAMES:
+        seen = {name: int((M.union_hysteresis(cls, defect) != base[name]).sum()) for name, cls in maps.items()}
+        print(defect, {k: v for k, v in seen.items() if v})
+        assert any(seen[name] for name in small.CLASS_MAPS), defect
+        assert any(seen[name] for name in seam), defect
+        assert seen["random_sparse"] >= 3, (defect, seen["random_sparse"])
+    # the link nothing saw before these maps: NE from a tile's top-right pixel into the tile diagonally above
+    d = "border_ne_not_across_corner"
+    assert int((M.union_hysteresis(maps["anti_staircase_64"], d) != base["anti_staircase_64"]).sum()) == 32
+    old = ("serpentine", "serpentine_unseeded", "staircase", "checkerboard", "all_weak", "all_strong", "all_zero",
+           "two_blobs", "three_frames", "odd_bytes", "random_near_percolation")
+    assert all(np.array_equal(M.union_hysteresis(maps[name], d), base[name]) for name in old)
+
+
+def test_hysteresis_model_equals_scipy_labelling():
+    """rule 5 from an independent implementation: scipy's labelling of the class 1 / 2 pixels with the 3 x 3 structure"""
+    ndimage = pytest.importorskip("scipy.ndimage")
+    for name, cls in _gpu_class_maps().items():
+        want = np.zeros(cls.shape, np.uint8)
+        for f, c in enumerate(cls):
+            c = np.where(c <= 2, c, 0)
+            lab, count = ndimage.label(c > 0, structure=np.ones((3, 3), int))
+            keep = np.zeros(count + 1, bool)
+            keep[lab[c == 2]] = True
+            keep[0] = False
+            want[f] = keep[lab] * 255
+        assert np.array_equal(M.hysteresis(cls), want), name
+
+
+def test_new_maps_are_what_they_are_for():
+    a = M.anti_staircase(64, 64)
+    assert a[0, 63] == 2 and int((a > 0).sum()) == 64 and a[31, 32] == 1 and a[32, 31] == 1  # the step across the corner
+    for c in (M.serpentine(seed="last"), M.line(70, 75), M.line(70, 75, vertical=True), M.line(1, 97), M.line(97, 1, True)):
+        assert int((c == 2).sum()) == 1 and np.flatnonzero(c)[-1] == np.flatnonzero(c == 2)[0]
+        assert np.array_equal(M.hysteresis(c) == 255, c > 0)
+    assert np.argwhere(M.serpentine(256, 256, seed="last") == 2).tolist() == [[255, 0]]
+    for H, W in ((70, 75), (256, 256)):
+        sp = M.spiral(H, W)
+        count = int((sp > 0).sum())
+        assert 0.45 * H * W < count < 0.55 * H * W and int((sp == 2).sum()) == 1 and sp[0, 0] == 1
+        assert np.array_equal(M.hysteresis(sp) == 255, sp > 0)
+        # one path and no way round: cut in its first arm, the inner seed lights all but the cut-off piece, the outer seed
+        # that piece alone
+        for seed, lit in (("last", count - 1 - W // 2), ("first", W // 2)):
+            cut = M.spiral(H, W, seed=seed)
+            cut[0, W // 2] = 0
+            assert int((M.hysteresis(cut) == 255).sum()) == lit
+        assert not M.hysteresis(M.spiral(H, W, seed=False)).any()
+    cp = M.corner_patterns()
+    assert cp.shape == (11264, 34, 34) and cp.dtype == np.uint8
+    assert not cp[:, :30].any() and not cp[:, :, :30].any() and int((cp == 2).reshape(len(cp), -1).sum(1).max()) == 1
+    for k, (r0, c0) in enumerate(((30, 30), (30, 31), (31, 30), (31, 31))):  # the four cuts, 2 816 different maps at each
+        block = cp[2816 * k:2816 * (k + 1)]
+        assert len({c.tobytes() for c in block}) == 2816 and block[-1, r0:r0 + 3, c0:c0 + 3].all()
+    pool = M.all_3x3_class_maps()
+    assert pool.shape == (19683, 3, 3) and len({c.tobytes() for c in pool}) == 19683 and pool.max() == 2
+
+
+def test_the_large_gradient_frames_reach_the_ends_of_the_range():
+    """the blocky frames reach dx, dy = +-1020 and m = 1530, take each of the three NMS branches with a component above 512,
+    and hold weak and strong pixels at 1000 / 1500; on the uniform frame at 500 / 900 every rule variant changes a pixel"""
+    for f in M.blocky(2, 70, 75, 3, seed=1):
+        dx, dy = M.gradients(f)
+        assert dx.min() == -1020 and dx.max() == 1020 and dy.min() == -1020 and dy.max() == 1020
+        assert (np.abs(dx) + np.abs(dy)).max() == 1530
+        branch, big = M.nms_branch(dx, dy), np.maximum(np.abs(dx), np.abs(dy)) > 512
+        c = M.classify(f, 1000, 1500)
+        for k in range(3):
+            assert (big & (branch == k) & (c > 0)).any(), k
+        print("blocky at 1000 / 1500: %d weak, %d strong" % (int((c == 1).sum()), int((c == 2).sum())))
+        assert (c == 1).sum() > 500 and (c == 2).sum() > 250
+    c = M.classify(M.blocky(1, 70, 75, 3, seed=1)[0], 1000, 1500)
+    assert (int((c == 1).sum()), int((c == 2).sum())) == (1139, 557)
+    u = M.uniform(1, 70, 75, seed=0)[0]
+    dx, dy = M.gradients(u)
+    assert dx.max() == 885 and dx.min() < -800 and dy.max() > 800 and dy.min() < -800
+    base = M.classify(u, 500, 900)
+    assert (base == 1).sum() > 1000 and (base == 2).sum() > 200
+    for name in M.VARIANT_NAMES:
+        assert int((M.classify(u, 500, 900, name) != base).sum()) >= 1, name
+    for d in ("right", "left", "down", "up"):
+        dx, dy = M.gradients(M.step(70, 75, d, 33))
+        want = {"right": (0, 1020, 0, 0), "left": (-1020, 0, 0, 0), "down": (0, 0, 0, 1020), "up": (0, 0, -1020, 0)}[d]
+        assert (dx.min(), dx.max(), dy.min(), dy.max()) == want
 
 
 def test_uniform_noise_would_not_do():
