@@ -694,12 +694,17 @@ def _check_permutations(owner, fwd_map, HW):
     _check_once(("perm", owner.data_ptr(), tuple(owner.shape), owner._version), owner, run)
 
 
+def _prep_fwd_map(fwd_map, N, HW):
+    """the kernels read the row table as raw contiguous (N, HW) int64 words (N = -1: as many frames as it holds)"""
+    fwd_map = fwd_map.reshape(N, HW)
+    if fwd_map.dtype != torch.int64:
+        fwd_map = fwd_map.to(torch.int64)
+    return fwd_map.contiguous()
+
+
 def _prep_maps(fwd_map, mask, N, HW):
     if fwd_map is not None:
-        fwd_map = fwd_map.reshape(N, HW)
-        if fwd_map.dtype != torch.int64:
-            fwd_map = fwd_map.to(torch.int64)
-        fwd_map = fwd_map.contiguous()
+        fwd_map = _prep_fwd_map(fwd_map, N, HW)
     mask = mask.reshape(-1, N, N)
     if mask.dtype == torch.bool:
         mask = mask.contiguous().view(torch.uint8)
@@ -744,6 +749,10 @@ def temporal_pack(q, k, v, fwd_map, chunk, n_loc, f0, world):
     q, q_ld, _ = _rows(q)
     k, k_ld, _ = _rows(k)
     v, v_ld, _ = _rows(v)
+    fwd_map = _prep_fwd_map(fwd_map, -1, HW)
+    if fwd_map.shape[0] < f0 + n_loc:
+        raise ValueError("fresco_amd.temporal_pack: fwd_map has %d frames, frames [%d, %d) asked for"
+                         % (fwd_map.shape[0], f0, f0 + n_loc))
     buf = torch.empty((world, n_loc, chunk, HW // world, 3 * C), dtype=q.dtype, device=q.device)
     rc = _lib.load().fresco_temporal_pack(q.data_ptr(), k.data_ptr(), v.data_ptr(), fwd_map.data_ptr(), buf.data_ptr(),
                                           chunk, n_loc, f0, HW, C, world, q_ld, k_ld, v_ld, _stream())
@@ -778,6 +787,10 @@ def temporal_unpack(buf, fwd_map, chunk, n_loc, f0, world):
         raise TypeError("fresco_amd.temporal_unpack: buf must be fp16 or bf16 (got %s)" % buf.dtype)
     w, nl, ch, Pw, C = buf.shape
     HW = Pw * world
+    fwd_map = _prep_fwd_map(fwd_map, -1, HW)
+    if fwd_map.shape[0] < f0 + n_loc:
+        raise ValueError("fresco_amd.temporal_unpack: fwd_map has %d frames, frames [%d, %d) asked for"
+                         % (fwd_map.shape[0], f0, f0 + n_loc))
     out = torch.empty((chunk * n_loc, HW, C), dtype=buf.dtype, device=buf.device)
     rc = _lib.load().fresco_temporal_unpack(buf.contiguous().data_ptr(), fwd_map.data_ptr(), out.data_ptr(), chunk,
                                             n_loc, f0, HW, C, world, _stream())
