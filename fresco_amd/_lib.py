@@ -117,6 +117,16 @@ SIGNATURES = {
     "fresco_canny_hysteresis": (_i, [_vp, _vp, _vp, _i, _vp, _sz, _i, _i, _i, _vp]),
 }
 
+# the key-frame selection kernels (csrc/keyframe.hip) in the same library, declared in include/fresco_keyframe.h: named
+# keyframe_*, beside the fresco_* surface that SIGNATURES and include/fresco_hip.h describe; bound on the same handle
+KEYFRAME_SIGNATURES = {
+    "keyframe_resize_table_bytes": (_sz, [_i, _i, _i, _i]),
+    "keyframe_resize_table": (_i, [_i, _i, _i, _i, _vp, _sz]),
+    "keyframe_resize_area_u8": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "keyframe_workspace_bytes": (_sz, [_i, _i, _i]),
+    "keyframe_frame_errors": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -133,7 +143,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise FrescoHipError("fresco_amd: cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

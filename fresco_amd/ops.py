@@ -1233,6 +1233,81 @@ def canny_hysteresis(cls, cond_dtype=None):
 
 
 # ---------------------------------------------------------------------------------------------
+# key-frame selection (src/keyframe_selection.py: resize_image, cv2.GaussianBlur, mse_loss per frame) (csrc/keyframe.hip)
+# ---------------------------------------------------------------------------------------------
+def _u8_frames(frames, name):
+    _dense(frames, name, torch.uint8)
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise ValueError("%s must be (n, H, W, 3), got %s" % (name, tuple(frames.shape)))
+    return frames
+
+
+_AREA_TABLES = {}      # (H0, W0, H, W, device) -> the coverage tables of the geometry on that device, int32 words
+_AREA_TABLES_MAX = 32  # geometries kept; the oldest goes first
+
+
+def _area_table(H0, W0, H, W, device):
+    """the two coverage tables of INTER_AREA for one geometry: built on the host by the library (keyframe_resize_table),
+    uploaded once and kept; the kernel walks them in their order"""
+    key = (H0, W0, H, W, str(device))
+    tab = _AREA_TABLES.get(key)
+    if tab is None:
+        lib = _lib.load()
+        what = "keyframe_resize_table(%dx%d->%dx%d)" % (H0, W0, H, W)
+        need = lib.keyframe_resize_table_bytes(H0, W0, H, W)
+        if need == 0:  # the geometry is refused: let the call say why
+            _lib.check(lib.keyframe_resize_table(H0, W0, H, W, None, 0), what)
+            raise FrescoHipError("%s: no table for this geometry" % what)
+        host = (ctypes.c_int32 * (need // 4))()
+        _lib.check(lib.keyframe_resize_table(H0, W0, H, W, ctypes.addressof(host), need), what)
+        tab = torch.frombuffer(host, dtype=torch.int32).to(device)  # (a blocking copy: `host` may go afterwards)
+        while len(_AREA_TABLES) >= _AREA_TABLES_MAX:
+            _AREA_TABLES.pop(next(iter(_AREA_TABLES)))
+        _AREA_TABLES[key] = tab
+    return tab
+
+
+def resize_area_u8(frames, H, W):
+    """frames (n, H0, W0, 3) uint8 -> (n, H, W, 3) uint8: OpenCV's INTER_AREA where no side is enlarged; a side that would
+    be is refused (keyframe_resize_area_u8)"""
+    _u8_frames(frames, "resize_area_u8: frames")
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError("resize_area_u8: the size %d x %d is not positive" % (H, W))
+    _need_gpu(frames)
+    n, H0, W0, _ = frames.shape
+    tab = _area_table(H0, W0, H, W, frames.device)
+    out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=frames.device)
+    rc = _lib.load().keyframe_resize_area_u8(frames.data_ptr(), out.data_ptr(), tab.data_ptr(), tab.numel() * 4, n, H0, W0, H,
+                                             W, _stream())
+    _lib.check(rc, "keyframe_resize_area_u8(n=%d,%dx%d->%dx%d)" % (n, H0, W0, H, W))
+    return out
+
+
+def frame_sq_diffs(frames, carry=None):
+    """frames (n, H, W, 3) uint8, carry (H, W, 3) uint8 or None -> (n,) int64 on the device: entry i is the sum of squared
+    differences of the 9 x 9 blurred frames i - 1 and i (frame -1 is the carry; entry 0 is 0 without one)
+    (keyframe_frame_errors)"""
+    _u8_frames(frames, "frame_sq_diffs: frames")
+    n, H, W, _ = frames.shape
+    if carry is not None:
+        _dense(carry, "frame_sq_diffs: carry", torch.uint8, (H, W, 3))
+        if carry.device != frames.device:
+            raise ValueError("frame_sq_diffs: carry on %s, frames on %s" % (carry.device, frames.device))
+    _need_gpu(frames, carry)
+    lib = _lib.load()
+    need = lib.keyframe_workspace_bytes(n, H, W)
+    if need == 0:
+        raise FrescoHipError("frame_sq_diffs: frames of %d x %d x %d are outside what the kernels take (sides >= 5, "
+                             "n H W 3 < 2^40)" % (n, H, W))
+    ws = torch.empty(need // 8, dtype=torch.int64, device=frames.device)
+    out = torch.empty(n, dtype=torch.int64, device=frames.device)  # the kernel's uint64; the sums stay far below 2^63
+    rc = lib.keyframe_frame_errors(frames.data_ptr(), _ptr(carry), out.data_ptr(), ws.data_ptr(), need, n, H, W, _stream())
+    _lib.check(rc, "keyframe_frame_errors(n=%d,H=%d,W=%d)" % (n, H, W))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # feature optimisation (fp32)
 # ---------------------------------------------------------------------------------------------
 def _opt_args(cs, prep, target, chunk):
