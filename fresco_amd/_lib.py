@@ -127,6 +127,15 @@ KEYFRAME_SIGNATURES = {
     "keyframe_frame_errors": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
 }
 
+# the tap resizes (csrc/resize.hip: INTER_LANCZOS4, and INTER_AREA's rule where a side is enlarged), declared in
+# include/fresco_resize.h: named frame_resize_*, beside both pinned surfaces; bound on the same handle
+RESIZE_SIGNATURES = {
+    "frame_resize_table_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "frame_resize_table": (_i, [_i, _i, _i, _i, _i, _vp, _sz]),
+    "frame_resize_u8": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp]),
+}
+RESIZE_LANCZOS4, RESIZE_LINEAR_AREA = 0, 1  # FRAME_RESIZE_* of the header
+
 _lib = None
 
 
@@ -143,7 +152,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise FrescoHipError("fresco_amd: cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

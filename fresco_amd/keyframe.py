@@ -1,11 +1,11 @@
 """Key-frame selection (reference: src/keyframe_selection.py get_keyframe_ind, src/utils.py resize_image) with the per-frame
 work on the GPU.
 
-The reference runs, for every frame of the video, resize_image (cv2.resize, INTER_AREA) -> cv2.GaussianBlur(img, (9, 9), 0)
--> numpy2tensor(...).cuda() -> F.mse_loss(prev, cur).cpu(): one upload and one device synchronisation per frame.  Here a
-chunk of frames is uploaded once and goes through
+The reference runs, for every frame of the video, resize_image (cv2.resize, INTER_AREA or INTER_LANCZOS4) ->
+cv2.GaussianBlur(img, (9, 9), 0) -> numpy2tensor(...).cuda() -> F.mse_loss(prev, cur).cpu(): one upload and one device
+synchronisation per frame.  Here a chunk of frames is uploaded once and goes through
 
-    ops.resize_area_u8 (one launch) -> ops.frame_sq_diffs (two launches: the blur of both frames of every pair in LDS and
+    ops.resize_area_u8 or, where the geometry enlarges, ops.resize_taps_u8 (one launch) -> ops.frame_sq_diffs (two launches: the blur of both frames of every pair in LDS and
     the integer sum of their squared differences; the last resized frame is carried into the next chunk)
 
 and the sums of all chunks come back in one copy at the end.  The greedy choice over the error curve (select_keyframes)
@@ -41,20 +41,30 @@ def _check_batch(frames, what):
     return frames
 
 
-def resize_frames(frames, resolution=512):
-    """frames: uint8 (n, H0, W0, 3) on the GPU -> resize_image of every frame, uint8 (n, H, W, 3) on the GPU.  Only the
-    shrinking INTER_AREA case is built: k > 1 (the reference switches to Lanczos) and a side that the rounding to 64 would
-    enlarge raise NotImplementedError; there is no host fallback."""
+def resize_frames(frames, resolution=512, enlarge=False):
+    """frames: uint8 (n, H0, W0, 3) on the GPU -> resize_image of every frame, uint8 (n, H, W, 3) on the GPU.  By default
+    only the shrinking INTER_AREA case is taken: k > 1 (the reference switches to Lanczos) and a side that the rounding to
+    64 would enlarge raise NotImplementedError.  enlarge=True takes every geometry as resize_image and cv2.resize do
+    together: k > 1 -> INTER_LANCZOS4 on both sides, whatever each does; otherwise INTER_AREA, which is the area rule when no
+    side grows and its two-tap rule on both sides when one does.  There is no host fallback."""
     _check_batch(frames, "resize_frames")
     _, H0, W0, _ = frames.shape
     H, W, k = resize_size(H0, W0, resolution)
-    if k > 1:
-        raise NotImplementedError("resize_frames: %d x %d to resolution %s enlarges (k = %.4f > 1): the reference resizes "
-                                  "with INTER_LANCZOS4 there, which is not built" % (H0, W0, resolution, k))
-    if H > H0 or W > W0 or H <= 0 or W <= 0:
+    if H <= 0 or W <= 0:
         raise NotImplementedError("resize_frames: %d x %d to resolution %s gives %d x %d after the rounding to multiples "
-                                  "of 64; INTER_AREA that enlarges a side (or an empty image) is not built"
-                                  % (H0, W0, resolution, H, W))
+                                  "of 64; an empty image is not built" % (H0, W0, resolution, H, W))
+    if k > 1:
+        if not enlarge:
+            raise NotImplementedError("resize_frames: %d x %d to resolution %s enlarges (k = %.4f > 1): the reference "
+                                      "resizes with INTER_LANCZOS4 there, which only enlarge=True takes"
+                                      % (H0, W0, resolution, k))
+        return ops.resize_taps_u8(frames.contiguous(), H, W, ops.RESIZE_LANCZOS4)
+    if H > H0 or W > W0:
+        if not enlarge:
+            raise NotImplementedError("resize_frames: %d x %d to resolution %s gives %d x %d after the rounding to "
+                                      "multiples of 64; INTER_AREA that enlarges a side is another rule, which only "
+                                      "enlarge=True takes" % (H0, W0, resolution, H, W))
+        return ops.resize_taps_u8(frames.contiguous(), H, W, ops.RESIZE_LINEAR_AREA)
     return ops.resize_area_u8(frames.contiguous(), H, W)
 
 
@@ -64,7 +74,7 @@ def resize_image(input_image, resolution):
             or input_image.shape[2] != 3:
         raise TypeError("resize_image: the image is an (H, W, 3) uint8 array")
     frames = torch.from_numpy(np.ascontiguousarray(input_image)[None]).cuda()
-    return resize_frames(frames, resolution)[0].cpu().numpy()
+    return resize_frames(frames, resolution, enlarge=True)[0].cpu().numpy()
 
 
 def _as_chunk(chunk):
@@ -102,7 +112,7 @@ def _sq_diff_chunks(chunks, resolution, keep_frames, measure=True):
     for chunk in chunks:
         frames = _as_chunk(chunk)
         if resolution is not None:
-            frames = resize_frames(frames, resolution)
+            frames = resize_frames(frames, resolution, enlarge=True)
         if size is None:
             size = tuple(frames.shape[1:3])
         elif tuple(frames.shape[1:3]) != size:

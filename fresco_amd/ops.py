@@ -1284,6 +1284,52 @@ def resize_area_u8(frames, H, W):
     return out
 
 
+RESIZE_LANCZOS4, RESIZE_LINEAR_AREA = _lib.RESIZE_LANCZOS4, _lib.RESIZE_LINEAR_AREA
+_TAP_TABLES = {}      # (H0, W0, H, W, method, device) -> the tap table of the geometry on that device, int32 words
+_TAP_TABLES_MAX = 32  # geometries kept; the oldest goes first
+
+
+def _tap_table(H0, W0, H, W, method, device):
+    """the tap table of one geometry and method (per axis and output index the first source index and the 8 or 2 fixed-point
+    coefficients): built on the host by the library (frame_resize_table), uploaded once and kept"""
+    key = (H0, W0, H, W, method, str(device))
+    tab = _TAP_TABLES.get(key)
+    if tab is None:
+        lib = _lib.load()
+        what = "frame_resize_table(%dx%d->%dx%d, method %d)" % (H0, W0, H, W, method)
+        need = lib.frame_resize_table_bytes(H0, W0, H, W, method)
+        if need == 0:  # the geometry is refused: let the call say why
+            _lib.check(lib.frame_resize_table(H0, W0, H, W, method, None, 0), what)
+            raise FrescoHipError("%s: no table for this geometry" % what)
+        host = (ctypes.c_int32 * (need // 4))()
+        _lib.check(lib.frame_resize_table(H0, W0, H, W, method, ctypes.addressof(host), need), what)
+        tab = torch.frombuffer(host, dtype=torch.int32).to(device)  # (a blocking copy: `host` may go afterwards)
+        while len(_TAP_TABLES) >= _TAP_TABLES_MAX:
+            _TAP_TABLES.pop(next(iter(_TAP_TABLES)))
+        _TAP_TABLES[key] = tab
+    return tab
+
+
+def resize_taps_u8(frames, H, W, method):
+    """frames (n, H0, W0, 3) uint8 -> (n, H, W, 3) uint8 through OpenCV's fixed-point tap resizes: method RESIZE_LANCZOS4 is
+    cv2.INTER_LANCZOS4, RESIZE_LINEAR_AREA what cv2.INTER_AREA does when a side is enlarged.  A side that shrinks by more
+    than a factor 2 is refused (frame_resize_u8)"""
+    _u8_frames(frames, "resize_taps_u8: frames")
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0:
+        raise ValueError("resize_taps_u8: the size %d x %d is not positive" % (H, W))
+    if method not in (RESIZE_LANCZOS4, RESIZE_LINEAR_AREA):
+        raise ValueError("resize_taps_u8: method %r (RESIZE_LANCZOS4 or RESIZE_LINEAR_AREA)" % (method,))
+    _need_gpu(frames)
+    n, H0, W0, _ = frames.shape
+    tab = _tap_table(H0, W0, H, W, method, frames.device)
+    out = torch.empty(n, H, W, 3, dtype=torch.uint8, device=frames.device)
+    rc = _lib.load().frame_resize_u8(frames.data_ptr(), out.data_ptr(), tab.data_ptr(), tab.numel() * 4, n, H0, W0, H, W,
+                                     method, _stream())
+    _lib.check(rc, "frame_resize_u8(n=%d,%dx%d->%dx%d, method %d)" % (n, H0, W0, H, W, method))
+    return out
+
+
 def frame_sq_diffs(frames, carry=None):
     """frames (n, H, W, 3) uint8, carry (H, W, 3) uint8 or None -> (n,) int64 on the device: entry i is the sum of squared
     differences of the 9 x 9 blurred frames i - 1 and i (frame -1 is the carry; entry 0 is 0 without one)

@@ -13,7 +13,12 @@ tests/keyframe_model.py, in milliseconds per frame:
 Every mode is a child process of its own under a time limit; a child that fails ends the run.  Per mode: warm-up, then the
 median of five timed blocks (a host clock around 100 or 20 calls of 64 frames, ended by a device synchronise).
 
+--small runs the three package modes on 64 frames of 480 x 854 instead, a video whose short side is below 512: resize_image
+enlarges it to 512 x 896 through INTER_LANCZOS4 (the tap-resize kernel, eight taps per axis).  The 1080p `resident` leg is
+timed again in the same run for scale.  The reference's chain on that size is not measured (no cv2 here either).
+
     python tools/bench_keyframe.py        # writes profiles/keyframe_bench.json (--out FILE: elsewhere)
+    python tools/bench_keyframe.py --small   # writes profiles/keyframe_small_bench.json
 """
 import argparse
 import json
@@ -28,6 +33,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 N, H0, W0, RES = 64, 1080, 1920, 512
+SMALL_H0, SMALL_W0 = 480, 854
 CHUNK = 32
 MODES = ("resident", "from_host", "keys", "reference")
 LIMITS = dict(resident=240, from_host=240, keys=240, reference=480)  # seconds per child
@@ -48,7 +54,7 @@ def timed(fn, iters, blocks=5, warmup=2):
     return statistics.median(out) * 1e3 / N, [t * 1e3 / N for t in out]
 
 
-def child(mode):
+def child(mode, H0=H0, W0=W0):
     import numpy as np
     import torch
     import fresco_amd
@@ -56,7 +62,7 @@ def child(mode):
     if not torch.cuda.is_available():
         sys.exit("bench_keyframe.py needs a GPU")
     dev = "cuda:0"
-    host = M.synthetic_frames(1, N, H0, W0, block=48)
+    host = M.synthetic_frames(1, N, H0, W0, block=48 if H0 >= 1080 else 24)
     chunks = [host[i:i + CHUNK] for i in range(0, N, CHUNK)]
     res = dict(mode=mode, device=torch.cuda.get_device_name(0))
     if mode == "resident":
@@ -104,12 +110,18 @@ def child(mode):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "keyframe_bench.json"),
-                    help="the result as JSON goes here as well")
+    ap.add_argument("--out", default=None, help="the result as JSON goes here as well (default: profiles/keyframe_bench.json, "
+                    "with --small profiles/keyframe_small_bench.json)")
+    ap.add_argument("--small", action="store_true", help="the 480 x 854 legs (see above)")
     ap.add_argument("--mode", choices=MODES, default=None, help="(internal) run one mode in this process")
+    ap.add_argument("--size", nargs=2, type=int, default=(H0, W0), help="(internal) the frame size of that mode")
     args = ap.parse_args()
     if args.mode:
-        return child(args.mode)
+        return child(args.mode, *args.size)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "keyframe_small_bench.json" if args.small else "keyframe_bench.json")
+    if args.small:
+        return main_small(args)
     got = {}
     for mode in MODES:
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode], stdout=subprocess.PIPE,
@@ -135,6 +147,42 @@ def main():
         with open(args.out, "w") as f:
             json.dump(result, f, indent=1)
             f.write("\n")
+
+
+def run_mode(mode, size):
+    """one mode in a child process of its own under its time limit -> its result; a child that fails ends the run"""
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--size", str(size[0]), str(size[1])],
+                       stdout=subprocess.PIPE, timeout=LIMITS[mode], text=True)
+    if p.returncode != 0:
+        sys.exit("bench_keyframe.py: mode %s at %d x %d ended with status %d; nothing further is started"
+                 % (mode, size[0], size[1], p.returncode))
+    res = json.loads(p.stdout.strip().splitlines()[-1])
+    print(mode, size, res, flush=True)
+    return res
+
+
+def main_small(args):
+    small = (SMALL_H0, SMALL_W0)
+    got = {mode: run_mode(mode, small) for mode in ("resident", "from_host", "keys")}
+    big = run_mode("resident", (H0, W0))
+    result = dict(bench="keyframe_frame_errors_small", device=got["resident"]["device"], frames=N, chunk=CHUNK,
+                  height=SMALL_H0, width=SMALL_W0, resized=got["resident"]["size"], resize="INTER_LANCZOS4 (frame_resize_u8)",
+                  resident_ms_per_frame=got["resident"]["ms_per_frame"],
+                  from_host_ms_per_frame=got["from_host"]["ms_per_frame"],
+                  get_keyframe_ind_ms_per_frame=got["keys"]["ms_per_frame"], keys=got["keys"]["keys"],
+                  area_1080p_resident_ms_per_frame=big["ms_per_frame"], area_1080p_resized=big["size"],
+                  runs="per figure: 2 warm-up calls, then the median of 5 timed blocks of 100 (resident) or 20 calls of "
+                       "64 frames",
+                  reference_note="cv2 is not installed here: the reference's per-frame chain is unmeasured, no speed-up is "
+                                 "claimed",
+                  timed_blocks_ms_per_frame=dict(resident=got["resident"]["blocks_ms_per_frame"],
+                                                 from_host=got["from_host"]["blocks_ms_per_frame"],
+                                                 keys=got["keys"]["blocks_ms_per_frame"],
+                                                 area_1080p_resident=big["blocks_ms_per_frame"]))
+    print(json.dumps(result))
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
 
 
 if __name__ == "__main__":
