@@ -136,6 +136,23 @@ RESIZE_SIGNATURES = {
 }
 RESIZE_LANCZOS4, RESIZE_LINEAR_AREA = 0, 1  # FRAME_RESIZE_* of the header
 
+# the MiDaS depth annotator's kernels (csrc/midas.hip, and the stem's "same" origin in csrc/flownet.hip), declared in
+# include/fresco_midas.h: named midas_*, beside the pinned surfaces; bound on the same handle
+MIDAS_SIGNATURES = {
+    "midas_input": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "midas_stem_conv": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "midas_groupnorm_workspace_bytes": (_sz, [_i, _i, _i]),
+    "midas_groupnorm_stats": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _vp]),
+    "midas_groupnorm_apply": (_i, [_vp] * 9 + [_i] * 7 + [_f, _vp, _vp]),
+    "midas_pool": (_i, [_vp] * 4 + [_i, _i, _i, _i, _f, _vp, _vp]),
+    "midas_layernorm": (_i, [_vp] * 6 + [_i64, _i, _f, _f, _vp, _vp]),
+    "midas_tokens": (_i, [_vp] * 4 + [_i, _i, _i, _vp]),
+    "midas_head_merge": (_i, [_vp] * 4 + [_i, _i, _i, _f, _vp, _vp]),
+    "midas_rowbias_gelu": (_i, [_vp] * 5 + [_i64, _i, _i, _f, _vp, _vp]),
+    "midas_tail_workspace_bytes": (_sz, [_i, _i, _i]),
+    "midas_tail": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _sz, _i, _i, _i, _f, _f, _vp]),
+}
+
 _lib = None
 
 
@@ -152,7 +169,8 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise FrescoHipError("fresco_amd: cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
+            + list(MIDAS_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "fn_split.h"  // fn_split / fn_flag_range: how a producer writes a value into the (hi, lo) planes
 #include "lds_dma.h"
+#include "../../include/fresco_midas.h"  // midas_stem_conv: the stem kernel at the "same" padding origin
 
 namespace fresco {
 
@@ -638,6 +639,9 @@ constexpr int C7_ROWS = 9;     // input rows of two output rows
 constexpr int C7_K = 224, C7_WROW = 464;
 typedef uint32_t uintx4 __attribute__((ext_vector_type(4)));
 static_assert(C7_K == 28 * 8 && C7_WROW >= C7_K * 2 && (C7_WROW / 16) % 2 == 1, "stem weight rows: 28 pieces, odd LDS pitch");
+// PAD: rows / columns of zero padding BEFORE the map, the window origin (3: nn.Conv2d's padding 3; 2: the "same" padding of an
+// even side, 2 before and 3 after -- midas_stem_conv); what lies past the map is zero either way.
+template <int PAD>
 __global__ __launch_bounds__(512, 1) void fn_conv7_rgb_kernel(const float* __restrict__ x, const half_t* __restrict__ w_hi,
                                                               const half_t* __restrict__ w_lo, float* __restrict__ out,
                                                               double* __restrict__ stats, int H, int W, int OH, int OW,
@@ -667,8 +671,8 @@ __global__ __launch_bounds__(512, 1) void fn_conv7_rgb_kernel(const float* __res
             *reinterpret_cast<uintx4*>((pl ? wl : wh) + n * C7_WROW + pc * 16) = wv[k];
         }
     }
-    // ---- input rows: value e = 3 cx + ci of staged row ry is x[img][2 oy0 - 3 + ry][2 ox0 - 3 + cx][ci] (zero outside)
-    const int iy0 = oy0 * 2 - 3, ix0 = ox0 * 2 - 3;
+    // ---- input rows: value e = 3 cx + ci of staged row ry is x[img][2 oy0 - PAD + ry][2 ox0 - PAD + cx][ci] (zero outside)
+    const int iy0 = oy0 * 2 - PAD, ix0 = ox0 * 2 - PAD;
     // Value e of a staged row sits 3 ix0 + e floats into its input row (NHWC rows are contiguous): no division per address,
     // in-row test = 0 <= 3 ix0 + e < 3 W.  ALL of a thread's 36 loads are issued before the first split, unconditionally
     // (clamped offsets, zeroed afterwards): left as one loop with the test around the load hipcc waits for every value
@@ -967,11 +971,29 @@ extern "C" int fresco_fn_conv7_rgb(const float* x, const void* w_hi, const void*
     // fresco_fn_colstats_finish combines whole 256-row groups
     if (stats && (OW % 64 != 0 || ((int64_t)OH * OW) % 256 != 0)) return FRESCO_EUNSUPPORTED;
     const int lds = 2 * C7_ROWS * C7_PROW * 2 + 2 * 64 * C7_WROW;
-    if (int rc = allow_dyn_lds(&fn_conv7_rgb_kernel, lds)) return rc;
+    if (int rc = allow_dyn_lds(&fn_conv7_rgb_kernel<3>, lds)) return rc;
     hipStream_t st = as_stream(stream);
     ProfScope ps(FRESCO_PROF_FN_GEMM, n_img * OH * OW, 64, 147, 7, st);
-    hipLaunchKernelGGL(fn_conv7_rgb_kernel, dim3((OW + 255) / 256, (OH + 1) / 2, n_img), dim3(512), lds, st, x,
+    hipLaunchKernelGGL(fn_conv7_rgb_kernel<3>, dim3((OW + 255) / 256, (OH + 1) / 2, n_img), dim3(512), lds, st, x,
                        static_cast<const half_t*>(w_hi), static_cast<const half_t*>(w_lo), out, static_cast<double*>(stats), H, W,
+                       OH, OW, 64.f, 1.f / (64.f * 1024.f), range_flag);
+    return check_launch();
+}
+
+// The MiDaS backbone's stem (include/fresco_midas.h): the same kernel with the "same" padding of an even side, 2 before and 3
+// after: output pixel (oy, ox) reads rows 2 oy - 2 .. 2 oy + 4, OH = H / 2.
+extern "C" int midas_stem_conv(const float* x, const void* w_hi, const void* w_lo, float* out, int n, int H, int W,
+                               int32_t* range_flag, void* stream) {
+    if (!x || !w_hi || !w_lo || !out || n <= 0 || H <= 0 || W <= 0) return FRESCO_EINVAL;
+    if (H % 2 || W % 2) return FRESCO_EUNSUPPORTED;  // (an odd side pads 3 and 3: fresco_fn_conv7_rgb)
+    const int OH = H / 2, OW = W / 2;
+    if (n > 65535 || (OH + 1) / 2 > 65535) return FRESCO_EUNSUPPORTED;
+    const int lds = 2 * C7_ROWS * C7_PROW * 2 + 2 * 64 * C7_WROW;
+    if (int rc = allow_dyn_lds(&fn_conv7_rgb_kernel<2>, lds)) return rc;
+    hipStream_t st = as_stream(stream);
+    ProfScope ps(FRESCO_PROF_FN_GEMM, n * OH * OW, 64, 147, 7, st);
+    hipLaunchKernelGGL(fn_conv7_rgb_kernel<2>, dim3((OW + 255) / 256, (OH + 1) / 2, n), dim3(512), lds, st, x,
+                       static_cast<const half_t*>(w_hi), static_cast<const half_t*>(w_lo), out, static_cast<double*>(nullptr), H, W,
                        OH, OW, 64.f, 1.f / (64.f * 1024.f), range_flag);
     return check_launch();
 }

@@ -1,5 +1,6 @@
 """Weight operands of the split-fp16 dense layers (csrc/flownet.hip), cached per parameter version: what the flow network
-(gmflow.py), the HED annotator (hed.py) and the EGNet saliency detector (egnet.py) hand to ops.fn_gemm."""
+(gmflow.py), the HED annotator (hed.py), the EGNet saliency detector (egnet.py) and the MiDaS depth annotator (midas.py)
+hand to ops.fn_gemm."""
 import torch
 import torch.nn.functional as F
 
@@ -43,6 +44,28 @@ class WeightPlanes:
             w = w.reshape(w.shape[0], -1)
         with ops.fn_range_guard(w.device) as g:
             if kind == "stem":  # (64, 3, 7, 7) -> the (64, 224) layout of fresco_fn_conv7_rgb
+                val = ops.fn_conv7_weight(w)
+            else:
+                _, val = ops.fn_prep(w.contiguous(), scale=ops.FN_W_SCALE)
+        bad = g.tripped()  # (one host sync per parameter version)
+        self.out_of_range |= bad
+        self.cache[key] = (stamp, val, bad)
+        return val
+
+    def get_prepared(self, p, kind, tag, prepare):
+        """planes of prepare(p) -- a tensor in p's layout made from p alone (a weight-standardised convolution, a column
+        slice of a linear layer: MiDaS) -- cached per version of p under (kind, tag).  kind as in get()."""
+        key = (id(p), kind, tag)
+        hit = self.cache.get(key)
+        stamp = self._stamp(p)
+        if hit is not None and stamp is not None and hit[0] == stamp:
+            self.out_of_range |= hit[2]
+            return hit[1]
+        w = prepare(p.detach()).float()
+        if kind == "conv":
+            w = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+        with ops.fn_range_guard(w.device) as g:
+            if kind == "stem":
                 val = ops.fn_conv7_weight(w)
             else:
                 _, val = ops.fn_prep(w.contiguous(), scale=ops.FN_W_SCALE)

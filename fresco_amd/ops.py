@@ -1477,3 +1477,203 @@ def gram_target(x, workspace=None):
                                         _stream())
     _lib.check(rc, "fresco_gram_target")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# MiDaS depth annotator (src/ControlNet/annotator/midas): the pieces around fn_gemm / attention_f32 / egnet_resize_add
+# (csrc/midas.hip, include/fresco_midas.h)
+# ---------------------------------------------------------------------------------------------
+MIDAS_GN_CHANNELS = (64, 128, 256, 512, 1024)
+
+
+def _planes(rows, C, device, want):
+    if not want:
+        return None, None
+    return (torch.empty(rows, C, dtype=torch.float16, device=device), torch.empty(rows, C, dtype=torch.float16, device=device))
+
+
+def midas_input(frames):
+    """frames (n, H, W, 3) uint8 -> x / 127.5 - 1 as (n, H, W, 3) fp32 NHWC (midas_input)"""
+    _dense(frames, "midas_input: frames", torch.uint8)
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.numel() == 0:
+        raise ValueError("midas_input: frames must be (n, H, W, 3), got %s" % (tuple(frames.shape),))
+    _need_gpu(frames)
+    n, H, W, _ = frames.shape
+    out = torch.empty(n, H, W, 3, dtype=torch.float32, device=frames.device)
+    _lib.check(_lib.load().midas_input(frames.data_ptr(), out.data_ptr(), n, H, W, _stream()),
+               "midas_input(n=%d,H=%d,W=%d)" % (n, H, W))
+    return out
+
+
+def midas_stem_conv(x_nhwc, w_split):
+    """StdConv2dSame(3, 64, 7, stride 2) at even sizes (padding 2 before, 3 after) on (n, H, W, 3) fp32 NHWC, w_split =
+    fn_conv7_weight(the standardised weight) -> (n, H / 2, W / 2, 64) fp32 (midas_stem_conv)"""
+    _dense(x_nhwc, "midas_stem_conv: x", torch.float32)
+    wh, wl = w_split
+    for w in (wh, wl):
+        _dense(w, "midas_stem_conv: weight planes", torch.float16, (64, 224), align=16)
+    if x_nhwc.dim() != 4 or x_nhwc.shape[3] != 3 or x_nhwc.shape[1] % 2 or x_nhwc.shape[2] % 2 or x_nhwc.numel() == 0:
+        raise ValueError("midas_stem_conv: x must be (n, even H, even W, 3), got %s" % (tuple(x_nhwc.shape),))
+    _need_gpu(x_nhwc, wh, wl)
+    n, H, W, _ = x_nhwc.shape
+    out = torch.empty(n, H // 2, W // 2, 64, dtype=torch.float32, device=x_nhwc.device)
+    rc = _lib.load().midas_stem_conv(x_nhwc.data_ptr(), wh.data_ptr(), wl.data_ptr(), out.data_ptr(), n, H, W,
+                                     _fn_flag_ptr(x_nhwc.device), _stream())
+    _lib.check(rc, "midas_stem_conv(n=%d,H=%d,W=%d)" % (n, H, W))
+    return out
+
+
+def midas_groupnorm(x, gamma, beta, relu=False, residual=None, eps=1e-5, want_f32=True, want_split=False, far_border=False,
+                    scale=FN_A_SCALE):
+    """GroupNorm(32, C) on x (n, H, W, C) fp32 NHWC: (x - mean) rstd gamma + beta [ReLU] [+ residual, ReLU]
+    (midas_groupnorm_stats + midas_groupnorm_apply).  -> (y (n, H, W, C) fp32 or None, (hi, lo) planes or None).
+    far_border: the planes are (n (H + 1) (W + 1), C) rows of a map with one zero row below and one zero column to the right
+    -- what a "same" 3 x 3 stride-2 convolution reads with fn_gemm's pad = 0."""
+    _dense(x, "midas_groupnorm: x", torch.float32, align=16)
+    if x.dim() != 4 or x.numel() == 0 or x.shape[3] not in MIDAS_GN_CHANNELS:
+        raise ValueError("midas_groupnorm: x must be (n, H, W, C), C in %s, got %s" % (MIDAS_GN_CHANNELS, tuple(x.shape)))
+    n, H, W, C = x.shape
+    if not (want_f32 or want_split):
+        raise ValueError("midas_groupnorm: nothing asked for")
+    if residual is not None:
+        _dense(residual, "midas_groupnorm: residual", torch.float32, (n, H, W, C), align=16)
+    scale = _split_scale(scale)
+    _need_gpu(x)
+    gamma, beta = _fn_f32_operand(gamma, "gamma", x), _fn_f32_operand(beta, "beta", x)
+    if gamma.numel() != C or beta.numel() != C:
+        raise ValueError("midas_groupnorm: gamma / beta of %d channels" % C)
+    lib = _lib.load()
+    dev = x.device
+    nbytes = lib.midas_groupnorm_workspace_bytes(n, H * W, C)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    mean = torch.empty(n, 32, dtype=torch.float32, device=dev)
+    rstd = torch.empty(n, 32, dtype=torch.float32, device=dev)
+    rc = lib.midas_groupnorm_stats(x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), nbytes, n, H * W, C,
+                                   float(eps), _stream())
+    _lib.check(rc, "midas_groupnorm_stats(n=%d,P=%d,C=%d)" % (n, H * W, C))
+    y = torch.empty_like(x) if want_f32 else None
+    hi = lo = None
+    ph, pw = (H + 1, W + 1) if far_border else (H, W)
+    if want_split:
+        make = torch.zeros if far_border else torch.empty
+        hi = make(n * ph * pw, C, dtype=torch.float16, device=dev)
+        lo = make(n * ph * pw, C, dtype=torch.float16, device=dev)
+    rc = lib.midas_groupnorm_apply(x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                   _ptr(residual), _ptr(y), _ptr(hi), _ptr(lo), n, H, W, C, ph, pw, int(bool(relu)), scale,
+                                   _fn_flag_ptr(dev), _stream())
+    _lib.check(rc, "midas_groupnorm_apply(n=%d,H=%d,W=%d,C=%d)" % (n, H, W, C))
+    return y, ((hi, lo) if want_split else None)
+
+
+def midas_pool(x, want_f32=False, scale=FN_A_SCALE):
+    """MaxPool2dSame(3, stride 2) at even sizes on x (n, H, W, 64) fp32 NHWC -> (fp32 (n, H / 2, W / 2, 64) or None, planes)"""
+    _dense(x, "midas_pool: x", torch.float32, align=16)
+    if x.dim() != 4 or x.shape[3] != 64 or x.numel() == 0 or x.shape[1] % 2 or x.shape[2] % 2:
+        raise ValueError("midas_pool: x must be (n, even H, even W, 64), got %s" % (tuple(x.shape),))
+    scale = _split_scale(scale)
+    _need_gpu(x)
+    n, H, W, C = x.shape
+    out = torch.empty(n, H // 2, W // 2, C, dtype=torch.float32, device=x.device) if want_f32 else None
+    hi, lo = _planes(n * (H // 2) * (W // 2), C, x.device, True)
+    rc = _lib.load().midas_pool(x.data_ptr(), _ptr(out), hi.data_ptr(), lo.data_ptr(), n, H, W, C, scale,
+                                _fn_flag_ptr(x.device), _stream())
+    _lib.check(rc, "midas_pool(n=%d,H=%d,W=%d)" % (n, H, W))
+    return out, (hi, lo)
+
+
+def midas_layernorm(x, gamma, beta, eps=1e-6, want_f32=False, want_split=True, scale=FN_A_SCALE):
+    """nn.LayerNorm(C) on (M, C) fp32 rows, C % 4 == 0 and C <= 1024 -> (y or None, planes or None) (midas_layernorm)"""
+    _dense(x, "midas_layernorm: x", torch.float32, align=16)
+    if x.dim() != 2 or x.numel() == 0 or x.shape[1] % 4 or x.shape[1] > 1024:
+        raise ValueError("midas_layernorm: x must be (M, C), C a multiple of 4 up to 1024, got %s" % (tuple(x.shape),))
+    if not (want_f32 or want_split):
+        raise ValueError("midas_layernorm: nothing asked for")
+    scale = _split_scale(scale)
+    _need_gpu(x)
+    M, C = x.shape
+    gamma, beta = _fn_f32_operand(gamma, "gamma", x), _fn_f32_operand(beta, "beta", x)
+    if gamma.numel() != C or beta.numel() != C:
+        raise ValueError("midas_layernorm: gamma / beta of %d channels" % C)
+    y = torch.empty_like(x) if want_f32 else None
+    hi, lo = _planes(M, C, x.device, want_split)
+    rc = _lib.load().midas_layernorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(y), _ptr(hi), _ptr(lo), M, C,
+                                     float(eps), scale, _fn_flag_ptr(x.device), _stream())
+    _lib.check(rc, "midas_layernorm(M=%d,C=%d)" % (M, C))
+    return y, ((hi, lo) if want_split else None)
+
+
+def midas_tokens(grid, cls, pos):
+    """grid (n, L - 1, C) fp32, cls (C), pos (L, C) -> [cls | grid] + pos, (n, L, C) fp32 (midas_tokens)"""
+    _dense(grid, "midas_tokens: grid", torch.float32, align=16)
+    if grid.dim() != 3 or grid.numel() == 0 or grid.shape[2] % 4:
+        raise ValueError("midas_tokens: grid must be (n, L - 1, C), C a multiple of 4, got %s" % (tuple(grid.shape),))
+    n, L, C = grid.shape[0], grid.shape[1] + 1, grid.shape[2]
+    _need_gpu(grid)
+    cls, pos = _fn_f32_operand(cls, "cls", grid), _fn_f32_operand(pos, "pos", grid)
+    if cls.numel() != C or pos.numel() != L * C:
+        raise ValueError("midas_tokens: cls of %d values and pos of %d x %d expected" % (C, L, C))
+    out = torch.empty(n, L, C, dtype=torch.float32, device=grid.device)
+    rc = _lib.load().midas_tokens(grid.data_ptr(), cls.data_ptr(), pos.data_ptr(), out.data_ptr(), n, L, C, _stream())
+    _lib.check(rc, "midas_tokens(n=%d,L=%d,C=%d)" % (n, L, C))
+    return out
+
+
+def midas_head_merge(x, n, want_f32=False, want_split=True, scale=FN_A_SCALE):
+    """attention output x (heads * n, L, 64) fp32, batch = head * n + image -> rows (n L, heads 64): (fp32 or None, planes or
+    None) (midas_head_merge)"""
+    _dense(x, "midas_head_merge: x", torch.float32, align=16)
+    if x.dim() != 3 or x.shape[2] != 64 or x.numel() == 0 or x.shape[0] % int(n):
+        raise ValueError("midas_head_merge: x must be (heads * n, L, 64), got %s with n = %r" % (tuple(x.shape), n))
+    if not (want_f32 or want_split):
+        raise ValueError("midas_head_merge: nothing asked for")
+    scale = _split_scale(scale)
+    _need_gpu(x)
+    heads, L = x.shape[0] // int(n), x.shape[1]
+    out = torch.empty(n * L, heads * 64, dtype=torch.float32, device=x.device) if want_f32 else None
+    hi, lo = _planes(n * L, heads * 64, x.device, want_split)
+    rc = _lib.load().midas_head_merge(x.data_ptr(), _ptr(out), _ptr(hi), _ptr(lo), int(n), L, heads, scale,
+                                      _fn_flag_ptr(x.device), _stream())
+    _lib.check(rc, "midas_head_merge(n=%d,L=%d,heads=%d)" % (n, L, heads))
+    return out, ((hi, lo) if want_split else None)
+
+
+def midas_rowbias_gelu(x, rowbias, rows_per_img, want_f32=False, want_split=True, scale=FN_A_SCALE):
+    """GELU(x[m] + rowbias[m // rows_per_img]) (erf form) on (M, C) fp32 rows -> (fp32 or None, planes or None)"""
+    _dense(x, "midas_rowbias_gelu: x", torch.float32, align=16)
+    if x.dim() != 2 or x.numel() == 0 or x.shape[1] % 4 or int(rows_per_img) < 1 or x.shape[0] % int(rows_per_img):
+        raise ValueError("midas_rowbias_gelu: x must be (images * rows_per_img, C), got %s" % (tuple(x.shape),))
+    M, C = x.shape
+    _dense(rowbias, "midas_rowbias_gelu: rowbias", torch.float32, (M // int(rows_per_img), C), align=16)
+    if not (want_f32 or want_split):
+        raise ValueError("midas_rowbias_gelu: nothing asked for")
+    scale = _split_scale(scale)
+    _need_gpu(x, rowbias)
+    out = torch.empty_like(x) if want_f32 else None
+    hi, lo = _planes(M, C, x.device, want_split)
+    rc = _lib.load().midas_rowbias_gelu(x.data_ptr(), rowbias.data_ptr(), _ptr(out), _ptr(hi), _ptr(lo), M, C,
+                                        int(rows_per_img), scale, _fn_flag_ptr(x.device), _stream())
+    _lib.check(rc, "midas_rowbias_gelu(M=%d,C=%d)" % (M, C))
+    return out, ((hi, lo) if want_split else None)
+
+
+def midas_tail(depth, a, bg_th, cond_dtype=None):
+    """depth (n, H, W) fp32 -> (depth image (n, H, W) uint8, normal image (n, H, W, 3) uint8, ControlNet condition
+    (n, 3, H, W) of cond_dtype or None): the lines after the network of annotator/midas/__init__.py (midas_tail)"""
+    _dense(depth, "midas_tail: depth", torch.float32)
+    if depth.dim() != 3 or depth.numel() == 0 or depth.shape[1] < 2 or depth.shape[2] < 2:
+        raise ValueError("midas_tail: depth must be (n, H >= 2, W >= 2), got %s" % (tuple(depth.shape),))
+    if cond_dtype is not None and cond_dtype not in _ELEMWISE_DTYPES:
+        raise TypeError("midas_tail: cond_dtype %s (fp16, bf16 or fp32)" % (cond_dtype,))
+    _need_gpu(depth)
+    n, H, W = depth.shape
+    dev = depth.device
+    lib = _lib.load()
+    nbytes = lib.midas_tail_workspace_bytes(n, H, W)
+    ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=dev)
+    dimg = torch.empty(n, H, W, dtype=torch.uint8, device=dev)
+    nimg = torch.empty(n, H, W, 3, dtype=torch.uint8, device=dev)
+    cond = torch.empty(n, 3, H, W, dtype=cond_dtype, device=dev) if cond_dtype is not None else None
+    rc = lib.midas_tail(depth.data_ptr(), dimg.data_ptr(), nimg.data_ptr(), _ptr(cond), _ELEMWISE_DTYPES.get(cond_dtype, _lib.F32),
+                        ws.data_ptr(), nbytes, n, H, W, float(a), float(bg_th), _stream())
+    _lib.check(rc, "midas_tail(n=%d,H=%d,W=%d)" % (n, H, W))
+    return dimg, nimg, cond
