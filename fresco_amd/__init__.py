@@ -22,6 +22,7 @@ from .hed import ControlNetHED_Apache2, DoubleConvBlock, HEDdetector, patch_hed
 from .egnet import TUN_bone, build_model, get_saliency, patch_saliency
 from .canny import CannyDetector, patch_canny
 from .midas import DPTDepthModel, MidasDetector, patch_midas
+from .vae import VAEDecoder, patch_vae_decode, unpatch_vae_decode
 from .keyframe import (frame_errors, get_keyframe_ind, patch_keyframe_selection, resize_frames, resize_image, resize_size,
                        select_keyframes)
 from .paras import (correlation_matrices, forward_backward_consistency_check, get_flow_and_interframe_paras,
@@ -39,6 +40,7 @@ __all__ = [
     "TUN_bone", "build_model", "get_saliency", "patch_saliency",
     "CannyDetector", "patch_canny",
     "MidasDetector", "DPTDepthModel", "patch_midas",
+    "VAEDecoder", "patch_vae_decode", "unpatch_vae_decode",
     "get_keyframe_ind", "frame_errors", "select_keyframes", "resize_frames", "resize_image", "resize_size",
     "patch_keyframe_selection",
 ]

@@ -153,6 +153,17 @@ MIDAS_SIGNATURES = {
     "midas_tail": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _sz, _i, _i, _i, _f, _f, _vp]),
 }
 
+# the VAE decoder's kernels (csrc/vae.hip), declared in include/fresco_vae.h: named vae_*, beside the pinned surfaces; bound
+# on the same handle
+VAE_SIGNATURES = {
+    "vae_input": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "vae_conv": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp] + [_i] * 9 + [_i64, _vp]),
+    "vae_groupnorm_workspace_bytes": (_sz, [_i, _i, _i]),
+    "vae_groupnorm": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _i, _vp]),
+    "vae_softmax": (_i, [_vp, _vp, _i64, _i, _i64, _i64, _f, _vp]),
+}
+VAE_OUT_F16, VAE_OUT_F32, VAE_OUT_F16_NCHW = 0, 1, 2  # VAE_OUT_* of the header
+
 _lib = None
 
 
@@ -170,7 +181,7 @@ def load():
     except OSError as e:
         raise FrescoHipError("fresco_amd: cannot load %s: %s" % (LIB_PATH, e))
     for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
-            + list(MIDAS_SIGNATURES.items()):
+            + list(MIDAS_SIGNATURES.items()) + list(VAE_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -1677,3 +1677,113 @@ def midas_tail(depth, a, bg_th, cond_dtype=None):
                         ws.data_ptr(), nbytes, n, H, W, float(a), float(bg_th), _stream())
     _lib.check(rc, "midas_tail(n=%d,H=%d,W=%d)" % (n, H, W))
     return dimg, nimg, cond
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the VAE decoder's kernels (include/fresco_vae.h): fp16 NHWC activations, plain-fp16 implicit-GEMM convolutions
+# ---------------------------------------------------------------------------------------------------------------------
+VAE_GN_CHANNELS = (128, 256, 512)
+VAE_CIN_PAD = 32  # conv_in's four input channels padded to the convolution's K chunk
+
+
+def vae_input(z, weight, bias, cpad=VAE_CIN_PAD):
+    """latents (n, 4, h, w) fp16 NCHW -> post_quant_conv (weight (4, 4), bias (4) fp32) -> (n, h, w, cpad) fp16 NHWC, channels
+    4 .. zero (vae_input)"""
+    _dense(z, "vae_input: z", torch.float16)
+    if z.dim() != 4 or z.shape[1] != 4 or z.numel() == 0:
+        raise ValueError("vae_input: z must be (n, 4, h, w), got %s" % (tuple(z.shape),))
+    _dense(weight, "vae_input: weight", torch.float32, (4, 4))
+    _dense(bias, "vae_input: bias", torch.float32, (4,))
+    _need_gpu(z, weight, bias)
+    n, _, h, w = z.shape
+    out = torch.empty(n, h, w, cpad, dtype=torch.float16, device=z.device)
+    rc = _lib.load().vae_input(z.data_ptr(), weight.data_ptr(), bias.data_ptr(), out.data_ptr(), n, h, w, cpad, _stream())
+    _lib.check(rc, "vae_input(n=%d,h=%d,w=%d,cpad=%d)" % (n, h, w, cpad))
+    return out
+
+
+def vae_conv(x, w, bias, n, H, W, cin, cout, ksize, up2=False, residual=None, out_kind=_lib.VAE_OUT_F16, x_img_stride=None,
+             w_img_stride=0, bias_rows=False, ldo=None, out=None):
+    """out = [residual +] conv(x) + bias on the plain-fp16 implicit GEMM (vae_conv of include/fresco_vae.h).  x: fp16, ksize 3:
+    (n, H, W, cin) NHWC, or (n, H / 2, W / 2, cin) with up2; ksize 1: H * W rows of cin per image, x_img_stride elements
+    apart (default H W cin; 0 = shared).  w: fp16 (cout, ksize^2 cin) with k = (ky, kx, ci), or n such matrices w_img_stride
+    elements apart.  -> `out`, or a new (n, H, W, cout) fp16 / fp32 tensor of row stride ldo, (n, cout, H, W) for
+    VAE_OUT_F16_NCHW."""
+    _dense(x, "vae_conv: x", torch.float16, align=16)
+    _dense(w, "vae_conv: w", torch.float16, align=16)
+    if bias is not None:
+        _dense(bias, "vae_conv: bias", torch.float32, align=16)
+    K = ksize * ksize * cin
+    Hs, Ws = (H // 2, W // 2) if up2 else (H, W)
+    if x_img_stride is None:
+        x_img_stride = Hs * Ws * cin
+    need_x = (n - 1) * x_img_stride + Hs * Ws * cin
+    need_w = (n - 1) * w_img_stride + cout * K
+    if x.numel() < need_x or w.numel() < need_w:
+        raise ValueError("vae_conv: x holds %d elements (needs %d), w %d (needs %d)" % (x.numel(), need_x, w.numel(), need_w))
+    if bias is not None and bias.numel() < (H * W if bias_rows else cout):
+        raise ValueError("vae_conv: bias of %d values" % bias.numel())
+    ldo = cout if ldo is None else int(ldo)
+    odt = torch.float32 if out_kind == _lib.VAE_OUT_F32 else torch.float16
+    if out is None:
+        if out_kind == _lib.VAE_OUT_F16_NCHW:
+            out = torch.empty(n, cout, H, W, dtype=odt, device=x.device)
+        elif ldo == cout:
+            out = torch.empty(n, H, W, cout, dtype=odt, device=x.device)
+        else:
+            out = torch.empty(n, H * W, ldo, dtype=odt, device=x.device)
+    else:
+        _dense(out, "vae_conv: out", odt, align=8)
+    if out.numel() < n * H * W * (cout if out_kind == _lib.VAE_OUT_F16_NCHW else ldo):
+        raise ValueError("vae_conv: out holds %d elements" % out.numel())
+    if residual is not None:
+        _dense(residual, "vae_conv: residual", torch.float16, align=8)
+        if residual.numel() < n * H * W * ldo:
+            raise ValueError("vae_conv: residual holds %d elements" % residual.numel())
+    _need_gpu(x, w, bias, residual, out)
+    rc = _lib.load().vae_conv(x.data_ptr(), x_img_stride, w.data_ptr(), w_img_stride, _ptr(bias), _ptr(residual),
+                              out.data_ptr(), n, H, W, cin, cout, ksize, int(bool(up2)), out_kind, int(bool(bias_rows)), ldo,
+                              _stream())
+    _lib.check(rc, "vae_conv(n=%d,H=%d,W=%d,cin=%d,cout=%d,k=%d,up2=%d,kind=%d)" % (n, H, W, cin, cout, ksize, up2, out_kind))
+    return out
+
+
+_vae_gn_ws = _PerStreamWorkspace()
+
+
+def vae_groupnorm(x, gamma, beta, eps=1e-6, silu=False):
+    """GroupNorm(32, C, eps) [+ SiLU] on x (n, ..., C) fp16 NHWC, C in VAE_GN_CHANNELS; gamma / beta fp32 -> fp16 like x
+    (vae_groupnorm)"""
+    _dense(x, "vae_groupnorm: x", torch.float16, align=16)
+    if x.dim() < 3 or x.numel() == 0 or x.shape[-1] not in VAE_GN_CHANNELS:
+        raise ValueError("vae_groupnorm: x must be (n, ..., C), C in %s, got %s" % (VAE_GN_CHANNELS, tuple(x.shape)))
+    n, C = x.shape[0], x.shape[-1]
+    P = x.numel() // (n * C)
+    _dense(gamma, "vae_groupnorm: gamma", torch.float32, (C,))
+    _dense(beta, "vae_groupnorm: beta", torch.float32, (C,))
+    _need_gpu(x, gamma, beta)
+    lib = _lib.load()
+    nbytes = lib.vae_groupnorm_workspace_bytes(n, P, C)
+    ws = _vae_gn_ws.get(nbytes, x.device)
+    y = torch.empty_like(x)
+    rc = lib.vae_groupnorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), ws.data_ptr(), nbytes, n, P, C,
+                           float(eps), int(bool(silu)), _stream())
+    _lib.check(rc, "vae_groupnorm(n=%d,P=%d,C=%d)" % (n, P, C))
+    return y
+
+
+def vae_softmax(scores, Lk, scale, ld_out=None):
+    """scores (rows, ld_in) fp32, the first Lk columns of a row its logits -> softmax(scale * logits) as (rows, ld_out) fp16,
+    columns Lk .. zero (vae_softmax)"""
+    _dense(scores, "vae_softmax: scores", torch.float32)
+    if scores.dim() != 2 or scores.numel() == 0 or not 0 < Lk <= scores.shape[1]:
+        raise ValueError("vae_softmax: scores (rows, ld_in >= Lk), got %s, Lk %d" % (tuple(scores.shape), Lk))
+    rows, ld_in = scores.shape
+    ld_out = Lk if ld_out is None else int(ld_out)
+    if ld_out < Lk:
+        raise ValueError("vae_softmax: ld_out %d < Lk %d" % (ld_out, Lk))
+    _need_gpu(scores)
+    p = torch.empty(rows, ld_out, dtype=torch.float16, device=scores.device)
+    rc = _lib.load().vae_softmax(scores.data_ptr(), p.data_ptr(), rows, Lk, ld_in, ld_out, float(scale), _stream())
+    _lib.check(rc, "vae_softmax(rows=%d,Lk=%d)" % (rows, Lk))
+    return p
