@@ -17,7 +17,7 @@ import math
 import numpy as np
 import torch
 
-from . import ops
+from . import _detector, ops
 
 
 def check_frames(frames):
@@ -64,9 +64,7 @@ def check_thresholds(low_threshold, high_threshold):
 
 
 def condition_dtype(dtype):
-    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
-        raise TypeError("Canny: the ControlNet condition is fp16, bf16 or fp32, got %s" % (dtype,))
-    return dtype
+    return _detector.condition_dtype(dtype, "Canny")
 
 
 class CannyDetector:

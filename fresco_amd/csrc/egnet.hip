@@ -5,13 +5,15 @@
 //
 //   egnet_input_kernel       uint8 frames -> cv2sod's tensor: (x - mean) halved with bilinear weights (the 2 x 2 block mean),
 //                            fp32 NHWC rows of 3 channels, what fresco_fn_conv7_rgb reads
-//   egnet_pool_kernel        MaxPool2d(3, stride 2, padding 1, ceil_mode=True) on 64-channel fp32 NHWC rows -> operand planes
+//   pool3s2_kernel<-1>       MaxPool2d(3, stride 2, padding 1, ceil_mode=True) on 64-channel fp32 NHWC rows -> operand planes
+//                            (pool3s2.h, shared with midas.hip)
 //   egnet_resize_add_kernel  F.interpolate(bilinear, align_corners=True) on NHWC fp32 (+ addend) (ReLU) -> fp32 and / or planes
 //   egnet_saliency_kernel    the tail: resize of the logit, sigmoid, k x k box sum with replicate padding, clamp, 1 - x
 //
 // All four are bound by memory traffic; no float atomics anywhere: same inputs, same bits.
 #include "common.h"
 #include "fn_split.h"
+#include "pool3s2.h"
 
 namespace fresco {
 
@@ -37,50 +39,6 @@ __global__ __launch_bounds__(256) void egnet_input_kernel(const uint8_t* __restr
         const int sum = (int)s[0] + (int)s[3] + (int)s[row] + (int)s[row + 3];
         out[idx] = (float)((double)sum * 0.25 - mean[c]);
     }
-}
-
-// One thread per (output pixel, four channels): 16 threads per pixel at C = 64.  Padding never wins (-inf), and every window
-// holds at least one pixel of the map (the launcher's output size follows PyTorch's ceil_mode rule).
-__global__ __launch_bounds__(256) void egnet_pool_kernel(const float* __restrict__ x, float* __restrict__ out,
-                                                         half_t* __restrict__ o_hi, half_t* __restrict__ o_lo, int64_t total,
-                                                         int H, int W, int OH, int OW, float scale, int32_t* range_flag) {
-    constexpr int C = 64, Q = C / 4;
-    bool sat = false;
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
-        const int c = (int)(idx % Q) * 4;
-        const int64_t p = idx / Q;
-        const int ox = (int)(p % OW), oy = (int)((p / OW) % OH);
-        const int64_t img = p / ((int64_t)OW * OH);
-        float v[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int iy = 2 * oy - 1 + ky;
-            if (iy < 0 || iy >= H) continue;
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int ix = 2 * ox - 1 + kx;
-                if (ix < 0 || ix >= W) continue;
-                const floatx4 t = *reinterpret_cast<const floatx4*>(x + ((img * H + iy) * W + ix) * C + c);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], t[e]);
-            }
-        }
-        if (out) {
-            const floatx4 t = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<floatx4*>(out + p * C + c) = t;
-        }
-        half4_t h, l;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            half_t hh, ll;
-            sat |= fn_split(v[e], scale, hh, ll);
-            h[e] = hh;
-            l[e] = ll;
-        }
-        *reinterpret_cast<half4_t*>(o_hi + p * C + c) = h;
-        *reinterpret_cast<half4_t*>(o_lo + p * C + c) = l;
-    }
-    fn_flag_range(range_flag, sat);
 }
 
 // align_corners=True source position of destination index d: d (src - 1) / (dst - 1) (0 for a single destination sample),
@@ -135,18 +93,7 @@ __global__ __launch_bounds__(256) void egnet_resize_add_kernel(const float* __re
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
         if (out) *reinterpret_cast<floatx4*>(out + p * C + c) = v;
-        if (o_hi) {
-            half4_t hh4, ll4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                half_t hh, ll;
-                sat |= fn_split(v[e], scale, hh, ll);
-                hh4[e] = hh;
-                ll4[e] = ll;
-            }
-            *reinterpret_cast<half4_t*>(o_hi + p * C + c) = hh4;
-            *reinterpret_cast<half4_t*>(o_lo + p * C + c) = ll4;
-        }
+        if (o_hi) sat |= fn_split_store4(v, scale, o_hi, o_lo, p * C + c);
     }
     fn_flag_range(range_flag, sat);
 }
@@ -222,7 +169,7 @@ extern "C" int fresco_egnet_pool(const float* x, float* out, void* out_hi, void*
     if (!aligned_to(x, 16) || !aligned_to(out, 16) || !aligned_to(out_hi, 8) || !aligned_to(out_lo, 8)) return FRESCO_EINVAL;
     const int OH = eg_pool_size(H), OW = eg_pool_size(W);
     const int64_t total = (int64_t)n * OH * OW * (C / 4);
-    hipLaunchKernelGGL(egnet_pool_kernel, dim3(stream_blocks(total)), dim3(256), 0, as_stream(stream), x, out,
+    hipLaunchKernelGGL(pool3s2_kernel<-1>, dim3(stream_blocks(total)), dim3(256), 0, as_stream(stream), x, out,
                        static_cast<half_t*>(out_hi), static_cast<half_t*>(out_lo), total, H, W, OH, OW, split_scale, range_flag);
     return check_launch();
 }

@@ -569,17 +569,7 @@ __global__ __launch_bounds__(256) void fn_prep_kernel(const float* __restrict__ 
         }
     }
     if (o_hi) {
-        half4_t h, l;
-        bool sat = false;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            half_t hh, ll;
-            sat |= fn_split(v[e], split_scale, hh, ll);
-            h[e] = hh;
-            l[e] = ll;
-        }
-        *reinterpret_cast<half4_t*>(o_hi + m * ldo + c) = h;
-        *reinterpret_cast<half4_t*>(o_lo + m * ldo + c) = l;
+        const bool sat = fn_split_store4(v, split_scale, o_hi, o_lo, m * ldo + c);
         if (sat && range_flag) atomicOr(range_flag, 1);  // (rare; threads past M * q have returned: no wave-wide vote here)
     }
 }

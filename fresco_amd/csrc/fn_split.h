@@ -19,6 +19,26 @@ __device__ __forceinline__ bool fn_split(float x, float scale, half_t& h, half_t
     l = (half_t)(x - (float)h);
     return !(fabsf(xs) <= 65000.f);
 }
+// Four consecutive channels (a float[4] or a floatx4) -> the two half4_t stores at o_hi / o_lo + offset (8-byte aligned);
+// true when one of them saturated.  OPTIONAL: the planes may be absent (o_hi == nullptr): the split is formed all the same and
+// nothing is stored -- such a caller hands fn_flag_range its flag word only where it has planes (midas_layernorm_kernel).
+template <bool OPTIONAL = false, typename V>
+__device__ __forceinline__ bool fn_split_store4(const V& v, float scale, half_t* o_hi, half_t* o_lo, int64_t offset) {
+    half4_t h4, l4;
+    bool sat = false;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        half_t hh, ll;
+        sat |= fn_split(v[e], scale, hh, ll);
+        h4[e] = hh;
+        l4[e] = ll;
+    }
+    if (!OPTIONAL || o_hi) {
+        *reinterpret_cast<half4_t*>(o_hi + offset) = h4;
+        *reinterpret_cast<half4_t*>(o_lo + offset) = l4;
+    }
+    return sat;
+}
 __device__ __forceinline__ void fn_flag_range(int32_t* range_flag, bool sat) {
     if (range_flag && sat) atomicOr(range_flag, 1);  // (rare path)
 }

@@ -3,11 +3,11 @@
 // convolutions and linear layers run on flownet.hip's GEMM from (hi, lo) fp16 operand planes.  DESIGN.md section 16.
 //
 //   midas_input_kernel         uint8 frames -> x / 127.5 - 1, fp32 NHWC rows of 3 channels (the stem splits them itself)
-//   midas_gn_stats_kernel      GroupNorm(32): fp64 partial sums per (image, 256-pixel chunk, group)
-//   midas_gn_finish_kernel     ... added in chunk order -> mean, 1 / sqrt(var + eps) per (image, group)
+//   gn_stats_kernel<float> / gn_finish_kernel   GroupNorm(32): the statistics pass shared with vae.hip (groupnorm_stats.h)
 //   midas_gn_apply_kernel      (x - mean) rstd gamma + beta [ReLU] [+ residual, ReLU] -> fp32 and / or planes, the planes with a
 //                              row pitch of their own (the far-side zero border of a "same" stride-2 convolution)
-//   midas_pool_kernel          MaxPool2dSame(3, 2) at even sizes: windows start AT 2 oy (0 before, 1 after)
+//   pool3s2_kernel<0>          MaxPool2dSame(3, 2) at even sizes: windows start AT 2 oy (0 before, 1 after) (pool3s2.h, shared
+//                              with egnet.hip; H, W even: the first two rows and columns of every window exist)
 //   midas_layernorm_kernel     LayerNorm over up to 1024 channels, one wave per row
 //   midas_tokens_kernel        [cls | grid] + positional embedding
 //   midas_head_merge_kernel    (head * n + image, L, 64) attention output -> (n L, heads 64) rows
@@ -17,77 +17,19 @@
 // All are bound by memory traffic.  Built with -ffp-contract=off: the tail follows the reference's fp32 operation order.
 #include "common.h"
 #include "fn_split.h"
+#include "groupnorm_stats.h"
+#include "pool3s2.h"
 #include "../../include/fresco_midas.h"
 
 namespace fresco {
 
-constexpr int MD_GROUPS = 32;
-constexpr int MD_GN_ROWS = 256;    // pixels per workgroup of the statistics pass
+constexpr int MD_GROUPS = GN_GROUPS;
 constexpr int MD_LN_MAXQ = 4;      // 16-byte pieces per lane of a LayerNorm row: C <= 64 * 4 * 4
 constexpr int MD_MM_BLOCKS = 64;   // partial min / max pairs per frame
 
 __global__ __launch_bounds__(256) void midas_input_kernel(const uint8_t* __restrict__ x, float* __restrict__ out, int64_t total) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256)
         out[i] = (float)x[i] / 127.5f - 1.0f;
-}
-
-// grid (chunks, n).  Thread t owns the four channels 4 (t % Q) .. + 3, Q = C / 4 (a divisor of 256), of the pixels t / Q,
-// t / Q + 256 / Q, ... of its chunk, and keeps one fp64 sum pair per HALF of them: two channels never straddle a group
-// (C / 32 is even).  Thread g < 32 then adds the 512 halves that belong to group g in index order.
-__global__ __launch_bounds__(256) void midas_gn_stats_kernel(const float* __restrict__ x, double* __restrict__ part, int P, int C,
-                                                             int chunks) {
-    __shared__ double s1[512], s2[512];
-    const int Q = C >> 2, tid = threadIdx.x, q = tid % Q, step = 256 / Q;
-    const int img = blockIdx.y, chunk = blockIdx.x;
-    const int pb = chunk * MD_GN_ROWS, pe = min(pb + MD_GN_ROWS, P);
-    double a1[2] = {0.0, 0.0}, a2[2] = {0.0, 0.0};
-    for (int p = pb + tid / Q; p < pe; p += step) {
-        const floatx4 v = *reinterpret_cast<const floatx4*>(x + ((int64_t)img * P + p) * C + q * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const double d = (double)v[e];
-            a1[e >> 1] += d;
-            a2[e >> 1] += d * d;
-        }
-    }
-    s1[tid * 2] = a1[0];
-    s1[tid * 2 + 1] = a1[1];
-    s2[tid * 2] = a2[0];
-    s2[tid * 2 + 1] = a2[1];
-    __syncthreads();
-    if (tid < MD_GROUPS) {
-        const int cpg = C / MD_GROUPS;
-        double t1 = 0.0, t2 = 0.0;
-        for (int e = 0; e < 512; ++e) {
-            const int ch = ((e >> 1) % Q) * 4 + (e & 1) * 2;
-            if (ch / cpg == tid) {
-                t1 += s1[e];
-                t2 += s2[e];
-            }
-        }
-        double* o = part + (((int64_t)img * chunks + chunk) * MD_GROUPS + tid) * 2;
-        o[0] = t1;
-        o[1] = t2;
-    }
-}
-
-__global__ __launch_bounds__(256) void midas_gn_finish_kernel(const double* __restrict__ part, float* __restrict__ mean,
-                                                              float* __restrict__ rstd, int n, int chunks, double count,
-                                                              float eps) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n * MD_GROUPS) return;
-    const int img = idx / MD_GROUPS, g = idx - img * MD_GROUPS;
-    double t1 = 0.0, t2 = 0.0;
-    for (int c = 0; c < chunks; ++c) {
-        const double* o = part + (((int64_t)img * chunks + c) * MD_GROUPS + g) * 2;
-        t1 += o[0];
-        t2 += o[1];
-    }
-    const double m = t1 / count;
-    double var = t2 / count - m * m;
-    var = var > 0.0 ? var : 0.0;
-    mean[idx] = (float)m;
-    rstd[idx] = (float)(1.0 / sqrt(var + (double)eps));
 }
 
 // One thread per (pixel, four channels).
@@ -122,62 +64,8 @@ __global__ __launch_bounds__(256) void midas_gn_apply_kernel(const float* __rest
         if (o_hi) {
             const int64_t rem = p - img * HW;
             const int py = (int)(rem / W), px = (int)(rem - (int64_t)py * W);
-            const int64_t o = ((img * plane_h + py) * plane_w + px) * C + c;
-            half4_t h4, l4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                half_t hh, ll;
-                sat |= fn_split(v[e], scale, hh, ll);
-                h4[e] = hh;
-                l4[e] = ll;
-            }
-            *reinterpret_cast<half4_t*>(o_hi + o) = h4;
-            *reinterpret_cast<half4_t*>(o_lo + o) = l4;
+            sat |= fn_split_store4(v, scale, o_hi, o_lo, ((img * plane_h + py) * plane_w + px) * C + c);
         }
-    }
-    fn_flag_range(range_flag, sat);
-}
-
-// One thread per (output pixel, four channels); window rows 2 oy .. 2 oy + 2, clipped to the map (H, W even: the first two
-// rows of every window exist).
-__global__ __launch_bounds__(256) void midas_pool_kernel(const float* __restrict__ x, float* __restrict__ out,
-                                                         half_t* __restrict__ o_hi, half_t* __restrict__ o_lo, int64_t total,
-                                                         int H, int W, int OH, int OW, float scale, int32_t* range_flag) {
-    constexpr int C = 64, Q = C / 4;
-    bool sat = false;
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
-        const int c = (int)(idx % Q) * 4;
-        const int64_t p = idx / Q;
-        const int ox = (int)(p % OW), oy = (int)((p / OW) % OH);
-        const int64_t img = p / ((int64_t)OW * OH);
-        float v[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int iy = 2 * oy + ky;
-            if (iy >= H) continue;
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int ix = 2 * ox + kx;
-                if (ix >= W) continue;
-                const floatx4 t = *reinterpret_cast<const floatx4*>(x + ((img * H + iy) * W + ix) * C + c);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], t[e]);
-            }
-        }
-        if (out) {
-            const floatx4 t = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<floatx4*>(out + p * C + c) = t;
-        }
-        half4_t h4, l4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            half_t hh, ll;
-            sat |= fn_split(v[e], scale, hh, ll);
-            h4[e] = hh;
-            l4[e] = ll;
-        }
-        *reinterpret_cast<half4_t*>(o_hi + p * C + c) = h4;
-        *reinterpret_cast<half4_t*>(o_lo + p * C + c) = l4;
     }
     fn_flag_range(range_flag, sat);
 }
@@ -219,20 +107,10 @@ __global__ __launch_bounds__(256) void midas_layernorm_kernel(const float* __res
         if (q < Q) {
             const floatx4 ga = *reinterpret_cast<const floatx4*>(gamma + q * 4), be = *reinterpret_cast<const floatx4*>(beta + q * 4);
             floatx4 o;
-            half4_t h4, l4;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                o[e] = v[k][e] * rstd * ga[e] + be[e];
-                half_t hh, ll;
-                sat |= fn_split(o[e], scale, hh, ll);
-                h4[e] = hh;
-                l4[e] = ll;
-            }
+            for (int e = 0; e < 4; ++e) o[e] = v[k][e] * rstd * ga[e] + be[e];
             if (y) *reinterpret_cast<floatx4*>(y + row * C + q * 4) = o;
-            if (o_hi) {
-                *reinterpret_cast<half4_t*>(o_hi + row * C + q * 4) = h4;
-                *reinterpret_cast<half4_t*>(o_lo + row * C + q * 4) = l4;
-            }
+            sat |= fn_split_store4<true>(o, scale, o_hi, o_lo, row * C + q * 4);
         }
     }
     fn_flag_range(o_hi ? range_flag : nullptr, sat);
@@ -267,18 +145,7 @@ __global__ __launch_bounds__(256) void midas_head_merge_kernel(const float* __re
         const floatx4 v = *reinterpret_cast<const floatx4*>(x + (((int64_t)h * n + img) * L + t) * 64 + d);
         const int64_t o = row * heads * 64 + h * 64 + d;
         if (out) *reinterpret_cast<floatx4*>(out + o) = v;
-        if (o_hi) {
-            half4_t h4, l4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                half_t hh, ll;
-                sat |= fn_split(v[e], scale, hh, ll);
-                h4[e] = hh;
-                l4[e] = ll;
-            }
-            *reinterpret_cast<half4_t*>(o_hi + o) = h4;
-            *reinterpret_cast<half4_t*>(o_lo + o) = l4;
-        }
+        if (o_hi) sat |= fn_split_store4(v, scale, o_hi, o_lo, o);
     }
     fn_flag_range(range_flag, sat);
 }
@@ -294,21 +161,13 @@ __global__ __launch_bounds__(256) void midas_rowbias_gelu_kernel(const float* __
         const int64_t row = idx / Q;
         floatx4 v = *reinterpret_cast<const floatx4*>(x + row * C + c);
         const floatx4 b = *reinterpret_cast<const floatx4*>(rowbias + (row / rows_per_img) * C + c);
-        half4_t h4, l4;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float t = v[e] + b[e];
             v[e] = 0.5f * t * (1.f + erff(t * 0.70710678118654752440f));
-            half_t hh, ll;
-            sat |= fn_split(v[e], scale, hh, ll);
-            h4[e] = hh;
-            l4[e] = ll;
         }
         if (out) *reinterpret_cast<floatx4*>(out + row * C + c) = v;
-        if (o_hi) {
-            *reinterpret_cast<half4_t*>(o_hi + row * C + c) = h4;
-            *reinterpret_cast<half4_t*>(o_lo + row * C + c) = l4;
-        }
+        sat |= fn_split_store4<true>(v, scale, o_hi, o_lo, row * C + c);
     }
     fn_flag_range(o_hi ? range_flag : nullptr, sat);
 }
@@ -425,8 +284,7 @@ extern "C" int midas_input(const uint8_t* frames, float* out, int n, int H, int 
 
 extern "C" size_t midas_groupnorm_workspace_bytes(int n, int P, int C) {
     if (n <= 0 || P <= 0 || !md_gn_channels(C)) return 0;
-    const size_t chunks = ((size_t)P + MD_GN_ROWS - 1) / MD_GN_ROWS;
-    return (size_t)n * chunks * MD_GROUPS * 2 * sizeof(double);
+    return gn_workspace_bytes(n, P, false);
 }
 
 extern "C" int midas_groupnorm_stats(const float* x, float* mean, float* rstd, void* workspace, size_t workspace_bytes, int n,
@@ -436,13 +294,7 @@ extern "C" int midas_groupnorm_stats(const float* x, float* mean, float* rstd, v
     if (n > 65535 || (int64_t)n * P >= (int64_t)1 << 31) return FRESCO_EUNSUPPORTED;
     if (!aligned_to(x, 16) || !aligned_to(workspace, 8) || !aligned_to(mean, 4) || !aligned_to(rstd, 4)) return FRESCO_EINVAL;
     if (workspace_bytes < midas_groupnorm_workspace_bytes(n, P, C)) return FRESCO_EWORKSPACE;
-    const int chunks = (P + MD_GN_ROWS - 1) / MD_GN_ROWS;
-    hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(midas_gn_stats_kernel, dim3(chunks, n), dim3(256), 0, st, x, static_cast<double*>(workspace), P, C, chunks);
-    if (int rc = check_launch()) return rc;
-    hipLaunchKernelGGL(midas_gn_finish_kernel, dim3((n * MD_GROUPS + 255) / 256), dim3(256), 0, st,
-                       static_cast<const double*>(workspace), mean, rstd, n, chunks, (double)P * (C / MD_GROUPS), eps);
-    return check_launch();
+    return gn_statistics(x, workspace, mean, rstd, n, P, C, eps, as_stream(stream));
 }
 
 extern "C" int midas_groupnorm_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
@@ -471,7 +323,7 @@ extern "C" int midas_pool(const float* x, float* out, void* out_hi, void* out_lo
     if (!aligned_to(x, 16) || !aligned_to(out, 16) || !aligned_to(out_hi, 8) || !aligned_to(out_lo, 8)) return FRESCO_EINVAL;
     const int OH = H / 2, OW = W / 2;
     const int64_t total = (int64_t)n * OH * OW * (C / 4);
-    hipLaunchKernelGGL(midas_pool_kernel, dim3(stream_blocks(total)), dim3(256), 0, as_stream(stream), x, out,
+    hipLaunchKernelGGL(pool3s2_kernel<0>, dim3(stream_blocks(total)), dim3(256), 0, as_stream(stream), x, out,
                        static_cast<half_t*>(out_hi), static_cast<half_t*>(out_lo), total, H, W, OH, OW, split_scale, range_flag);
     return check_launch();
 }

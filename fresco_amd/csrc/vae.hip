@@ -3,7 +3,8 @@
 //   vae_input_kernel       latents NCHW fp16 -> post_quant_conv (4 -> 4, fp32) -> fp16 NHWC rows padded to conv_in's K chunk
 //   vae_conv_kernel<9>     3 x 3, stride 1, pad 1 implicit-GEMM convolution, optionally through a nearest 2x upsample
 //   vae_conv_kernel<1>     1 x 1 / linear form; per-image weight matrices (Q K^T, P V) and a per-row bias (V^T) as options
-//   vae_gn_stats_kernel / vae_gn_finish_kernel / vae_gn_apply_kernel   GroupNorm(32) [+ SiLU], fp64 statistics
+//   gn_stats_kernel<half_t> / gn_finish_kernel (groupnorm_stats.h, shared with midas.hip) / vae_gn_apply_kernel
+//                          GroupNorm(32) [+ SiLU], fp64 statistics
 //   vae_softmax_kernel     fp32 scores -> fp16 probabilities, one workgroup per row
 //
 // vae_conv_kernel: plain fp16 operands, one v_mfma_f32_32x32x16_f16 per product, fp32 accumulators.  A workgroup of four
@@ -24,12 +25,12 @@
 // with the pixel tile fastest, so one column tile's weights (1.2 MB at K = 4608) stay in that XCD's L2.
 #include "common.h"
 #include "lds_dma.h"
+#include "groupnorm_stats.h"
 #include "../../include/fresco_vae.h"
 
 namespace fresco {
 
-constexpr int VA_GROUPS = 32;
-constexpr int VA_GN_ROWS = 256;  // pixels per workgroup of the statistics pass
+constexpr int VA_GROUPS = GN_GROUPS;
 constexpr int VC_BM = 128, VC_BN = 128, VC_BK = 32;
 constexpr int VC_TH = 8, VC_TW = 16, VC_WW = VC_TW + 2, VC_NPOS = (VC_TH + 2) * VC_WW;
 constexpr int VC_A_BYTES = 12 * 1024;  // 12 pieces of 64 lanes x 16 bytes = 192 window rows of 64 bytes (180 used)
@@ -287,65 +288,6 @@ __global__ __launch_bounds__(256) void vae_input_kernel(const half_t* __restrict
     }
 }
 
-// midas_gn_stats_kernel on fp16 rows: grid (chunks, n); thread t owns the four channels 4 (t % Q) .. + 3, Q = C / 4 (a
-// divisor of 256), of the pixels t / Q, t / Q + 256 / Q, ... of its chunk, one fp64 sum pair per HALF of them (two channels
-// never straddle a group: C / 32 is even).  Thread g < 32 then adds the 512 halves that belong to group g in index order.
-__global__ __launch_bounds__(256) void vae_gn_stats_kernel(const half_t* __restrict__ x, double* __restrict__ part, int P, int C,
-                                                           int chunks) {
-    __shared__ double s1[512], s2[512];
-    const int Q = C >> 2, tid = threadIdx.x, q = tid % Q, step = 256 / Q;
-    const int img = blockIdx.y, chunk = blockIdx.x;
-    const int pb = chunk * VA_GN_ROWS, pe = min(pb + VA_GN_ROWS, P);
-    double a1[2] = {0.0, 0.0}, a2[2] = {0.0, 0.0};
-    for (int p = pb + tid / Q; p < pe; p += step) {
-        const half4_t v = *reinterpret_cast<const half4_t*>(x + ((int64_t)img * P + p) * C + q * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const double d = (double)(float)v[e];
-            a1[e >> 1] += d;
-            a2[e >> 1] += d * d;
-        }
-    }
-    s1[tid * 2] = a1[0];
-    s1[tid * 2 + 1] = a1[1];
-    s2[tid * 2] = a2[0];
-    s2[tid * 2 + 1] = a2[1];
-    __syncthreads();
-    if (tid < VA_GROUPS) {
-        const int lcpg = 31 - __clz(C / VA_GROUPS);  // (C is a power of two: launcher)
-        double t1 = 0.0, t2 = 0.0;
-        for (int e = 0; e < 512; ++e) {
-            const int ch = ((e >> 1) & (Q - 1)) * 4 + (e & 1) * 2;
-            if ((ch >> lcpg) == tid) {
-                t1 += s1[e];
-                t2 += s2[e];
-            }
-        }
-        double* o = part + (((int64_t)img * chunks + chunk) * VA_GROUPS + tid) * 2;
-        o[0] = t1;
-        o[1] = t2;
-    }
-}
-
-__global__ __launch_bounds__(256) void vae_gn_finish_kernel(const double* __restrict__ part, float* __restrict__ mean,
-                                                            float* __restrict__ rstd, int n, int chunks, double count,
-                                                            float eps) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n * VA_GROUPS) return;
-    const int img = idx / VA_GROUPS, g = idx - img * VA_GROUPS;
-    double t1 = 0.0, t2 = 0.0;
-    for (int c = 0; c < chunks; ++c) {
-        const double* o = part + (((int64_t)img * chunks + c) * VA_GROUPS + g) * 2;
-        t1 += o[0];
-        t2 += o[1];
-    }
-    const double m = t1 / count;
-    double var = t2 / count - m * m;
-    var = var > 0.0 ? var : 0.0;
-    mean[idx] = (float)m;
-    rstd[idx] = (float)(1.0 / sqrt(var + (double)eps));
-}
-
 // One thread per (pixel, eight channels); grid (blocks, n).  C is a power of two, so item idx of an image is its elements
 // 8 idx .. 8 idx + 7, channel 8 (idx & (C / 8 - 1)): shifts, no division (the first version divided int64 indices three
 // times per item and ran at a fifth of this one's rate).
@@ -475,8 +417,7 @@ extern "C" int vae_conv(const void* x, int64_t x_img_stride, const void* w, int6
 
 extern "C" size_t vae_groupnorm_workspace_bytes(int n, int P, int C) {
     if (n <= 0 || P <= 0 || !va_gn_channels(C)) return 0;
-    const size_t chunks = ((size_t)P + VA_GN_ROWS - 1) / VA_GN_ROWS;
-    return (size_t)n * chunks * VA_GROUPS * 2 * sizeof(double) + align_up((size_t)n * VA_GROUPS * 2 * sizeof(float), 8);
+    return gn_workspace_bytes(n, P, true);
 }
 
 extern "C" int vae_groupnorm(const void* x, const float* gamma, const float* beta, void* y, void* workspace,
@@ -487,16 +428,9 @@ extern "C" int vae_groupnorm(const void* x, const float* gamma, const float* bet
     if (!aligned_to(x, 16) || !aligned_to(y, 16) || !aligned_to(workspace, 8) || !aligned_to(gamma, 16) || !aligned_to(beta, 16))
         return FRESCO_EINVAL;
     if (workspace_bytes < vae_groupnorm_workspace_bytes(n, P, C)) return FRESCO_EWORKSPACE;
-    const int chunks = (P + VA_GN_ROWS - 1) / VA_GN_ROWS;
-    double* part = static_cast<double*>(workspace);
-    float* mean = reinterpret_cast<float*>(part + (size_t)n * chunks * VA_GROUPS * 2);
-    float* rstd = mean + (size_t)n * VA_GROUPS;
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(vae_gn_stats_kernel, dim3(chunks, n), dim3(256), 0, st, static_cast<const half_t*>(x), part, P, C, chunks);
-    if (int rc = check_launch()) return rc;
-    hipLaunchKernelGGL(vae_gn_finish_kernel, dim3((n * VA_GROUPS + 255) / 256), dim3(256), 0, st, part, mean, rstd, n, chunks,
-                       (double)P * (C / VA_GROUPS), eps);
-    if (int rc = check_launch()) return rc;
+    float *mean = nullptr, *rstd = nullptr;  // (in the workspace, behind the partial sums)
+    if (int rc = gn_statistics(static_cast<const half_t*>(x), workspace, mean, rstd, n, P, C, eps, st)) return rc;
     const int64_t per_img = (int64_t)P * (C / 8);
     const int lcpg = C == 128 ? 2 : (C == 256 ? 3 : 4);  // log2(C / 32)
     hipLaunchKernelGGL(vae_gn_apply_kernel, dim3(stream_blocks(per_img), n), dim3(256), 0, st, static_cast<const half_t*>(x), mean,

@@ -15,14 +15,13 @@ library ops (all three outputs).  DESIGN.md section 13 has the data flow and the
 two ways to use it.
 """
 import os
-import warnings
 
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import _detector, ops
+from ._detector import Act as _Act
 from .fnweights import WeightPlanes
 
 MIN_SIDE = 32  # layer3 / layer4 of a 32-pixel side are 2 pixels
@@ -199,17 +198,6 @@ class MergeLayer2(nn.Module):
             fea = self.relu(torch.add(fea, _resize(f, feats[0].shape[2:])))
         up_score.append(_resize(self.final_score(fea), x_size))
         return up_score
-
-
-class _Act:
-    """an activation of the native path: NHWC rows as fp32 (M, C) and / or operand planes written with `scale`"""
-    __slots__ = ("f32", "planes", "scale", "n", "H", "W", "C")
-
-    def __init__(self, f32, planes, scale, n, H, W, C):
-        self.f32, self.planes, self.scale, self.n, self.H, self.W, self.C = f32, planes, scale, n, H, W, C
-
-    def nhwc(self):
-        return self.f32.view(self.n, self.H, self.W, self.C)
 
 
 class TUN_bone(nn.Module):
@@ -398,23 +386,12 @@ class TUN_bone(nn.Module):
             raise RuntimeError("fresco_amd.egnet: the detector folds BatchNorm's running statistics -- call .eval() first")
         size = (frames.shape[1] // 2, frames.shape[2] // 2)
         chunks = [c.contiguous() for c in frames.split(self.max_frames)]
-        scores = None
-        if not self._use_library():
-            # the operand planes saturate beyond 65000 / scale (weights, BatchNorm folded in: beyond 63): every producer
-            # flags that on the device, ONE word is read back per call, and the call is recomputed with library ops when set
-            self._wts.out_of_range = False
-            with ops.fn_range_guard(frames.device) as guard:
-                scores = [self._score_native(c, taps) for c in chunks]
-            if guard.tripped() or self._wts.out_of_range:
-                scores = None
-                if not self._warned:
-                    self._warned = True
-                    warnings.warn("fresco_amd.egnet: an activation or a folded weight left the range of the split-fp16 "
-                                  "convolutions (|activation| * split_scale < 65000, |weight| < 63); calls of this module "
-                                  "are recomputed with library ops -- lower the stage's split scale", RuntimeWarning,
-                                  stacklevel=3)
-        if scores is None:
-            scores = [self._score_library(c, taps) for c in chunks]
+        scores = _detector.guarded_run(
+            self, frames.device, lambda: [self._score_native(c, taps) for c in chunks],
+            lambda: [self._score_library(c, taps) for c in chunks],
+            "fresco_amd.egnet: an activation or a folded weight left the range of the split-fp16 convolutions "
+            "(|activation| * split_scale < 65000, |weight| < 63); calls of this module are recomputed with library ops "
+            "-- lower the stage's split scale", use_library=self._use_library())
         outs = [ops.egnet_saliency(s, size, k=k, want_logit=want_logit) for s in scores]
         sal = outs[0][0] if len(outs) == 1 else torch.cat([o[0] for o in outs], 0)
         logit = None
@@ -435,25 +412,7 @@ def build_model(base_model_cfg="resnet"):
 def check_frames(frames):
     """a uint8 (n, H, W, 3) tensor, or a list of (H, W, 3) uint8 ndarrays of one size -> the uint8 (n, H, W, 3) tensor
     (on the host for ndarrays: the caller moves it)"""
-    if isinstance(frames, np.ndarray):
-        frames = [frames] if frames.ndim == 3 else list(frames)
-    if isinstance(frames, (list, tuple)):
-        if not frames:
-            raise ValueError("EGNet: no frames")
-        for f in frames:
-            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
-                raise TypeError("EGNet: frames are (H, W, 3) uint8 arrays")
-            if f.shape != frames[0].shape:
-                raise ValueError("EGNet: frames of one batch share a size, got %s and %s" % (frames[0].shape, f.shape))
-        frames = torch.from_numpy(np.stack(frames, 0))
-    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
-        raise TypeError("EGNet: frames must be a uint8 tensor (n, H, W, 3) or a list of uint8 arrays (H, W, 3)")
-    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] == 0:
-        raise ValueError("EGNet: frames must be (n, H, W, 3), got %s" % (tuple(frames.shape),))
-    if frames.shape[1] < MIN_SIDE or frames.shape[2] < MIN_SIDE:
-        raise ValueError("EGNet: frames of at least %d x %d, got %d x %d"
-                         % (MIN_SIDE, MIN_SIDE, frames.shape[1], frames.shape[2]))
-    return frames
+    return _detector.check_frames(frames, "EGNet", min_side=MIN_SIDE)
 
 
 def get_saliency(imgs, sod_model, dilate):

@@ -30,7 +30,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import _detector, ops
 from .fnweights import WeightPlanes as _Weights
 
 
@@ -464,21 +464,20 @@ class GMFlow(nn.Module):
     def forward_normalised(self, x, splits=2, pred_bidir_flow=True):
         """forward() from the network's own input: x (2b, 3, H, W) fp32, images 0 then images 1, already normalised
         ((img / 255.0 - mean) / std) -- what fresco_amd.flowcalc builds from uint8 frames on the device."""
+        # the dense layers' operands live as fp16 planes of x * 2^6 (weights: w * 2^10): an activation beyond +-1015 or a
+        # weight beyond +-63 would saturate there -- finite, wrong, and these flows feed occlusion thresholds and pixel
+        # correspondences.  Every producer kernel flags it on the device; one word is read back per forward and the
+        # forward is recomputed with library ops (exact fp32 range) when it is set.
+        flow = _detector.guarded_run(
+            self, x.device, lambda: self._forward_native(x, splits, pred_bidir_flow),
+            lambda: self._forward_library(x, splits, pred_bidir_flow),
+            "fresco_amd.GMFlow: an activation or weight left the range of the split-fp16 dense layers "
+            "(|activation| < 1015, |weight| < 63); this forward is recomputed with library ops",
+            use_library=not x.is_cuda or os.environ.get("FRESCO_GMFLOW_LIBRARY_OPS", "0") == "1", once=False)
+        return {"flow_preds": [flow]}
+
+    def _forward_library(self, x, splits, pred_bidir_flow):
         dev = x.device
-        if x.is_cuda and os.environ.get("FRESCO_GMFLOW_LIBRARY_OPS", "0") != "1":
-            # the dense layers' operands live as fp16 planes of x * 2^6 (weights: w * 2^10): an activation beyond +-1015 or a
-            # weight beyond +-63 would saturate there -- finite, wrong, and these flows feed occlusion thresholds and pixel
-            # correspondences.  Every producer kernel flags it on the device; one word is read back per forward and the
-            # forward is recomputed with library ops (exact fp32 range) when it is set.
-            self._wts.out_of_range = False
-            with ops.fn_range_guard(x.device) as guard:
-                flow = self._forward_native(x, splits, pred_bidir_flow)
-            if not (guard.tripped() or self._wts.out_of_range):
-                return {"flow_preds": [flow]}
-            import warnings
-            warnings.warn("fresco_amd.GMFlow: an activation or weight left the range of the split-fp16 dense layers "
-                          "(|activation| < 1015, |weight| < 63); this forward is recomputed with library ops",
-                          RuntimeWarning, stacklevel=3)
         feats = self.backbone(x)
         f0, f1 = feats.chunk(2, 0)
         b, c, h, w = f0.shape
@@ -500,4 +499,4 @@ class GMFlow(nn.Module):
         flow = corr.transpose(1, 2).reshape(-1, 2, h, w) - grid.unsqueeze(0)
         feature0 = torch.cat((f0, f1), 0) if pred_bidir_flow else f0
         flow = self.feature_flow_attn(feature0, flow)
-        return {"flow_preds": [self.upsample_flow(flow, feature0)]}
+        return self.upsample_flow(flow, feature0)

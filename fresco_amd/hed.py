@@ -14,14 +14,13 @@ with no host round trip.  The module tree carries the reference's parameter name
 section 12 has the data flow, the bytes and the range policy; INTEGRATION.md recipe G the two ways to use it.
 """
 import os
-import warnings
 
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import _detector, ops
 from .fnweights import WeightPlanes
 
 CHECKPOINT_NAME = "ControlNetHED.pth"
@@ -125,23 +124,12 @@ class ControlNetHED_Apache2(nn.Module):
         if not frames.is_cuda:
             raise ops.FrescoHipError("fresco_amd HED runs on the GPU only (got %s frames)" % frames.device)
         chunks = frames.split(self.max_frames)
-        per_chunk = None
-        if not self._use_library():
-            # the operand planes saturate beyond 65000 / scale (weights: beyond 63): every producer flags that on the
-            # device, ONE word is read back per call, and the call is recomputed with library ops when it is set
-            self._wts.out_of_range = False
-            with ops.fn_range_guard(frames.device) as guard:
-                per_chunk = [self._sides_native(c.contiguous()) for c in chunks]
-            if guard.tripped() or self._wts.out_of_range:
-                per_chunk = None
-                if not self._warned:
-                    self._warned = True
-                    warnings.warn("fresco_amd.ControlNetHED_Apache2: an activation or weight left the range of the "
-                                  "split-fp16 convolutions (|activation| * split_scale < 65000, |weight| < 63); forwards "
-                                  "of this module are recomputed with library ops -- lower the block's split scale",
-                                  RuntimeWarning, stacklevel=3)
-        if per_chunk is None:
-            per_chunk = [self._sides_library(c) for c in chunks]
+        per_chunk = _detector.guarded_run(
+            self, frames.device, lambda: [self._sides_native(c.contiguous()) for c in chunks],
+            lambda: [self._sides_library(c) for c in chunks],
+            "fresco_amd.ControlNetHED_Apache2: an activation or weight left the range of the split-fp16 convolutions "
+            "(|activation| * split_scale < 65000, |weight| < 63); forwards of this module are recomputed with library ops "
+            "-- lower the block's split scale", use_library=self._use_library())
         if len(per_chunk) == 1:
             return per_chunk[0]
         return [torch.cat([s[k] for s in per_chunk], 0) for k in range(5)]
@@ -155,38 +143,11 @@ class ControlNetHED_Apache2(nn.Module):
 def check_frames(frames):
     """a uint8 (n, H, W, 3) tensor, or a list of (H, W, 3) uint8 ndarrays of one size -> the uint8 (n, H, W, 3) tensor
     (on the host for ndarrays: the caller moves it)"""
-    if isinstance(frames, np.ndarray):
-        frames = [frames] if frames.ndim == 3 else list(frames)
-    if isinstance(frames, (list, tuple)):
-        if not frames:
-            raise ValueError("HED: no frames")
-        for f in frames:
-            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
-                raise TypeError("HED: frames are (H, W, 3) uint8 arrays")
-            if f.shape != frames[0].shape:
-                raise ValueError("HED: frames of one batch share a size, got %s and %s" % (frames[0].shape, f.shape))
-        frames = torch.from_numpy(np.stack(frames, 0))
-    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
-        raise TypeError("HED: frames must be a uint8 tensor (n, H, W, 3) or a list of uint8 arrays (H, W, 3)")
-    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] == 0:
-        raise ValueError("HED: frames must be (n, H, W, 3), got %s" % (tuple(frames.shape),))
-    if frames.shape[1] < MIN_SIDE or frames.shape[2] < MIN_SIDE:
-        raise ValueError("HED: frames of at least %d x %d, got %d x %d" % (MIN_SIDE, MIN_SIDE, frames.shape[1], frames.shape[2]))
-    return frames
+    return _detector.check_frames(frames, "HED", min_side=MIN_SIDE)
 
 
 def condition_dtype(dtype):
-    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
-        raise TypeError("HED: the ControlNet condition is fp16, bf16 or fp32, got %s" % (dtype,))
-    return dtype
-
-
-def _default_checkpoint():
-    try:
-        from annotator.util import annotator_ckpts_path
-    except ImportError:
-        return None
-    return os.path.join(annotator_ckpts_path, CHECKPOINT_NAME)
+    return _detector.condition_dtype(dtype, "HED")
 
 
 class HEDdetector:
@@ -198,7 +159,7 @@ class HEDdetector:
 
     def __init__(self, model_path=None, *, network=None, max_frames=None):
         if network is None:
-            path = model_path or _default_checkpoint()
+            path = model_path or _detector.default_checkpoint(CHECKPOINT_NAME)
             if path is None or not os.path.exists(path):
                 raise FileNotFoundError(
                     "fresco_amd.HEDdetector: no checkpoint%s. Put %s (lllyasviel/Annotators) into the reference's "

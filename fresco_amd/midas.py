@@ -20,7 +20,6 @@ DESIGN.md section 16 has the data flow, the padding origins and what is unverifi
 use it.
 """
 import os
-import warnings
 from collections import OrderedDict
 
 import numpy as np
@@ -28,7 +27,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import _detector, ops
+from ._detector import Act as _Act
 from .fnweights import WeightPlanes
 
 CHECKPOINT_NAME = "dpt_hybrid-midas-501f0c75.pt"
@@ -233,17 +233,6 @@ class FeatureFusionBlock(nn.Module):
 class _Up2(nn.Module):
     def forward(self, x):
         return _up2(x)
-
-
-class _Act:
-    """an activation of the native path: NHWC rows as fp32 (M, C) and / or operand planes written with `scale`"""
-    __slots__ = ("f32", "planes", "scale", "n", "H", "W", "C")
-
-    def __init__(self, f32, planes, scale, n, H, W, C):
-        self.f32, self.planes, self.scale, self.n, self.H, self.W, self.C = f32, planes, scale, n, H, W, C
-
-    def nhwc(self):
-        return self.f32.view(self.n, self.H, self.W, self.C)
 
 
 class DPTDepthModel(nn.Module):
@@ -517,22 +506,12 @@ class DPTDepthModel(nn.Module):
         if not frames.is_cuda:
             raise ops.FrescoHipError("fresco_amd MiDaS runs on the GPU only (got %s frames)" % frames.device)
         chunks = [c.contiguous() for c in frames.split(self.max_frames)]
-        maps = None
-        if not self._use_library():
-            # the operand planes saturate beyond 65000 / scale (weights: beyond 63): every producer flags that on the
-            # device, ONE word is read back per call, and the call is recomputed with library ops when it is set
-            self._wts.out_of_range = False
-            with ops.fn_range_guard(frames.device) as guard:
-                maps = [self._depth_native(c, taps) for c in chunks]
-            if guard.tripped() or self._wts.out_of_range:
-                maps = None
-                if not self._warned:
-                    self._warned = True
-                    warnings.warn("fresco_amd.midas: an activation or a weight left the range of the split-fp16 products "
-                                  "(|activation| * split_scale < 65000, |weight| < 63); calls of this module are recomputed "
-                                  "with library ops -- lower the stage's split scale", RuntimeWarning, stacklevel=3)
-        if maps is None:
-            maps = [self._depth_library(c, taps) for c in chunks]
+        maps = _detector.guarded_run(
+            self, frames.device, lambda: [self._depth_native(c, taps) for c in chunks],
+            lambda: [self._depth_library(c, taps) for c in chunks],
+            "fresco_amd.midas: an activation or a weight left the range of the split-fp16 products "
+            "(|activation| * split_scale < 65000, |weight| < 63); calls of this module are recomputed with library ops "
+            "-- lower the stage's split scale", use_library=self._use_library())
         return maps[0] if len(maps) == 1 else torch.cat(maps, 0)
 
     def detect(self, frames, a=np.pi * 2.0, bg_th=0.1, cond_dtype=None):
@@ -544,39 +523,11 @@ def check_frames(frames):
     """a uint8 (n, H, W, 3) tensor, or a list of (H, W, 3) uint8 ndarrays of one size -> the uint8 (n, H, W, 3) tensor
     (on the host for ndarrays: the caller moves it).  The sides must be multiples of 32: the token grid is the frame / 16
     and layer 4 halves it once more (FRESCO resizes its frames to multiples of 64)."""
-    if isinstance(frames, np.ndarray):
-        frames = [frames] if frames.ndim == 3 else list(frames)
-    if isinstance(frames, (list, tuple)):
-        if not frames:
-            raise ValueError("MiDaS: no frames")
-        for f in frames:
-            if not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3:
-                raise TypeError("MiDaS: frames are (H, W, 3) uint8 arrays")
-            if f.shape != frames[0].shape:
-                raise ValueError("MiDaS: frames of one batch share a size, got %s and %s" % (frames[0].shape, f.shape))
-        frames = torch.from_numpy(np.stack(frames, 0))
-    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
-        raise TypeError("MiDaS: frames must be a uint8 tensor (n, H, W, 3) or a list of uint8 arrays (H, W, 3)")
-    if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] == 0:
-        raise ValueError("MiDaS: frames must be (n, H, W, 3), got %s" % (tuple(frames.shape),))
-    if frames.shape[1] % SIDE_MULTIPLE or frames.shape[2] % SIDE_MULTIPLE or 0 in frames.shape[1:3]:
-        raise ValueError("MiDaS: frame sides must be multiples of %d, got %d x %d"
-                         % (SIDE_MULTIPLE, frames.shape[1], frames.shape[2]))
-    return frames
+    return _detector.check_frames(frames, "MiDaS", multiple=SIDE_MULTIPLE)
 
 
 def condition_dtype(dtype):
-    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
-        raise TypeError("MiDaS: the ControlNet condition is fp16, bf16 or fp32, got %s" % (dtype,))
-    return dtype
-
-
-def _default_checkpoint():
-    try:
-        from annotator.util import annotator_ckpts_path
-    except ImportError:
-        return None
-    return os.path.join(annotator_ckpts_path, CHECKPOINT_NAME)
+    return _detector.condition_dtype(dtype, "MiDaS")
 
 
 def load_checkpoint(network, path):
@@ -597,7 +548,7 @@ class MidasDetector:
 
     def __init__(self, model_path=None, *, network=None, max_frames=None):
         if network is None:
-            path = model_path or _default_checkpoint()
+            path = model_path or _detector.default_checkpoint(CHECKPOINT_NAME)
             if path is None or not os.path.exists(path):
                 raise FileNotFoundError(
                     "fresco_amd.MidasDetector: no checkpoint%s. Put %s (lllyasviel/ControlNet, annotator/ckpts) into the "

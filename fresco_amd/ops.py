@@ -36,6 +36,13 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _planes(rows, C, device, want=True):
+    """a pair of uninitialised (hi, lo) fp16 operand planes of (rows, C), or (None, None) when they are not wanted"""
+    if not want:
+        return None, None
+    return (torch.empty(rows, C, dtype=torch.float16, device=device), torch.empty(rows, C, dtype=torch.float16, device=device))
+
+
 def _f32c(t):
     return t.to(torch.float32).contiguous()
 
@@ -485,8 +492,7 @@ def fn_prep(x, mean=None, rstd=None, residual=None, rows_per_img=0, relu_a=False
         hi, lo, ldo = out_split
     elif want_split:
         ldo = ld or C
-        hi = torch.empty(M, ldo, dtype=torch.float16, device=x.device)
-        lo = torch.empty(M, ldo, dtype=torch.float16, device=x.device)
+        hi, lo = _planes(M, ldo, x.device)
     rc = _lib.load().fresco_fn_prep(x.data_ptr(), _ptr(mean), _ptr(rstd), _ptr(residual), _ptr(y), _ptr(hi), _ptr(lo), M, C,
                                     int(ldo), int(rows_per_img), int(relu_a), int(relu_b), float(scale),
                                     _fn_flag_ptr(x.device), _stream())
@@ -557,13 +563,11 @@ def fn_gemm(a, w, N, K, bias=None, act=0, conv=None, M=None, want_f32=True, want
         obs, ldc = M * ocb, ocb
     else:
         out = out_f32 if out_f32 is not None else (torch.empty(M, N, dtype=torch.float32, device=dev) if want_f32 else None)
-    oh = ol = None
     ldo = N
     if out_split is not None:
         oh, ol, ldo = out_split
-    elif want_split:
-        oh = torch.empty(M, N, dtype=torch.float16, device=dev)
-        ol = torch.empty(M, N, dtype=torch.float16, device=dev)
+    else:
+        oh, ol = _planes(M, N, dev, want_split)
     stats = None
     fused = instance_norm_eps is not None and conv is not None and (M // conv[0]) % 256 == 0
     if fused:
@@ -597,13 +601,11 @@ def fn_layernorm(x, gamma, beta, residual=None, eps=1e-5, want_f32=True, want_sp
     M, C = x.shape
     gamma, beta, residual = (_fn_f32_operand(t, n_, x) for t, n_ in ((gamma, "gamma"), (beta, "beta"), (residual, "residual")))
     y = torch.empty_like(x) if want_f32 else None
-    oh = ol = None
     ldo = C
     if out_split is not None:
         oh, ol, ldo = out_split
-    elif want_split:
-        oh = torch.empty(M, C, dtype=torch.float16, device=x.device)
-        ol = torch.empty(M, C, dtype=torch.float16, device=x.device)
+    else:
+        oh, ol = _planes(M, C, x.device, want_split)
     rc = _lib.load().fresco_fn_layernorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(residual), _ptr(y), _ptr(oh),
                                          _ptr(ol), C, int(ldo), M, C, float(eps), FN_A_SCALE, _fn_flag_ptr(x.device),
                                          _stream())
@@ -1019,8 +1021,7 @@ def hed_input(frames, norm, scale=FN_A_SCALE):
     scale = _split_scale(scale)
     _need_gpu(frames)
     n, H, W, _ = frames.shape
-    hi = torch.empty(n * H * W, 32, dtype=torch.float16, device=frames.device)
-    lo = torch.empty_like(hi)
+    hi, lo = _planes(n * H * W, 32, frames.device)
     rc = _lib.load().fresco_hed_input(frames.data_ptr(), norm.data_ptr(), hi.data_ptr(), lo.data_ptr(), n, H, W, scale,
                                       _fn_flag_ptr(frames.device), _stream())
     _lib.check(rc, "fresco_hed_input(n=%d,H=%d,W=%d)" % (n, H, W))
@@ -1050,10 +1051,7 @@ def hed_side_pool(h, n, H, W, weight, bias=None, want_proj=True, want_pool=True,
     scale = _split_scale(scale)
     _need_gpu(h)
     proj = torch.empty(n, H, W, dtype=torch.float32, device=h.device) if want_proj else None
-    hi = lo = None
-    if want_pool:
-        hi = torch.empty(n * (H // 2) * (W // 2), C, dtype=torch.float16, device=h.device)
-        lo = torch.empty_like(hi)
+    hi, lo = _planes(n * (H // 2) * (W // 2), C, h.device, want_pool)
     rc = _lib.load().fresco_hed_side_pool(h.data_ptr(), weight.data_ptr(), _ptr(bias), _ptr(proj), _ptr(hi), _ptr(lo), n, H,
                                           W, C, scale, _fn_flag_ptr(h.device), _stream())
     _lib.check(rc, "fresco_hed_side_pool(n=%d,H=%d,W=%d,C=%d)" % (n, H, W, C))
@@ -1131,8 +1129,7 @@ def egnet_pool(x, want_f32=False, scale=FN_A_SCALE):
     n, H, W, C = x.shape
     OH, OW = egnet_pool_size(H), egnet_pool_size(W)
     out = torch.empty(n, OH, OW, C, dtype=torch.float32, device=x.device) if want_f32 else None
-    hi = torch.empty(n * OH * OW, C, dtype=torch.float16, device=x.device)
-    lo = torch.empty_like(hi)
+    hi, lo = _planes(n * OH * OW, C, x.device)
     rc = _lib.load().fresco_egnet_pool(x.data_ptr(), _ptr(out), hi.data_ptr(), lo.data_ptr(), n, H, W, C, scale,
                                        _fn_flag_ptr(x.device), _stream())
     _lib.check(rc, "fresco_egnet_pool(n=%d,H=%d,W=%d,C=%d)" % (n, H, W, C))
@@ -1160,10 +1157,7 @@ def egnet_resize_add(x, size, addend=None, relu=False, want_f32=True, want_split
     scale = _split_scale(scale)
     _need_gpu(x)
     out = torch.empty(n, H, W, C, dtype=torch.float32, device=x.device) if want_f32 else None
-    hi = lo = None
-    if want_split:
-        hi = torch.empty(n * H * W, C, dtype=torch.float16, device=x.device)
-        lo = torch.empty_like(hi)
+    hi, lo = _planes(n * H * W, C, x.device, want_split)
     rc = _lib.load().fresco_egnet_resize_add(x.data_ptr(), _ptr(addend), _ptr(out), _ptr(hi), _ptr(lo), n, h, w, H, W, C,
                                              int(bool(relu)), scale, _fn_flag_ptr(x.device), _stream())
     _lib.check(rc, "fresco_egnet_resize_add(n=%d,%dx%d->%dx%d,C=%d)" % (n, h, w, H, W, C))
@@ -1242,6 +1236,24 @@ def _u8_frames(frames, name):
     return frames
 
 
+def _cached_table(cache, cache_max, key, what, nbytes, build, args, device):
+    """the int32 table the library builds on the host for `args` (nbytes(*args) sizes it, build(*args, buffer, bytes) fills
+    it), uploaded once per `key` and kept in `cache`, the oldest entry going first beyond cache_max"""
+    tab = cache.get(key)
+    if tab is None:
+        need = nbytes(*args)
+        if need == 0:  # the geometry is refused: let the call say why
+            _lib.check(build(*args, None, 0), what)
+            raise FrescoHipError("%s: no table for this geometry" % what)
+        host = (ctypes.c_int32 * (need // 4))()
+        _lib.check(build(*args, ctypes.addressof(host), need), what)
+        tab = torch.frombuffer(host, dtype=torch.int32).to(device)  # (a blocking copy: `host` may go afterwards)
+        while len(cache) >= cache_max:
+            cache.pop(next(iter(cache)))
+        cache[key] = tab
+    return tab
+
+
 _AREA_TABLES = {}      # (H0, W0, H, W, device) -> the coverage tables of the geometry on that device, int32 words
 _AREA_TABLES_MAX = 32  # geometries kept; the oldest goes first
 
@@ -1249,22 +1261,10 @@ _AREA_TABLES_MAX = 32  # geometries kept; the oldest goes first
 def _area_table(H0, W0, H, W, device):
     """the two coverage tables of INTER_AREA for one geometry: built on the host by the library (keyframe_resize_table),
     uploaded once and kept; the kernel walks them in their order"""
-    key = (H0, W0, H, W, str(device))
-    tab = _AREA_TABLES.get(key)
-    if tab is None:
-        lib = _lib.load()
-        what = "keyframe_resize_table(%dx%d->%dx%d)" % (H0, W0, H, W)
-        need = lib.keyframe_resize_table_bytes(H0, W0, H, W)
-        if need == 0:  # the geometry is refused: let the call say why
-            _lib.check(lib.keyframe_resize_table(H0, W0, H, W, None, 0), what)
-            raise FrescoHipError("%s: no table for this geometry" % what)
-        host = (ctypes.c_int32 * (need // 4))()
-        _lib.check(lib.keyframe_resize_table(H0, W0, H, W, ctypes.addressof(host), need), what)
-        tab = torch.frombuffer(host, dtype=torch.int32).to(device)  # (a blocking copy: `host` may go afterwards)
-        while len(_AREA_TABLES) >= _AREA_TABLES_MAX:
-            _AREA_TABLES.pop(next(iter(_AREA_TABLES)))
-        _AREA_TABLES[key] = tab
-    return tab
+    lib = _lib.load()
+    return _cached_table(_AREA_TABLES, _AREA_TABLES_MAX, (H0, W0, H, W, str(device)),
+                         "keyframe_resize_table(%dx%d->%dx%d)" % (H0, W0, H, W), lib.keyframe_resize_table_bytes,
+                         lib.keyframe_resize_table, (H0, W0, H, W), device)
 
 
 def resize_area_u8(frames, H, W):
@@ -1292,22 +1292,10 @@ _TAP_TABLES_MAX = 32  # geometries kept; the oldest goes first
 def _tap_table(H0, W0, H, W, method, device):
     """the tap table of one geometry and method (per axis and output index the first source index and the 8 or 2 fixed-point
     coefficients): built on the host by the library (frame_resize_table), uploaded once and kept"""
-    key = (H0, W0, H, W, method, str(device))
-    tab = _TAP_TABLES.get(key)
-    if tab is None:
-        lib = _lib.load()
-        what = "frame_resize_table(%dx%d->%dx%d, method %d)" % (H0, W0, H, W, method)
-        need = lib.frame_resize_table_bytes(H0, W0, H, W, method)
-        if need == 0:  # the geometry is refused: let the call say why
-            _lib.check(lib.frame_resize_table(H0, W0, H, W, method, None, 0), what)
-            raise FrescoHipError("%s: no table for this geometry" % what)
-        host = (ctypes.c_int32 * (need // 4))()
-        _lib.check(lib.frame_resize_table(H0, W0, H, W, method, ctypes.addressof(host), need), what)
-        tab = torch.frombuffer(host, dtype=torch.int32).to(device)  # (a blocking copy: `host` may go afterwards)
-        while len(_TAP_TABLES) >= _TAP_TABLES_MAX:
-            _TAP_TABLES.pop(next(iter(_TAP_TABLES)))
-        _TAP_TABLES[key] = tab
-    return tab
+    lib = _lib.load()
+    return _cached_table(_TAP_TABLES, _TAP_TABLES_MAX, (H0, W0, H, W, method, str(device)),
+                         "frame_resize_table(%dx%d->%dx%d, method %d)" % (H0, W0, H, W, method), lib.frame_resize_table_bytes,
+                         lib.frame_resize_table, (H0, W0, H, W, method), device)
 
 
 def resize_taps_u8(frames, H, W, method):
@@ -1486,12 +1474,6 @@ def gram_target(x, workspace=None):
 MIDAS_GN_CHANNELS = (64, 128, 256, 512, 1024)
 
 
-def _planes(rows, C, device, want):
-    if not want:
-        return None, None
-    return (torch.empty(rows, C, dtype=torch.float16, device=device), torch.empty(rows, C, dtype=torch.float16, device=device))
-
-
 def midas_input(frames):
     """frames (n, H, W, 3) uint8 -> x / 127.5 - 1 as (n, H, W, 3) fp32 NHWC (midas_input)"""
     _dense(frames, "midas_input: frames", torch.uint8)
@@ -1552,12 +1534,12 @@ def midas_groupnorm(x, gamma, beta, relu=False, residual=None, eps=1e-5, want_f3
                                    float(eps), _stream())
     _lib.check(rc, "midas_groupnorm_stats(n=%d,P=%d,C=%d)" % (n, H * W, C))
     y = torch.empty_like(x) if want_f32 else None
-    hi = lo = None
     ph, pw = (H + 1, W + 1) if far_border else (H, W)
-    if want_split:
-        make = torch.zeros if far_border else torch.empty
-        hi = make(n * ph * pw, C, dtype=torch.float16, device=dev)
-        lo = make(n * ph * pw, C, dtype=torch.float16, device=dev)
+    if want_split and far_border:  # the border rows and columns are never written: zeros
+        hi = torch.zeros(n * ph * pw, C, dtype=torch.float16, device=dev)
+        lo = torch.zeros(n * ph * pw, C, dtype=torch.float16, device=dev)
+    else:
+        hi, lo = _planes(n * ph * pw, C, dev, want_split)
     rc = lib.midas_groupnorm_apply(x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                                    _ptr(residual), _ptr(y), _ptr(hi), _ptr(lo), n, H, W, C, ph, pw, int(bool(relu)), scale,
                                    _fn_flag_ptr(dev), _stream())

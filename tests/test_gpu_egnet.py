@@ -67,12 +67,14 @@ def test_input_matches_a_float64_cv2sod(shape):
     assert torch.equal(ops.egnet_input(_gpu(x)), got)
 
 
-@pytest.mark.parametrize("shape", [(2, 16, 18), (1, 17, 5), (1, 5, 16), (1, 18, 17)], ids=lambda s: "%dx%dx%d" % s)
+@pytest.mark.parametrize("shape", [(2, 16, 18), (1, 17, 5), (1, 5, 16), (1, 18, 17), (1, 5, 7), (1, 2, 2)],
+                         ids=lambda s: "%dx%dx%d" % s)
 def test_pool_matches_ceil_mode_max_pool(shape):
-    """16 -> 9, 18 -> 10, 17 -> 9, 5 -> 3 on either axis; negative values everywhere, so a padded tap must never win"""
+    """16 -> 9, 18 -> 10, 17 -> 9, 5 -> 3, 7 -> 4, 2 -> 2 on either axis (odd sizes: the last window hangs off the map);
+    negative values everywhere, so a padded tap must never win"""
     from fresco_amd import ops
     n, H, W = shape
-    sizes = {16: 9, 18: 10, 17: 9, 5: 3}
+    sizes = {16: 9, 18: 10, 17: 9, 5: 3, 7: 4, 2: 2}
     x = torch.randn(n, H, W, 64, generator=torch.Generator().manual_seed(H * 100 + W)) * 60.0 - 30.0
     x[:, ::3] *= 1e-3
     want = _nhwc(F.max_pool2d(x.permute(0, 3, 1, 2), 3, 2, 1, ceil_mode=True))

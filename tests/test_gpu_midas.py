@@ -56,13 +56,8 @@ def _check(name, got, ref, bound):
 # ---------------------------------------------------------------------------------------------------------------
 # the kernels
 # ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C", [64, 256, 1024], ids=lambda c: "C%d_cpg%d" % (c, c // 32))
-@pytest.mark.parametrize("residual", [False, True], ids=["plain", "residual"])
-def test_groupnorm_matches_float64(C, residual):
-    """(n, 18, 30): 540 pixels = three workgroups of the statistics pass, the last one partly filled; image 1 has its own
-    statistics; the planes also go into the far-side bordered buffer"""
+def _groupnorm_against_float64(n, H, W, C, residual):
     from fresco_amd import ops
-    n, H, W = 2, 18, 30
     x = _randn(n, H, W, C, seed=C) * 3.0 + 1.5
     x[1] = x[1] * 0.25 - 4.0
     gamma, beta = _randn(C, seed=C + 1) * 0.5 + 1.0, _randn(C, seed=C + 2)
@@ -90,6 +85,23 @@ def test_groupnorm_matches_float64(C, residual):
         b = bordered[k].view(n, H + 1, W + 1, C)
         assert torch.equal(b[:, :H, :W], planes[k].view(n, H, W, C))
         assert not b[:, H].any() and not b[:, :, W].any()
+
+
+@pytest.mark.parametrize("C", [64, 256, 1024], ids=lambda c: "C%d_cpg%d" % (c, c // 32))
+@pytest.mark.parametrize("residual", [False, True], ids=["plain", "residual"])
+def test_groupnorm_matches_float64(C, residual):
+    """(n, 18, 30): 540 pixels = three workgroups of the statistics pass, the last one partly filled; image 1 has its own
+    statistics; the planes also go into the far-side bordered buffer"""
+    _groupnorm_against_float64(2, 18, 30, C, residual)
+
+
+@pytest.mark.parametrize("C", [64, 1024], ids=lambda c: "C%d_cpg%d" % (c, c // 32))
+@pytest.mark.parametrize("size", [(1, 1), (17, 16)], ids=lambda s: "%dx%d" % s)
+def test_groupnorm_at_one_pixel_and_a_short_second_chunk(C, size):
+    """the edges of the statistics pass (csrc/groupnorm_stats.h): one pixel per image; 272 pixels = a full chunk and one of 16.
+    C = 1024: 256 quads, each thread walks its chunk one pixel per step; C = 64: two channels per group, so the two halves of
+    every quad belong to different groups"""
+    _groupnorm_against_float64(2, size[0], size[1], C, False)
 
 
 def _conv_bound(x64, w64, stride, pad4):
@@ -138,9 +150,10 @@ def test_same_stride2_conv_reads_the_far_border(shape):
     assert symmetric.shape == ref.shape and np.abs(symmetric - ref).max() > 100 * bound.max()  # (nn.Conv2d's origin is another)
 
 
-@pytest.mark.parametrize("shape", [(2, 16, 20), (1, 6, 34)], ids=lambda s: "%dx%dx%d" % s)
+@pytest.mark.parametrize("shape", [(2, 16, 20), (1, 6, 34), (1, 2, 2), (2, 6, 4)], ids=lambda s: "%dx%dx%d" % s)
 def test_pool_windows_start_at_the_even_pixel(shape):
-    """negative values everywhere, so padding must never win; the last output row / column see two input rows / columns"""
+    """negative values everywhere, so padding must never win; the last output row / column see two input rows / columns
+    (2 x 2: the one window is the whole map)"""
     from fresco_amd import ops
     n, H, W = shape
     x = _randn(n, H, W, 64, seed=H * W) * 40.0 - 60.0
@@ -150,7 +163,8 @@ def test_pool_windows_start_at_the_even_pixel(shape):
     ref = want.double().numpy()
     _check("pool planes", _planes64(planes).reshape(ref.shape), ref, 2.0 ** -21 * np.abs(ref) + 2.0 ** -25)
     ceil_mode = F.max_pool2d(x.permute(0, 3, 1, 2), 3, 2, 1, ceil_mode=True).permute(0, 2, 3, 1)[:, :H // 2, :W // 2]
-    assert not torch.equal(ceil_mode, want)  # (EGNet's pool starts one pixel earlier)
+    if min(H, W) > 2:  # (on a 2 x 2 map both windows hold all four pixels)
+        assert not torch.equal(ceil_mode, want)  # (EGNet's pool starts one pixel earlier)
 
 
 def test_layernorm_768():

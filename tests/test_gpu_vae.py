@@ -169,13 +169,8 @@ def test_conv_per_image_weights_in_both_attention_arrangements():
 # ---------------------------------------------------------------------------------------------------------------
 # GroupNorm + SiLU, softmax
 # ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("silu", [True, False], ids=["silu", "plain"])
-@pytest.mark.parametrize("C", [128, 256, 512], ids=lambda c: "C%d_cpg%d" % (c, c // 32))
-def test_groupnorm_silu_matches_float64(C, silu):
-    """(2, 18, 30): 540 pixels = three workgroups of the statistics pass, the last one partly filled; image 1 is shifted and
-    scaled, so that its statistics differ"""
+def _groupnorm_against_float64(n, H, W, C, silu):
     from fresco_amd import ops
-    n, H, W = 2, 18, 30
     x = _randn(n, H, W, C, seed=C) * 3.0 + 1.5
     x[1] = x[1] * 0.25 - 4.0
     x = x.half()
@@ -193,6 +188,22 @@ def test_groupnorm_silu_matches_float64(C, silu):
     y = ops.vae_groupnorm(x.to(DEV), gamma.to(DEV), beta.to(DEV), 1e-6, silu=silu)
     assert y.dtype == torch.float16 and y.shape == x.shape
     _check("groupnorm C=%d%s" % (C, " + SiLU" if silu else ""), y, ref, bound)
+
+
+@pytest.mark.parametrize("silu", [True, False], ids=["silu", "plain"])
+@pytest.mark.parametrize("C", [128, 256, 512], ids=lambda c: "C%d_cpg%d" % (c, c // 32))
+def test_groupnorm_silu_matches_float64(C, silu):
+    """(2, 18, 30): 540 pixels = three workgroups of the statistics pass, the last one partly filled; image 1 is shifted and
+    scaled, so that its statistics differ"""
+    _groupnorm_against_float64(2, 18, 30, C, silu)
+
+
+@pytest.mark.parametrize("C", [128, 512], ids=lambda c: "C%d_cpg%d" % (c, c // 32))
+@pytest.mark.parametrize("P", [1, 257])
+def test_groupnorm_at_one_pixel_and_a_second_chunk_of_one(C, P):
+    """the edges of the statistics pass (csrc/groupnorm_stats.h) on fp16 rows: one pixel per image, and 257 pixels = a full
+    chunk and one more pixel"""
+    _groupnorm_against_float64(2, 1, P, C, True)
 
 
 @pytest.mark.parametrize("Lk", [70, 1000, 4096])

@@ -37,7 +37,8 @@ def listing(tmp_path_factory):
 
 def test_vae_kernels_exist_and_do_not_spill(listing):
     _, kernels = listing
-    single = ("vae_input_kernel", "vae_gn_stats_kernel", "vae_gn_finish_kernel", "vae_gn_apply_kernel", "vae_softmax_kernel")
+    # the statistics pass comes from groupnorm_stats.h: fp16 rows (IDF16_E)
+    single = ("vae_input_kernel", "gn_stats_kernelIDF16_E", "gn_finish_kernel", "vae_gn_apply_kernel", "vae_softmax_kernel")
     for pat in single:
         assert len([n for n in kernels if pat in n]) == 1, (pat, sorted(kernels))
     conv = sorted(n for n in kernels if "vae_conv_kernel" in n)
@@ -55,7 +56,7 @@ def test_lds_is_what_the_comments_say(listing):
     _, kernels = listing
     lds = lambda pat: [r["lds"] for n, r in kernels.items() if pat in n]  # noqa: E731
     assert lds("vae_conv_kernel") == [0, 0]                 # dynamic: VC_LDS below
-    assert lds("vae_gn_stats_kernel") == [2 * 512 * 8]      # two fp64 arrays of one entry per half quad
+    assert lds("gn_stats_kernel") == [2 * 512 * 8]          # two fp64 arrays of one entry per half quad
     assert lds("vae_softmax_kernel") == [4 * 4] and lds("vae_gn_apply_kernel") == [0] and lds("vae_input_kernel") == [0]
     src = open(os.path.join(CSRC, "vae.hip")).read()
     consts = dict(re.findall(r"constexpr int (VC_[AB]_BYTES) = (\d+) \* 1024;", src))
