@@ -22,7 +22,8 @@ from .hed import ControlNetHED_Apache2, DoubleConvBlock, HEDdetector, patch_hed
 from .egnet import TUN_bone, build_model, get_saliency, patch_saliency
 from .canny import CannyDetector, patch_canny
 from .midas import DPTDepthModel, MidasDetector, patch_midas
-from .vae import VAEDecoder, patch_vae_decode, unpatch_vae_decode
+from .vae import (VAEDecoder, VAEEncoder, patch_vae, patch_vae_decode, patch_vae_encode, unpatch_vae, unpatch_vae_decode,
+                  unpatch_vae_encode)
 from .keyframe import (frame_errors, get_keyframe_ind, patch_keyframe_selection, resize_frames, resize_image, resize_size,
                        select_keyframes)
 from .paras import (correlation_matrices, forward_backward_consistency_check, get_flow_and_interframe_paras,
@@ -41,6 +42,7 @@ __all__ = [
     "CannyDetector", "patch_canny",
     "MidasDetector", "DPTDepthModel", "patch_midas",
     "VAEDecoder", "patch_vae_decode", "unpatch_vae_decode",
+    "VAEEncoder", "patch_vae_encode", "unpatch_vae_encode", "patch_vae", "unpatch_vae",
     "get_keyframe_ind", "frame_errors", "select_keyframes", "resize_frames", "resize_image", "resize_size",
     "patch_keyframe_selection",
 ]

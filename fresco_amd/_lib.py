@@ -164,6 +164,14 @@ VAE_SIGNATURES = {
 }
 VAE_OUT_F16, VAE_OUT_F32, VAE_OUT_F16_NCHW = 0, 1, 2  # VAE_OUT_* of the header
 
+# what the VAE encoder adds to them (csrc/vae_enc.hip), declared in include/fresco_vae_enc.h: named vaeenc_*
+VAE_ENC_SIGNATURES = {
+    "vaeenc_input": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "vaeenc_conv_down": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "vaeenc_moments": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "vaeenc_sample": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+}
+
 _lib = None
 
 
@@ -181,7 +189,7 @@ def load():
     except OSError as e:
         raise FrescoHipError("fresco_amd: cannot load %s: %s" % (LIB_PATH, e))
     for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
-            + list(MIDAS_SIGNATURES.items()) + list(VAE_SIGNATURES.items()):
+            + list(MIDAS_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(VAE_ENC_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

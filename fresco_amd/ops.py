@@ -1769,3 +1769,70 @@ def vae_softmax(scores, Lk, scale, ld_out=None):
     rc = _lib.load().vae_softmax(scores.data_ptr(), p.data_ptr(), rows, Lk, ld_in, ld_out, float(scale), _stream())
     _lib.check(rc, "vae_softmax(rows=%d,Lk=%d)" % (rows, Lk))
     return p
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# what the VAE encoder adds (include/fresco_vae_enc.h)
+# ---------------------------------------------------------------------------------------------------------------------
+def vaeenc_input(image, cpad=VAE_CIN_PAD):
+    """image (n, 3, H, W) fp16 NCHW -> (n, H, W, cpad) fp16 NHWC, channels 3 .. zero (vaeenc_input)"""
+    _dense(image, "vaeenc_input: image", torch.float16)
+    if image.dim() != 4 or image.shape[1] != 3 or image.numel() == 0:
+        raise ValueError("vaeenc_input: image must be (n, 3, H, W), got %s" % (tuple(image.shape),))
+    _need_gpu(image)
+    n, _, H, W = image.shape
+    out = torch.empty(n, H, W, cpad, dtype=torch.float16, device=image.device)
+    rc = _lib.load().vaeenc_input(image.data_ptr(), out.data_ptr(), n, H, W, cpad, _stream())
+    _lib.check(rc, "vaeenc_input(n=%d,H=%d,W=%d,cpad=%d)" % (n, H, W, cpad))
+    return out
+
+
+def vaeenc_conv_down(x, w, bias):
+    """Downsample2D(padding=0): x (n, H, W, cin) fp16 NHWC, w (cout, 9 cin) fp16 with k = (ky, kx, ci), bias (cout) fp32 ->
+    (n, H // 2, W // 2, cout) fp16 NHWC: the 3 x 3, stride-2 convolution behind a zero row at the bottom and a zero column on
+    the right (vaeenc_conv_down)"""
+    _dense(x, "vaeenc_conv_down: x", torch.float16, align=16)
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError("vaeenc_conv_down: x must be (n, H, W, cin), got %s" % (tuple(x.shape),))
+    n, H, W, cin = x.shape
+    _dense(w, "vaeenc_conv_down: w", torch.float16, align=16)
+    if w.dim() != 2 or w.shape[0] == 0 or w.shape[1] != 9 * cin:
+        raise ValueError("vaeenc_conv_down: w must be (cout, %d), got %s" % (9 * cin, tuple(w.shape)))
+    cout = w.shape[0]
+    _dense(bias, "vaeenc_conv_down: bias", torch.float32, (cout,), align=16)
+    _need_gpu(x, w, bias)
+    out = torch.empty(n, H // 2, W // 2, cout, dtype=torch.float16, device=x.device)
+    rc = _lib.load().vaeenc_conv_down(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), n, H, W, cin, cout, _stream())
+    _lib.check(rc, "vaeenc_conv_down(n=%d,H=%d,W=%d,cin=%d,cout=%d)" % (n, H, W, cin, cout))
+    return out
+
+
+def vaeenc_moments(h, weight, bias):
+    """h (n, hh, ww, 8) fp32 NHWC (conv_out through vae_conv with VAE_OUT_F32) -> quant_conv (weight (8, 8), bias (8) fp32) ->
+    the distribution's parameters (n, 8, hh, ww) fp16 NCHW (vaeenc_moments)"""
+    _dense(h, "vaeenc_moments: h", torch.float32, align=16)
+    if h.dim() != 4 or h.shape[3] != 8 or h.numel() == 0:
+        raise ValueError("vaeenc_moments: h must be (n, hh, ww, 8), got %s" % (tuple(h.shape),))
+    _dense(weight, "vaeenc_moments: weight", torch.float32, (8, 8))
+    _dense(bias, "vaeenc_moments: bias", torch.float32, (8,))
+    _need_gpu(h, weight, bias)
+    n, hh, ww, _ = h.shape
+    params = torch.empty(n, 8, hh, ww, dtype=torch.float16, device=h.device)
+    rc = _lib.load().vaeenc_moments(h.data_ptr(), weight.data_ptr(), bias.data_ptr(), params.data_ptr(), n, hh, ww, _stream())
+    _lib.check(rc, "vaeenc_moments(n=%d,h=%d,w=%d)" % (n, hh, ww))
+    return params
+
+
+def vaeenc_sample(parameters, noise, scale=1.0):
+    """parameters (n, 8, h, w) fp16 (mean | logvar), noise (n, 4, h, w) fp16 -> scale (mean + exp(0.5 clamp(logvar, -30, 20))
+    noise) as (n, 4, h, w) fp16, computed in fp32 and rounded once (vaeenc_sample)"""
+    _dense(parameters, "vaeenc_sample: parameters", torch.float16)
+    if parameters.dim() != 4 or parameters.shape[1] != 8 or parameters.numel() == 0:
+        raise ValueError("vaeenc_sample: parameters must be (n, 8, h, w), got %s" % (tuple(parameters.shape),))
+    n, _, hh, ww = parameters.shape
+    _dense(noise, "vaeenc_sample: noise", torch.float16, (n, 4, hh, ww))
+    _need_gpu(parameters, noise)
+    out = torch.empty_like(noise)
+    rc = _lib.load().vaeenc_sample(parameters.data_ptr(), noise.data_ptr(), out.data_ptr(), n, hh, ww, float(scale), _stream())
+    _lib.check(rc, "vaeenc_sample(n=%d,h=%d,w=%d)" % (n, hh, ww))
+    return out

@@ -1,4 +1,5 @@
-"""AutoencoderKL.decode of the SD-1.5 VAE on this package's kernels, for fp16 pipelines.
+"""AutoencoderKL.decode and .encode of the SD-1.5 VAE on this package's kernels, for fp16 pipelines (DESIGN.md sections 17
+and 18).
 
 `VAEDecoder.from_vae(vae)` packs the weights of `vae.post_quant_conv` and `vae.decoder` from the module's state dict;
 `decode(z)` returns what the reference's call sites consume (`pipe.vae.decode(z).sample`, pipe_FRESCO.py:44 and
@@ -7,6 +8,11 @@ run_fresco.py:251).  `patch_vae_decode(pipe)` rebinds `pipe.vae.decode`.  Every 
 convolution's `up2` addressing and never written, the mid block's attention runs Q K^T and P V on the same convolution
 kernel with per-image weight matrices.  There is no fallback: what is not this architecture, not fp16 or not on the GPU
 raises.
+
+`VAEEncoder.from_vae(vae)` is the other half (`vae.encoder`, `vae.quant_conv`): `encode(x).latent_dist.sample()` is what
+pipe_FRESCO.py:47 and :160 and diffusion_hacked.py:874 consume; `patch_vae_encode(pipe)` rebinds `pipe.vae.encode`,
+`patch_vae(pipe)` both methods.  Its resnets, mid block and stride-1 convolutions are the decoder's code and kernels; the
+three Downsample2D layers, the image input, quant_conv and the Gaussian's sample are include/fresco_vae_enc.h.
 
 Parameter names and the module layout are those of diffusers 0.19.3 (models/autoencoder_kl.py, vae.py,
 unet_2d_blocks.py, attention_processor.py), with the older spelling of the attention block (query / key / value /
@@ -34,12 +40,19 @@ class DecoderOutput:
         self.sample = sample
 
 
-def canonical_state_dict(sd):
-    """the post_quant_conv.* and decoder.* entries of a VAE state dict under the 0.19.3 names (old attention spelling
-    renamed)"""
+class EncoderOutput:
+    """what AutoencoderKL.encode returns with return_dict=True, as far as the call sites read it"""
+
+    def __init__(self, latent_dist):
+        self.latent_dist = latent_dist
+
+
+def canonical_state_dict(sd, prefixes=("decoder.", "post_quant_conv.")):
+    """the post_quant_conv.* and decoder.* entries (or those under `prefixes`) of a VAE state dict under the 0.19.3 names
+    (old attention spelling renamed)"""
     out = OrderedDict()
     for k, v in sd.items():
-        if not (k.startswith("decoder.") or k.startswith("post_quant_conv.")):
+        if not k.startswith(tuple(prefixes)):
             continue
         parts = k.split(".")
         if "attentions" in parts:
@@ -69,6 +82,16 @@ def up2_source_index(y, x, H, W):
     if y < 0 or y >= H or x < 0 or x >= W:
         return None
     return y >> 1, x >> 1
+
+
+def down_source_index(yo, xo, ky, kx, H, W):
+    """the index rule of vaeenc_conv_down: tap (ky, kx) of output pixel (yo, xo), yo < H // 2 and xo < W // 2, of an (H, W)
+    plane -> source pixel, or None where the zero row below or the zero column to the right of the plane is read; nothing
+    is padded on the top or left"""
+    y, x = 2 * yo + ky, 2 * xo + kx
+    if y >= H or x >= W:
+        return None
+    return y, x
 
 
 class _Layer:
@@ -111,68 +134,60 @@ class _Resnet:
             raise ValueError("fresco_amd.vae: %s.conv_shortcut is not %d -> %d" % (prefix, cin, cout))
 
 
-class VAEDecoder:
-    """The decoder half of an fp16 AutoencoderKL (block channels (128, 256, 512, 512), two layers per block, GroupNorm(32,
-    eps 1e-6), single-head attention at 512 channels in the mid block) on HIP kernels."""
+class _Half:
+    """What the two halves of the VAE share: taking named layers out of a state dict and accounting for every entry, the
+    mid block (resnet, single-head attention at the top width, resnet), and the layer calls."""
 
-    def __init__(self, state_dict, device=None, module=None):
-        sd = canonical_state_dict(state_dict)
+    def _open(self, state_dict, prefixes, device, module):
+        sd = canonical_state_dict(state_dict, prefixes)
         if not sd:
-            raise ValueError("fresco_amd.vae: the state dict has no decoder.* / post_quant_conv.* entries")
+            raise ValueError("fresco_amd.vae: the state dict has no %s entries" % " / ".join(p + "*" for p in prefixes))
         self.module = module
         self.device = torch.device(device) if device is not None else next(iter(sd.values())).device
-        dev = self.device
-        used = set()
+        self._sd, self._used = sd, set()
+        return sd
 
-        def take(cls, prefix, *a):
-            obj = cls(sd, prefix, dev, *a)
-            used.update(k for k in sd if k.startswith(prefix + "."))
-            return obj
+    def _take(self, cls, prefix, *a):
+        obj = cls(self._sd, prefix, self.device, *a)
+        self._used.update(k for k in self._sd if k.startswith(prefix + "."))
+        return obj
 
-        rev = BLOCK_CHANNELS[::-1]
-        top = rev[0]
-        pq_w, pq_b = sd.get("post_quant_conv.weight"), sd.get("post_quant_conv.bias")
-        if pq_w is None or pq_b is None or tuple(pq_w.shape) != (LATENT_CHANNELS, LATENT_CHANNELS, 1, 1):
-            raise ValueError("fresco_amd.vae: post_quant_conv must be a 1 x 1 convolution of %d -> %d channels" % (LATENT_CHANNELS, LATENT_CHANNELS))
-        used.update(("post_quant_conv.weight", "post_quant_conv.bias"))
-        self.pq_w = pq_w.detach().reshape(4, 4).to(dev, torch.float32).contiguous()
-        self.pq_b = pq_b.detach().to(dev, torch.float32).contiguous()
-        self.conv_in = take(_Layer, "decoder.conv_in", 3, ops.VAE_CIN_PAD)
-        if (self.conv_in.cin_real, self.conv_in.cout) != (LATENT_CHANNELS, top):
-            raise ValueError("fresco_amd.vae: decoder.conv_in is not %d -> %d" % (LATENT_CHANNELS, top))
-        self.mid = [take(_Resnet, "decoder.mid_block.resnets.%d" % i, top, top) for i in (0, 1)]
-        ap = "decoder.mid_block.attentions.0"
-        self.attn_norm = take(_Norm, ap + ".group_norm", top)
-        self.attn = {k: take(_Layer, ap + "." + k, 1) for k in ("to_q", "to_k", "to_v", "to_out.0")}
+    def _take_small_conv(self, name, c):
+        """a 1 x 1 convolution of c -> c channels that runs in fp32: (weight (c, c), bias (c)) fp32"""
+        w, b = self._sd.get(name + ".weight"), self._sd.get(name + ".bias")
+        if w is None or b is None or tuple(w.shape) != (c, c, 1, 1) or b.numel() != c:
+            raise ValueError("fresco_amd.vae: %s must be a 1 x 1 convolution of %d -> %d channels" % (name, c, c))
+        self._used.update((name + ".weight", name + ".bias"))
+        return (w.detach().reshape(c, c).to(self.device, torch.float32).contiguous(),
+                b.detach().to(self.device, torch.float32).contiguous())
+
+    def _take_mid(self, prefix, top):
+        self.mid = [self._take(_Resnet, "%s.resnets.%d" % (prefix, i), top, top) for i in (0, 1)]
+        ap = prefix + ".attentions.0"
+        self.attn_norm = self._take(_Norm, ap + ".group_norm", top)
+        self.attn = {k: self._take(_Layer, ap + "." + k, 1) for k in ("to_q", "to_k", "to_v", "to_out.0")}
         for k, lay in self.attn.items():
             if (lay.cin, lay.cout) != (top, top):
                 raise ValueError("fresco_amd.vae: %s.%s is not %d -> %d" % (ap, k, top, top))
-        # V^T = W_v x^T: to_v's weight is the kernel's pixel operand there, its bias a per-row one
-        self.up, cin = [], top
-        for b, cout in enumerate(rev):
-            res = [take(_Resnet, "decoder.up_blocks.%d.resnets.%d" % (b, i), cin if i == 0 else cout, cout)
-                   for i in range(LAYERS_PER_BLOCK + 1)]
-            ups = None
-            if b < len(rev) - 1:
-                ups = take(_Layer, "decoder.up_blocks.%d.upsamplers.0.conv" % b, 3)
-                if (ups.cin, ups.cout) != (cout, cout):
-                    raise ValueError("fresco_amd.vae: up block %d's upsampler is not %d -> %d" % (b, cout, cout))
-            elif any(k.startswith("decoder.up_blocks.%d.upsamplers" % b) for k in sd):
-                raise ValueError("fresco_amd.vae: the last up block has an upsampler")
-            self.up.append((res, ups))
-            cin = cout
-        self.norm_out = take(_Norm, "decoder.conv_norm_out", rev[-1])
-        self.conv_out = take(_Layer, "decoder.conv_out", 3)
-        if (self.conv_out.cin, self.conv_out.cout) != (rev[-1], 3):
-            raise ValueError("fresco_amd.vae: decoder.conv_out is not %d -> 3" % rev[-1])
-        extra = sorted(k for k in sd if k not in used)
-        if extra:
-            raise ValueError("fresco_amd.vae: not the SD-1.5 decoder: unexpected parameters %s" % extra[:4])
 
-    @classmethod
-    def from_vae(cls, vae, device=None):
-        """device: where the packed weights go; default: where the module's parameters are (decode needs the GPU)"""
-        return cls(vae.state_dict(), device=device, module=vae)
+    def _close(self, what):
+        extra = sorted(k for k in self._sd if k not in self._used)
+        del self._sd, self._used
+        if extra:
+            raise ValueError("fresco_amd.vae: not the SD-1.5 %s: unexpected parameters %s" % (what, extra[:4]))
+
+    def _refuse(self, x, name, channels, dims):
+        """what decode and encode do not take, refused before anything touches the GPU"""
+        m = self.module
+        if m is not None and (getattr(m, "use_slicing", False) or getattr(m, "use_tiling", False)):
+            raise NotImplementedError("fresco_amd.vae: slicing / tiling of the VAE is not supported; disable it on the module")
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("fresco_amd.vae: %s must be a tensor" % name)
+        if x.dtype != torch.float16:
+            raise TypeError("fresco_amd.vae: fp16 %s only (got %s); bf16 and fp32 VAEs are not supported"
+                            % ("latents" if name == "z" else "images", x.dtype))
+        if x.dim() != 4 or x.shape[1] != channels or x.numel() == 0:
+            raise ValueError("fresco_amd.vae: %s must be (n, %d, %s), got %s" % (name, channels, dims, tuple(x.shape)))
 
     # ---- layers ------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -193,6 +208,7 @@ class VAEDecoder:
         h = ops.vae_groupnorm(x, self.attn_norm.g, self.attn_norm.b, EPS, silu=False)
         q = ops.vae_conv(h, a["to_q"].w, a["to_q"].b, 1, n * L, 1, C, C, 1)
         k = ops.vae_conv(h, a["to_k"].w, a["to_k"].b, 1, n * L, 1, C, C, 1)
+        # V^T = W_v x^T: to_v's weight is the kernel's pixel operand there, its bias a per-row one
         vt = torch.zeros(n, C, Lp, dtype=torch.float16, device=x.device)
         ops.vae_conv(a["to_v"].w, h, a["to_v"].b, n, C, 1, C, L, 1, x_img_stride=0, w_img_stride=L * C, bias_rows=True,
                      ldo=Lp, out=vt)
@@ -202,29 +218,63 @@ class VAEDecoder:
         o = ops.vae_conv(p, vt, None, n, L, 1, Lp, C, 1, w_img_stride=C * Lp)
         return ops.vae_conv(o, a["to_out.0"].w, a["to_out.0"].b, 1, n * L, 1, C, C, 1, residual=x).view(n, H, W, C)
 
+    def _mid(self, x, n, H, W):
+        x = self._resnet(x, self.mid[0], n, H, W)
+        x = self._attention(x, n, H, W)
+        return self._resnet(x, self.mid[1], n, H, W)
+
+
+class VAEDecoder(_Half):
+    """The decoder half of an fp16 AutoencoderKL (block channels (128, 256, 512, 512), two layers per block, GroupNorm(32,
+    eps 1e-6), single-head attention at 512 channels in the mid block) on HIP kernels."""
+
+    def __init__(self, state_dict, device=None, module=None):
+        sd = self._open(state_dict, ("decoder.", "post_quant_conv."), device, module)
+        take = self._take
+        rev = BLOCK_CHANNELS[::-1]
+        top = rev[0]
+        self.pq_w, self.pq_b = self._take_small_conv("post_quant_conv", LATENT_CHANNELS)
+        self.conv_in = take(_Layer, "decoder.conv_in", 3, ops.VAE_CIN_PAD)
+        if (self.conv_in.cin_real, self.conv_in.cout) != (LATENT_CHANNELS, top):
+            raise ValueError("fresco_amd.vae: decoder.conv_in is not %d -> %d" % (LATENT_CHANNELS, top))
+        self._take_mid("decoder.mid_block", top)
+        self.up, cin = [], top
+        for b, cout in enumerate(rev):
+            res = [take(_Resnet, "decoder.up_blocks.%d.resnets.%d" % (b, i), cin if i == 0 else cout, cout)
+                   for i in range(LAYERS_PER_BLOCK + 1)]
+            ups = None
+            if b < len(rev) - 1:
+                ups = take(_Layer, "decoder.up_blocks.%d.upsamplers.0.conv" % b, 3)
+                if (ups.cin, ups.cout) != (cout, cout):
+                    raise ValueError("fresco_amd.vae: up block %d's upsampler is not %d -> %d" % (b, cout, cout))
+            elif any(k.startswith("decoder.up_blocks.%d.upsamplers" % b) for k in sd):
+                raise ValueError("fresco_amd.vae: the last up block has an upsampler")
+            self.up.append((res, ups))
+            cin = cout
+        self.norm_out = take(_Norm, "decoder.conv_norm_out", rev[-1])
+        self.conv_out = take(_Layer, "decoder.conv_out", 3)
+        if (self.conv_out.cin, self.conv_out.cout) != (rev[-1], 3):
+            raise ValueError("fresco_amd.vae: decoder.conv_out is not %d -> 3" % rev[-1])
+        self._close("decoder")
+
+    @classmethod
+    def from_vae(cls, vae, device=None):
+        """device: where the packed weights go; default: where the module's parameters are (decode needs the GPU)"""
+        return cls(vae.state_dict(), device=device, module=vae)
+
     # ---- the decoder -------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def decode(self, z, return_dict=True, generator=None, taps=None):
         """z (n, 4, h, w) fp16 on the GPU -> DecoderOutput(sample (n, 3, 8 h, 8 w) fp16), or (sample,) with
         return_dict=False.  taps: a dict that receives the TAPS tensors (NHWC copies)."""
-        m = self.module
-        if m is not None and (getattr(m, "use_slicing", False) or getattr(m, "use_tiling", False)):
-            raise NotImplementedError("fresco_amd.vae: slicing / tiling of the VAE is not supported; disable it on the module")
-        if not isinstance(z, torch.Tensor):
-            raise TypeError("fresco_amd.vae: z must be a tensor")
-        if z.dtype != torch.float16:
-            raise TypeError("fresco_amd.vae: fp16 latents only (got %s); bf16 and fp32 VAEs are not supported" % z.dtype)
-        if z.dim() != 4 or z.shape[1] != LATENT_CHANNELS or z.numel() == 0:
-            raise ValueError("fresco_amd.vae: z must be (n, %d, h, w), got %s" % (LATENT_CHANNELS, tuple(z.shape)))
+        self._refuse(z, "z", LATENT_CHANNELS, "h, w")
         ops._need_gpu(z)
         keep = (lambda name, t: taps.__setitem__(name, t.clone())) if taps is not None else (lambda name, t: None)
         n, _, H, W = z.shape
         x = ops.vae_input(z.contiguous(), self.pq_w, self.pq_b)
         x = self._conv(x, self.conv_in, n, H, W)
         keep("conv_in", x)
-        x = self._resnet(x, self.mid[0], n, H, W)
-        x = self._attention(x, n, H, W)
-        x = self._resnet(x, self.mid[1], n, H, W)
+        x = self._mid(x, n, H, W)
         keep("mid", x)
         for b, (res, ups) in enumerate(self.up):
             for r in res:
@@ -241,6 +291,114 @@ class VAEDecoder:
     __call__ = decode
 
 
+class DiagonalGaussian:
+    """diffusers' DiagonalGaussianDistribution over `parameters` (n, 8, h, w) fp16 (mean | logvar), as far as the call sites
+    and the class's attributes go.  `sample` is one kernel (vaeenc_sample); the other attributes are views or small torch
+    expressions for inspection."""
+
+    def __init__(self, parameters):
+        self.parameters = parameters
+        self.mean = parameters[:, :LATENT_CHANNELS]
+
+    @property
+    def logvar(self):
+        return torch.clamp(self.parameters[:, LATENT_CHANNELS:], -30.0, 20.0)
+
+    @property
+    def std(self):
+        return torch.exp(0.5 * self.logvar)
+
+    @property
+    def var(self):
+        return torch.exp(self.logvar)
+
+    def mode(self):
+        return self.mean
+
+    def sample(self, generator=None, scale=1.0):
+        """scale (mean + std noise), rounded once.  The noise is drawn as diffusers' randn_tensor draws it here -- one
+        torch.randn of the mean's shape in fp16, on the parameters' device, or on the CPU and then moved where the generator
+        is a CPU one -- so a seeded run consumes the random stream as the module would."""
+        p = self.parameters
+        shape = tuple(self.mean.shape)
+        if generator is not None and generator.device.type == "cpu" and p.device.type != "cpu":
+            noise = torch.randn(shape, generator=generator, device="cpu", dtype=p.dtype).to(p.device)
+        else:
+            noise = torch.randn(shape, generator=generator, device=p.device, dtype=p.dtype)
+        return ops.vaeenc_sample(p, noise, scale)
+
+
+class VAEEncoder(_Half):
+    """The encoder half of the same AutoencoderKL on HIP kernels: conv_in, four down blocks of two resnets with a
+    Downsample2D behind the first three, the mid block, conv_norm_out + SiLU, conv_out (512 -> 8) and quant_conv (8 -> 8)."""
+
+    TAPS = ("conv_in", "down0", "down1", "down2", "down3", "mid", "norm_out")  # what encode(taps=...) fills, NHWC
+
+    def __init__(self, state_dict, device=None, module=None):
+        sd = self._open(state_dict, ("encoder.", "quant_conv."), device, module)
+        take = self._take
+        top = BLOCK_CHANNELS[-1]
+        self.q_w, self.q_b = self._take_small_conv("quant_conv", 2 * LATENT_CHANNELS)
+        self.conv_in = take(_Layer, "encoder.conv_in", 3, ops.VAE_CIN_PAD)
+        if (self.conv_in.cin_real, self.conv_in.cout) != (3, BLOCK_CHANNELS[0]):
+            raise ValueError("fresco_amd.vae: encoder.conv_in is not 3 -> %d" % BLOCK_CHANNELS[0])
+        self.down, cin = [], BLOCK_CHANNELS[0]
+        for b, cout in enumerate(BLOCK_CHANNELS):
+            res = [take(_Resnet, "encoder.down_blocks.%d.resnets.%d" % (b, i), cin if i == 0 else cout, cout)
+                   for i in range(LAYERS_PER_BLOCK)]
+            down = None
+            if b < len(BLOCK_CHANNELS) - 1:
+                down = take(_Layer, "encoder.down_blocks.%d.downsamplers.0.conv" % b, 3)
+                if (down.cin, down.cout) != (cout, cout):
+                    raise ValueError("fresco_amd.vae: down block %d's downsampler is not %d -> %d" % (b, cout, cout))
+            elif any(k.startswith("encoder.down_blocks.%d.downsamplers" % b) for k in sd):
+                raise ValueError("fresco_amd.vae: the last down block has a downsampler")
+            self.down.append((res, down))
+            cin = cout
+        self._take_mid("encoder.mid_block", top)
+        self.norm_out = take(_Norm, "encoder.conv_norm_out", top)
+        self.conv_out = take(_Layer, "encoder.conv_out", 3)
+        if (self.conv_out.cin, self.conv_out.cout) != (top, 2 * LATENT_CHANNELS):
+            raise ValueError("fresco_amd.vae: encoder.conv_out is not %d -> %d" % (top, 2 * LATENT_CHANNELS))
+        self._close("encoder")
+
+    @classmethod
+    def from_vae(cls, vae, device=None):
+        """device: where the packed weights go; default: where the module's parameters are (encode needs the GPU)"""
+        return cls(vae.state_dict(), device=device, module=vae)
+
+    @torch.no_grad()
+    def encode(self, x, return_dict=True, taps=None):
+        """x (n, 3, H, W) fp16 on the GPU, H and W >= 8 -> EncoderOutput(latent_dist), or (latent_dist,) with
+        return_dict=False; latent_dist.parameters is (n, 8, H // 8, W // 8) fp16.  taps: a dict that receives the TAPS tensors
+        (NHWC copies)."""
+        self._refuse(x, "x", 3, "H, W")
+        if x.shape[2] < 8 or x.shape[3] < 8:
+            raise ValueError("fresco_amd.vae: x must be at least 8 x 8, got %s" % (tuple(x.shape),))
+        ops._need_gpu(x)
+        keep = (lambda name, t: taps.__setitem__(name, t.clone())) if taps is not None else (lambda name, t: None)
+        n, _, H, W = x.shape
+        x = ops.vaeenc_input(x.contiguous())
+        x = self._conv(x, self.conv_in, n, H, W)
+        keep("conv_in", x)
+        for b, (res, down) in enumerate(self.down):
+            for r in res:
+                x = self._resnet(x, r, n, H, W)
+            if down is not None:
+                x = ops.vaeenc_conv_down(x, down.w, down.b)
+                H, W = H // 2, W // 2
+            keep("down%d" % b, x)
+        x = self._mid(x, n, H, W)
+        keep("mid", x)
+        x = ops.vae_groupnorm(x, self.norm_out.g, self.norm_out.b, EPS, silu=True)
+        keep("norm_out", x)
+        h = self._conv(x, self.conv_out, n, H, W, out_kind=_lib.VAE_OUT_F32)  # fp32: nothing is rounded before quant_conv
+        dist = DiagonalGaussian(ops.vaeenc_moments(h, self.q_w, self.q_b))
+        return EncoderOutput(dist) if return_dict else (dist,)
+
+    __call__ = encode
+
+
 def patch_vae_decode(pipe):
     """rebind pipe.vae.decode to a VAEDecoder built from pipe.vae; returns the decoder.  The module's own method stays on
     its class: unpatch_vae_decode removes the binding."""
@@ -255,3 +413,29 @@ def unpatch_vae_decode(pipe):
     vae = pipe.vae
     if "decode" in vars(vae):
         del vae.decode
+
+
+def patch_vae_encode(pipe):
+    """rebind pipe.vae.encode to a VAEEncoder built from pipe.vae; returns the encoder.  unpatch_vae_encode removes the
+    binding."""
+    vae = pipe.vae
+    unpatch_vae_encode(pipe)
+    enc = VAEEncoder.from_vae(vae)
+    vae.encode = enc.encode
+    return enc
+
+
+def unpatch_vae_encode(pipe):
+    vae = pipe.vae
+    if "encode" in vars(vae):
+        del vae.encode
+
+
+def patch_vae(pipe):
+    """both halves: returns (decoder, encoder)"""
+    return patch_vae_decode(pipe), patch_vae_encode(pipe)
+
+
+def unpatch_vae(pipe):
+    unpatch_vae_decode(pipe)
+    unpatch_vae_encode(pipe)
