@@ -24,6 +24,7 @@ from .canny import CannyDetector, patch_canny
 from .midas import DPTDepthModel, MidasDetector, patch_midas
 from .vae import (VAEDecoder, VAEEncoder, patch_vae, patch_vae_decode, patch_vae_encode, unpatch_vae, unpatch_vae_decode,
                   unpatch_vae_encode)
+from .unet_resnet import UNetResnet, patch_unet_resnets, unpatch_unet_resnets
 from .keyframe import (frame_errors, get_keyframe_ind, patch_keyframe_selection, resize_frames, resize_image, resize_size,
                        select_keyframes)
 from .paras import (correlation_matrices, forward_backward_consistency_check, get_flow_and_interframe_paras,
@@ -43,6 +44,7 @@ __all__ = [
     "MidasDetector", "DPTDepthModel", "patch_midas",
     "VAEDecoder", "patch_vae_decode", "unpatch_vae_decode",
     "VAEEncoder", "patch_vae_encode", "unpatch_vae_encode", "patch_vae", "unpatch_vae",
+    "UNetResnet", "patch_unet_resnets", "unpatch_unet_resnets",
     "get_keyframe_ind", "frame_errors", "select_keyframes", "resize_frames", "resize_image", "resize_size",
     "patch_keyframe_selection",
 ]

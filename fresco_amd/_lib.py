@@ -21,7 +21,7 @@ ERRORS = {
 F16, F32, BF16 = 0, 1, 2
 # what fresco_version() of the library these SIGNATURES describe reports: an older build exports the same names with other
 # argument lists
-VERSION = "0.5.0.2"  # (0.5.0.2: the fresco_egnet_* and fresco_canny_* entry points moved into this library)
+VERSION = "0.5.0.3"  # (0.5.0.2: the fresco_egnet_* and fresco_canny_* entry points moved into this library; 0.5.0.3: unet_*)
 
 
 class FrescoHipError(RuntimeError):
@@ -172,6 +172,14 @@ VAE_ENC_SIGNATURES = {
     "vaeenc_sample": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp]),
 }
 
+# the UNet resnet block's kernels (csrc/unet.hip), declared in include/fresco_unet.h: named unet_*
+UNET_SIGNATURES = {
+    "unet_groupnorm_workspace_bytes": (_sz, [_i, _i, _i]),
+    "unet_groupnorm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _i, _vp]),
+    "unet_groupnorm_lds_form": (_i, [_i, _i, _i]),
+    "unet_temb": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -189,7 +197,7 @@ def load():
     except OSError as e:
         raise FrescoHipError("fresco_amd: cannot load %s: %s" % (LIB_PATH, e))
     for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
-            + list(MIDAS_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(VAE_ENC_SIGNATURES.items()):
+            + list(MIDAS_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(VAE_ENC_SIGNATURES.items()) + list(UNET_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -1772,6 +1772,64 @@ def vae_softmax(scores, Lk, scale, ld_out=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the UNet resnet block's kernels (include/fresco_unet.h): GroupNorm at the UNet's widths with the time embedding folded in
+# ---------------------------------------------------------------------------------------------------------------------
+UNET_GN_MIN, UNET_GN_MAX, UNET_GN_STEP = 64, 2560, 64   # C of unet_groupnorm: the multiples of 64 in this range
+UNET_TEMB_MAX_N = 64
+
+_unet_gn_ws = _PerStreamWorkspace()
+
+
+def unet_gn_channels(C):
+    return UNET_GN_MIN <= C <= UNET_GN_MAX and C % UNET_GN_STEP == 0
+
+
+def unet_groupnorm(x, gamma, beta, eps=1e-5, silu=False, addend=None):
+    """[SiLU] GroupNorm(32, C, eps)(x + addend) on x (n, ..., C) fp16 NHWC, C a multiple of 64 in 64 .. 2560; gamma / beta fp32
+    (C); addend: fp32 (n, C), one term per image and channel, or None -> fp16 like x (unet_groupnorm)"""
+    _dense(x, "unet_groupnorm: x", torch.float16, align=16)
+    if x.dim() < 3 or x.numel() == 0 or not unet_gn_channels(x.shape[-1]):
+        raise ValueError("unet_groupnorm: x must be (n, ..., C), C a multiple of %d in %d .. %d, got %s"
+                         % (UNET_GN_STEP, UNET_GN_MIN, UNET_GN_MAX, tuple(x.shape)))
+    n, C = x.shape[0], x.shape[-1]
+    P = x.numel() // (n * C)
+    _dense(gamma, "unet_groupnorm: gamma", torch.float32, (C,), align=16)
+    _dense(beta, "unet_groupnorm: beta", torch.float32, (C,), align=16)
+    if addend is not None:
+        _dense(addend, "unet_groupnorm: addend", torch.float32, (n, C), align=16)
+    _need_gpu(x, gamma, beta, addend)
+    lib = _lib.load()
+    nbytes = lib.unet_groupnorm_workspace_bytes(n, P, C)
+    ws = _unet_gn_ws.get(nbytes, x.device)
+    y = torch.empty_like(x)
+    rc = lib.unet_groupnorm(x.data_ptr(), _ptr(addend), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), ws.data_ptr(), nbytes,
+                            n, P, C, float(eps), int(bool(silu)), _stream())
+    _lib.check(rc, "unet_groupnorm(n=%d,P=%d,C=%d)" % (n, P, C))
+    return y
+
+
+def unet_temb(temb, weight, bias, conv_bias):
+    """bias + conv_bias + SiLU(temb) W^T: temb fp16 (n, K), n <= 64, weight fp16 (cout, K), bias / conv_bias fp32 (cout) -> fp32
+    (n, cout) (unet_temb)"""
+    _dense(temb, "unet_temb: temb", torch.float16, align=16)
+    if temb.dim() != 2 or temb.numel() == 0:
+        raise ValueError("unet_temb: temb must be (n, K), got %s" % (tuple(temb.shape),))
+    n, K = temb.shape
+    _dense(weight, "unet_temb: weight", torch.float16, align=16)
+    if weight.dim() != 2 or weight.shape[1] != K or weight.shape[0] == 0:
+        raise ValueError("unet_temb: weight must be (cout, %d), got %s" % (K, tuple(weight.shape)))
+    cout = weight.shape[0]
+    _dense(bias, "unet_temb: bias", torch.float32, (cout,))
+    _dense(conv_bias, "unet_temb: conv_bias", torch.float32, (cout,))
+    _need_gpu(temb, weight, bias, conv_bias)
+    out = torch.empty(n, cout, dtype=torch.float32, device=temb.device)
+    rc = _lib.load().unet_temb(temb.data_ptr(), weight.data_ptr(), bias.data_ptr(), conv_bias.data_ptr(), out.data_ptr(), n, K,
+                               cout, _stream())
+    _lib.check(rc, "unet_temb(n=%d,K=%d,cout=%d)" % (n, K, cout))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # what the VAE encoder adds (include/fresco_vae_enc.h)
 # ---------------------------------------------------------------------------------------------------------------------
 def vaeenc_input(image, cpad=VAE_CIN_PAD):
