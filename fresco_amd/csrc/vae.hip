@@ -7,38 +7,30 @@
 //                          GroupNorm(32) [+ SiLU], fp64 statistics
 //   vae_softmax_kernel     fp32 scores -> fp16 probabilities, one workgroup per row
 //
-// vae_conv_kernel: plain fp16 operands, one v_mfma_f32_32x32x16_f16 per product, fp32 accumulators.  A workgroup of four
-// waves owns 128 output pixels x 128 output channels (waves 2 x 2, each 64 x 64 = 2 x 2 MFMA blocks); the WEIGHTS are
-// the MFMA's row operand and the pixels its column operand, so a lane ends up with one pixel and four CONSECUTIVE
-// channels per accumulator quad: the fp16 NHWC result leaves as 8-byte stores, the NCHW image as stores that run along x.
-// The K loop is channel chunks (32) OUTER, taps INNER.  LDS (dynamic, 40 KiB):
+// vae_conv_kernel: conv_tile.h's fp16 implicit-GEMM tile (operands, wave layout, weight ring, XCD deal, epilogue map) with the
+// tile's pixels held as an input WINDOW.  The fp16 NHWC result leaves as 8-byte stores, the NCHW image as stores that run
+// along x.  LDS (dynamic, 40 KiB):
 //   * two slots of 12 KiB for the input WINDOW of the tile, 32 channels deep: 3 x 3: the 10 x 18 pixels around the
 //     8 x 16 tile (180 rows of 64 bytes, fetched ONCE per chunk and read by all nine taps: tap (ky, kx) of tile pixel
-//     (ty, tx) is window row (ty + ky) 18 + tx + kx); 1 x 1: the tile's 128 rows.  Pixels outside the image, rows past
-//     the problem and weight rows >= cout come from a zero page.  up2 changes only the window's source addresses.
-//   * two slots of 8 KiB for the weights of one (chunk, tap) step: 128 rows of 64 bytes.
+//     (ty, tx) is window row (ty + ky) 18 + tx + kx); 1 x 1: the tile's 128 rows.  Pixels outside the image and rows past
+//     the problem come from the zero page.  up2 changes only the window's source addresses.
+//   * conv_tile.h's two weight slots of 8 KiB.
 // Everything arrives by LDS-DMA (lds_dma.h).  Step s: every wave waits for its own copies (all of them: vmcnt(0)), barrier
 // -- step s is in LDS and step s - 1 has been read -- then the weights of step s + 1 and, at a chunk's first tap, the
-// next chunk's window are issued into the other slots and fly under the MFMAs of step s.  A row's four 16-byte pieces
-// sit at piece ^ swizzle(row) (flownet.hip's maps: (R >> 2) & 3 for GEMM rows, (py + 2 (P >> 2)) & 3 for the 18-wide window).
-// Workgroups: the 1-D grid is dealt to the 8 XCDs in turn; XCD x walks a contiguous range of (column tile, pixel tile)
-// with the pixel tile fastest, so one column tile's weights (1.2 MB at K = 4608) stay in that XCD's L2.
+// next chunk's window are issued into the other slots and fly under the MFMAs of step s.  A window row's four 16-byte
+// pieces sit at piece ^ swizzle(row): flownet.hip's (py + 2 (P >> 2)) & 3 for the 18-wide window, the GEMM rows' map at 1 x 1.
 #include "common.h"
 #include "lds_dma.h"
+#include "conv_tile.h"
 #include "groupnorm_stats.h"
 #include "../../include/fresco_vae.h"
 
 namespace fresco {
 
 constexpr int VA_GROUPS = GN_GROUPS;
-constexpr int VC_BM = 128, VC_BN = 128, VC_BK = 32;
-constexpr int VC_TH = 8, VC_TW = 16, VC_WW = VC_TW + 2, VC_NPOS = (VC_TH + 2) * VC_WW;
+constexpr int VC_WW = CT_TW + 2, VC_NPOS = (CT_TH + 2) * VC_WW;
 constexpr int VC_A_BYTES = 12 * 1024;  // 12 pieces of 64 lanes x 16 bytes = 192 window rows of 64 bytes (180 used)
-constexpr int VC_B_BYTES = 8 * 1024;   // 128 weight rows of 64 bytes
-constexpr int VC_LDS = 2 * VC_A_BYTES + 2 * VC_B_BYTES;
-
-// what the LDS-DMA reads where there is nothing to read
-__device__ __attribute__((aligned(16))) unsigned int vae_zero_page[4] = {0u, 0u, 0u, 0u};
+constexpr int VC_LDS = 2 * VC_A_BYTES + 2 * CT_B_BYTES;
 
 struct VaeConv {
     const half_t* x;
@@ -64,26 +56,16 @@ __global__ __launch_bounds__(256) void vae_conv_kernel(const VaeConv a) {
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    int col_tile, img, t_in;
-    {
-        // XCD x = block % 8 owns the logical range [x q + min(x, rem), ..) of q + (x < rem) tiles, T = 8 q + rem
-        const int T = gridDim.x, b = blockIdx.x, x = b & 7, q = T >> 3, rem = T & 7;
-        const int L = x * q + min(x, rem) + (b >> 3);
-        const int PT = a.n * a.tiles_per_img;
-        col_tile = L / PT;
-        const int pt = L - col_tile * PT;
-        img = pt / a.tiles_per_img;
-        t_in = pt - img * a.tiles_per_img;
-    }
-    const int co0 = col_tile * VC_BN;
-    const int ty0 = TAPS == 9 ? (t_in / a.tiles_x) * VC_TH : 0;
-    const int tx0 = TAPS == 9 ? (t_in % a.tiles_x) * VC_TW : 0;
-    const int m0 = t_in * VC_BM;
-    const int K = TAPS * a.cin;
+    const CtTile t = ct_deal(a.n, a.tiles_per_img);
+    const int img = t.img, t_in = t.t_in;
+    const int co0 = t.col_tile * CT_BN;
+    const int ty0 = TAPS == 9 ? (t_in / a.tiles_x) * CT_TH : 0;
+    const int tx0 = TAPS == 9 ? (t_in % a.tiles_x) * CT_TW : 0;
+    const int m0 = t_in * CT_BM;
     const uint32_t lds0 = lds_addr(smem);
-    const char* zp = reinterpret_cast<const char*>(vae_zero_page);
+    const char* zp = reinterpret_cast<const char*>(ct_zero_page);
 
-    // ---- DMA sources: a lane owns LDS piece (slot & 3) of row slot >> 2 and fetches source piece (slot & 3) ^ swizzle(row)
+    // ---- DMA sources: a lane owns LDS piece (slot & 3) of window row slot >> 2 and fetches source piece (slot & 3) ^ swizzle(row)
     const char* a_src[APW];
 #pragma unroll
     for (int p = 0; p < APW; ++p) {
@@ -98,7 +80,7 @@ __global__ __launch_bounds__(256) void vae_conv_kernel(const VaeConv a) {
             ok = P < VC_NPOS && y >= 0 && y < a.H && x >= 0 && x < a.W;
             off = ((int64_t)(y >> a.up2) * a.Ws + (x >> a.up2)) * a.cin;
         } else {
-            ok = P < VC_BM && m0 + P < a.rows;
+            ok = P < CT_BM && m0 + P < a.rows;
             off = (int64_t)(m0 + P) * a.cin;
         }
         a_src[p] = ok ? reinterpret_cast<const char*>(a.x + (int64_t)img * a.x_img_stride + off + pc * 8) : nullptr;
@@ -106,63 +88,46 @@ __global__ __launch_bounds__(256) void vae_conv_kernel(const VaeConv a) {
     const char* b_src[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-        const int slot = (wave * 2 + p) * 64 + lane;
-        const int R = slot >> 2;
-        const int pc = (slot & 3) ^ ((R >> 2) & 3);
-        b_src[p] = co0 + R < a.cout
-                       ? reinterpret_cast<const char*>(a.w + (int64_t)img * a.w_img_stride + (int64_t)(co0 + R) * K + pc * 8)
-                       : nullptr;
+        int R, pc;
+        ct_gemm_slot(wave, p, lane, R, pc);
+        b_src[p] = ct_weight_src(a.w + (int64_t)img * a.w_img_stride, co0, R, pc, a.cout, TAPS * a.cin);
     }
     auto issue_a = [&](int chunk) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < APW; ++p)
-            lds_dma16(a_src[p] ? static_cast<const void*>(a_src[p] + (int64_t)chunk * (VC_BK * 2)) : static_cast<const void*>(zp),
+            lds_dma16(a_src[p] ? static_cast<const void*>(a_src[p] + (int64_t)chunk * (CT_BK * 2)) : static_cast<const void*>(zp),
                       lds0 + (uint32_t)((chunk & 1) * VC_A_BYTES + (wave * APW + p) * 1024));
     };
-    auto issue_b = [&](int s, int k0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-            lds_dma16(b_src[p] ? static_cast<const void*>(b_src[p] + (int64_t)k0 * 2) : static_cast<const void*>(zp),
-                      lds0 + (uint32_t)(2 * VC_A_BYTES + (s & 1) * VC_B_BYTES + (wave * 2 + p) * 1024));
-    };
+    const uint32_t lds_b = lds0 + 2 * VC_A_BYTES;
 
-    // this wave's 32-channel blocks that hold a channel < cout (wave-uniform): the others are skipped, not multiplied
-    int nbv = (a.cout - co0 - wn * 64 + 31) / 32;
-    nbv = nbv < 0 ? 0 : (nbv > 2 ? 2 : nbv);
+    const int nbv = ct_live_blocks(a.cout, co0, wn);
+    floatx16 acc[2][2] = {};  // [channel block j][pixel block i]
 
-    floatx16 acc[2][2];  // [channel block j][pixel block i]
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j][i][r] = 0.f;
-
-    const int chunks = a.cin / VC_BK, steps = chunks * TAPS;
+    const int chunks = a.cin / CT_BK, steps = chunks * TAPS;
     const int wsw = (l31 >> 2) & 3;
     issue_a(0);
-    issue_b(0, 0);
+    ct_issue_weights(b_src, 0, 0, lds_b, wave);
     int chunk = 0, tap = 0;
     for (int s = 0; s < steps; ++s) {
         dma_wait_barrier<0>();
         if (s + 1 < steps) {
             const int t1 = tap + 1 == TAPS ? 0 : tap + 1, c1 = tap + 1 == TAPS ? chunk + 1 : chunk;
-            issue_b(s + 1, t1 * a.cin + c1 * VC_BK);
+            ct_issue_weights(b_src, s + 1, t1 * a.cin + c1 * CT_BK, lds_b, wave);
             if (tap == 0 && chunk + 1 < chunks) issue_a(chunk + 1);
         }
-        const char* pa = smem + (chunk & 1) * VC_A_BYTES;
-        const char* pb = smem + 2 * VC_A_BYTES + (s & 1) * VC_B_BYTES + (wn * 64 + l31) * 64;
         const int ky = tap / 3, kx = tap - ky * 3;
+        const char* pa = smem + (chunk & 1) * VC_A_BYTES;
+        const char* pb = smem + 2 * VC_A_BYTES + (s & 1) * CT_B_BYTES + (wn * 64 + l31) * 64;
         int aoff[2], asw[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int r = wm * 64 + i * 32 + l31;
+            const int r = ct_row(wm, i, l31);
             const int P = TAPS == 9 ? ((r >> 4) + ky) * VC_WW + (r & 15) + kx : r;
             aoff[i] = P * 64;
             asw[i] = vc_swizzle<TAPS>(P);
         }
 #pragma unroll
-        for (int ks = 0; ks < VC_BK / 16; ++ks) {
+        for (int ks = 0; ks < CT_BK / 16; ++ks) {
             const int piece = ks * 2 + hi;
             half8_t px[2], wt[2];
 #pragma unroll
@@ -183,13 +148,12 @@ __global__ __launch_bounds__(256) void vae_conv_kernel(const VaeConv a) {
         }
     }
 
-    // ---- epilogue: lane (l31, hi) holds pixel .. + l31 and, in registers 4 g .. 4 g + 3 of a block, channels
-    // 8 g + 4 hi .. + 3.  Every address and every residual is read before the first store.
+    // ---- epilogue (conv_tile.h's map).  Every address and every residual is read before the first store.
     int64_t opix[2];   // pixel index over all images, -1: outside the problem
     int orow[2];       // the pixel's index inside its image
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int r = wm * 64 + i * 32 + l31;
+        const int r = ct_row(wm, i, l31);
         if (TAPS == 9) {
             const int y = ty0 + (r >> 4), x = tx0 + (r & 15);
             orow[i] = y * a.W + x;
@@ -209,7 +173,7 @@ __global__ __launch_bounds__(256) void vae_conv_kernel(const VaeConv a) {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const int co = co0 + wn * 64 + j * 32 + 8 * g + 4 * hi;
+                    const int co = ct_channel(co0, wn, j, hi, 4 * g);
                     half4_t z4 = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
                     rs[j][i][g] = (a.res && opix[i] >= 0 && co < a.cout)
                                       ? *reinterpret_cast<const half4_t*>(a.res + opix[i] * a.ldo + co)
@@ -219,7 +183,7 @@ __global__ __launch_bounds__(256) void vae_conv_kernel(const VaeConv a) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int co = co0 + wn * 64 + j * 32 + 8 * g + 4 * hi;
+                const int co = ct_channel(co0, wn, j, hi, 4 * g);
                 if (co >= a.cout) continue;
                 floatx4 bv = {0.f, 0.f, 0.f, 0.f};
                 if (a.bias && !a.bias_rows) bv = *reinterpret_cast<const floatx4*>(a.bias + co);
@@ -244,7 +208,7 @@ __global__ __launch_bounds__(256) void vae_conv_kernel(const VaeConv a) {
                 const float br = (a.bias && a.bias_rows) ? a.bias[orow[i]] : 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int co = co0 + wn * 64 + j * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
+                    const int co = ct_channel(co0, wn, j, hi, r);
                     if (co >= a.cout) continue;
                     float v = acc[j][i][r] + ((a.bias && !a.bias_rows) ? a.bias[co] : 0.f) + br;
                     if (a.out_kind == VAE_OUT_F32) {
@@ -280,11 +244,7 @@ __global__ __launch_bounds__(256) void vae_input_kernel(const half_t* __restrict
             for (int c = 0; c < 4; ++c) s += wq[o * 4 + c] * v[c];
             o8[o] = (half_t)s;
         }
-        half_t* row = out + idx * cpad;
-        *reinterpret_cast<half8_t*>(row) = o8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o8[e] = (half_t)0.f;
-        for (int c = 8; c < cpad; c += 8) *reinterpret_cast<half8_t*>(row + c) = o8;
+        ct_store_padded_row(out + idx * cpad, o8, cpad);
     }
 }
 
@@ -366,9 +326,7 @@ extern "C" int vae_conv(const void* x, int64_t x_img_stride, const void* w, int6
     if (!x || !w || !out || n <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return FRESCO_EINVAL;
     if (out_kind != VAE_OUT_F16 && out_kind != VAE_OUT_F32 && out_kind != VAE_OUT_F16_NCHW) return FRESCO_EINVAL;
     if (ksize != 1 && ksize != 3) return FRESCO_EUNSUPPORTED;
-    if (cin % VC_BK) return FRESCO_EUNSUPPORTED;
-    if (up2 && (H % 2 || W % 2)) return FRESCO_EUNSUPPORTED;
-    if (n > 65535 || (int64_t)n * H * W >= (int64_t)1 << 31) return FRESCO_EUNSUPPORTED;
+    if (!ct_supported(n, H, W, cin) || (up2 && (H % 2 || W % 2))) return FRESCO_EUNSUPPORTED;
     up2 = up2 ? 1 : 0;
     bias_rows = bias_rows ? 1 : 0;
     const int Hs = H >> up2, Ws = W >> up2;
@@ -399,19 +357,14 @@ extern "C" int vae_conv(const void* x, int64_t x_img_stride, const void* w, int6
     a.up2 = up2;
     a.out_kind = out_kind;
     a.bias_rows = bias_rows;
-    if (ksize == 3) {
-        a.tiles_x = (W + VC_TW - 1) / VC_TW;
-        a.tiles_per_img = a.tiles_x * ((H + VC_TH - 1) / VC_TH);
-    } else {
-        a.tiles_x = 1;
-        a.tiles_per_img = (int)(((int64_t)a.rows + VC_BM - 1) / VC_BM);
-    }
-    const int64_t grid = (int64_t)n * a.tiles_per_img * ((cout + VC_BN - 1) / VC_BN);
-    if (grid >= (int64_t)1 << 31) return FRESCO_EUNSUPPORTED;
+    a.tiles_x = ksize == 3 ? ct_tiles_x(W) : 1;
+    a.tiles_per_img = ksize == 3 ? ct_plane_tiles(H, W) : (int)(((int64_t)a.rows + CT_BM - 1) / CT_BM);
+    const unsigned grid = ct_grid(n, a.tiles_per_img, cout);
+    if (!grid) return FRESCO_EUNSUPPORTED;
     if (ksize == 3)
-        hipLaunchKernelGGL(vae_conv_kernel<9>, dim3((unsigned)grid), dim3(256), VC_LDS, as_stream(stream), a);
+        hipLaunchKernelGGL(vae_conv_kernel<9>, dim3(grid), dim3(256), VC_LDS, as_stream(stream), a);
     else
-        hipLaunchKernelGGL(vae_conv_kernel<1>, dim3((unsigned)grid), dim3(256), VC_LDS, as_stream(stream), a);
+        hipLaunchKernelGGL(vae_conv_kernel<1>, dim3(grid), dim3(256), VC_LDS, as_stream(stream), a);
     return check_launch();
 }
 

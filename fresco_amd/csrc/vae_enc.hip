@@ -6,37 +6,29 @@
 //   vaeenc_moments_kernel    conv_out's fp32 rows -> quant_conv (8 -> 8, fp32) -> parameters NCHW fp16
 //   vaeenc_sample_kernel     scale (mean + exp(0.5 clamp(logvar, -30, 20)) noise), fp32, one rounding
 //
-// vaeenc_conv_down_kernel has vae_conv_kernel's arithmetic and tiling: plain fp16 operands, one v_mfma_f32_32x32x16_f16 per
-// product, fp32 accumulators; four waves own 8 x 16 output pixels x 128 output channels (waves 2 x 2, each 64 x 64 = 2 x 2
-// MFMA blocks), the weights are the MFMA's row operand, K is channel chunks (32) outer, the nine taps inner.  What differs
-// is how the pixels arrive.  At stride 2 the tile's taps share little: its 17 x 33 source window (561 rows of 64 bytes,
+// vaeenc_conv_down_kernel is conv_tile.h's fp16 implicit-GEMM tile (operands, wave layout, weight ring, XCD deal, epilogue
+// map) on 8 x 16 output pixels, the nine taps inner.  What differs from vae_conv_kernel (vae.hip) is how the pixels
+// arrive.  At stride 2 the tile's taps share little: its 17 x 33 source window (561 rows of 64 bytes,
 // 35 KiB per slot) holds each source pixel for 2.25 taps on average where the stride-1 window holds it for 7.1, and two
 // such slots beside the weights leave one workgroup per CU and need allow_dyn_lds.  So there is NO window: every (chunk,
 // tap) step gathers its own 128 pixel rows, source pixel (2 yo + ky, 2 xo + kx), exactly as the 1 x 1 form of vae_conv
 // gathers its rows -- 2.05 x the window's bytes, read from L2, for a third of its LDS.  LDS (dynamic, 32 KiB):
-//   * two slots of 8 KiB for the pixels of one step: 128 rows of 64 bytes in tile order (row r = pixel (r >> 4, r & 15));
-//   * two slots of 8 KiB for the weights of one step: 128 rows of 64 bytes.
-// Five workgroups fit a CU's 160 KiB by LDS; the register file (144 of 512 per lane) keeps three.  Everything arrives by LDS-DMA (lds_dma.h).  Step
-// s: every wave waits for its own copies (vmcnt(0)), barrier -- step s is in LDS and step s - 1 has been read -- then the
-// pixels and weights of step s + 1 are issued into the other slots and fly under the MFMAs of step s.  A row's four
-// 16-byte pieces sit at piece ^ ((row >> 2) & 3) (flownet.hip's map for GEMM rows).  Source rows y = H and columns x = W
-// (the pad), output pixels past the plane and weight rows >= cout come from a zero page: a select, not a branch.
-// Workgroups are dealt to the 8 XCDs as in vae_conv: XCD x walks a contiguous range of (column tile, pixel tile), the
-// pixel tile fastest.  No split-K, no atomics: same inputs, same bits.
+//   * two slots of 8 KiB for the pixels of one step: 128 rows of 64 bytes in tile order (row r = pixel (r >> 4, r & 15)),
+//     swizzled as GEMM rows;
+//   * conv_tile.h's two weight slots of 8 KiB.
+// Five workgroups fit a CU's 160 KiB by LDS; the register file (144 of 512 per lane) keeps three.  Everything arrives by
+// LDS-DMA (lds_dma.h).  Step s: every wave waits for its own copies (vmcnt(0)), barrier -- step s is in LDS and step s - 1
+// has been read -- then the pixels and weights of step s + 1 are issued into the other slots and fly under the MFMAs of
+// step s.  Source rows y = H and columns x = W (the pad) and output pixels past the plane come from the zero page.
 #include "common.h"
 #include "lds_dma.h"
+#include "conv_tile.h"
 #include "../../include/fresco_vae_enc.h"
 
 namespace fresco {
 
-constexpr int VD_BN = 128, VD_BK = 32;
-constexpr int VD_TH = 8, VD_TW = 16;  // 128 output pixels
 constexpr int VD_A_BYTES = 8 * 1024;  // 128 pixel rows of 64 bytes
-constexpr int VD_B_BYTES = 8 * 1024;  // 128 weight rows of 64 bytes
-constexpr int VD_LDS = 2 * VD_A_BYTES + 2 * VD_B_BYTES;
-
-// what the LDS-DMA reads where there is nothing to read
-__device__ __attribute__((aligned(16))) unsigned int vaeenc_zero_page[4] = {0u, 0u, 0u, 0u};
+constexpr int VD_LDS = 2 * VD_A_BYTES + 2 * CT_B_BYTES;
 
 struct VaeDown {
     const half_t* x;
@@ -52,24 +44,13 @@ __global__ __launch_bounds__(256) void vaeenc_conv_down_kernel(const VaeDown a) 
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    int col_tile, img, t_in;
-    {
-        // XCD x = block % 8 owns the logical range [x q + min(x, rem), ..) of q + (x < rem) tiles, T = 8 q + rem
-        const int T = gridDim.x, b = blockIdx.x, x = b & 7, q = T >> 3, rem = T & 7;
-        const int L = x * q + min(x, rem) + (b >> 3);
-        const int PT = a.n * a.tiles_per_img;
-        col_tile = L / PT;
-        const int pt = L - col_tile * PT;
-        img = pt / a.tiles_per_img;
-        t_in = pt - img * a.tiles_per_img;
-    }
-    const int co0 = col_tile * VD_BN;
-    const int ty0 = (t_in / a.tiles_x) * VD_TH, tx0 = (t_in % a.tiles_x) * VD_TW;
-    const int K = 9 * a.cin;
+    const CtTile t = ct_deal(a.n, a.tiles_per_img);
+    const int img = t.img, co0 = t.col_tile * CT_BN;
+    const int ty0 = (t.t_in / a.tiles_x) * CT_TH, tx0 = (t.t_in % a.tiles_x) * CT_TW;
     const uint32_t lds0 = lds_addr(smem);
-    const char* zp = reinterpret_cast<const char*>(vaeenc_zero_page);
+    const char* zp = reinterpret_cast<const char*>(ct_zero_page);
 
-    // ---- DMA sources: a lane owns LDS piece (slot & 3) of row slot >> 2 and fetches source piece (slot & 3) ^ swizzle(row).
+    // ---- DMA sources, pixel rows laid out as the weight rows are (ct_gemm_slot).
     // a_src: tap (0, 0) of the row's output pixel, chunk 0 (always inside the image where the pixel is); a_ok: bit t set
     // where tap t of that pixel is inside the image.  Only taps with ky = 2 or kx = 2 can reach the pad.
     const char* a_src[2];
@@ -77,15 +58,14 @@ __global__ __launch_bounds__(256) void vaeenc_conv_down_kernel(const VaeDown a) 
     const char* b_src[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-        const int slot = (wave * 2 + p) * 64 + lane;
-        const int R = slot >> 2;
-        const int pc = (slot & 3) ^ ((R >> 2) & 3);
+        int R, pc;
+        ct_gemm_slot(wave, p, lane, R, pc);
         const int yo = ty0 + (R >> 4), xo = tx0 + (R & 15);
         const bool ok = yo < a.Ho && xo < a.Wo;
         const int rows_ok = 2 * yo + 2 < a.H ? 0x1FF : 0x03F, cols_ok = 2 * xo + 2 < a.W ? 0x1FF : 0x0DB;
         a_ok[p] = ok ? (rows_ok & cols_ok) : 0;
         a_src[p] = reinterpret_cast<const char*>(a.x + (((int64_t)img * a.H + 2 * yo) * a.W + 2 * xo) * a.cin + pc * 8);
-        b_src[p] = co0 + R < a.cout ? reinterpret_cast<const char*>(a.w + (int64_t)(co0 + R) * K + pc * 8) : nullptr;
+        b_src[p] = ct_weight_src(a.w, co0, R, pc, a.cout, 9 * a.cin);
     }
     // step (chunk, tap): pixels at a_off bytes from the lane's tap-(0, 0) address, weights at column k0
     auto issue = [&](int s, int tap, int64_t a_off, int k0) __attribute__((always_inline)) {
@@ -93,25 +73,13 @@ __global__ __launch_bounds__(256) void vaeenc_conv_down_kernel(const VaeDown a) 
         for (int p = 0; p < 2; ++p)
             lds_dma16((a_ok[p] >> tap) & 1 ? static_cast<const void*>(a_src[p] + a_off) : static_cast<const void*>(zp),
                       lds0 + (uint32_t)((s & 1) * VD_A_BYTES + (wave * 2 + p) * 1024));
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-            lds_dma16(b_src[p] ? static_cast<const void*>(b_src[p] + (int64_t)k0 * 2) : static_cast<const void*>(zp),
-                      lds0 + (uint32_t)(2 * VD_A_BYTES + (s & 1) * VD_B_BYTES + (wave * 2 + p) * 1024));
+        ct_issue_weights(b_src, s, k0, lds0 + 2 * VD_A_BYTES, wave);
     };
 
-    // this wave's 32-channel blocks that hold a channel < cout (wave-uniform): the others are skipped, not multiplied
-    int nbv = (a.cout - co0 - wn * 64 + 31) / 32;
-    nbv = nbv < 0 ? 0 : (nbv > 2 ? 2 : nbv);
+    const int nbv = ct_live_blocks(a.cout, co0, wn);
+    floatx16 acc[2][2] = {};  // [channel block j][pixel block i]
 
-    floatx16 acc[2][2];  // [channel block j][pixel block i]
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[j][i][r] = 0.f;
-
-    const int chunks = a.cin / VD_BK, steps = chunks * 9;
+    const int chunks = a.cin / CT_BK, steps = chunks * 9;
     const int sw = (l31 >> 2) & 3;  // rows wm 64 + i 32 + l31 and wn 64 + j 32 + l31 share it
     issue(0, 0, 0, 0);
     int chunk = 0, tap = 0;
@@ -120,12 +88,12 @@ __global__ __launch_bounds__(256) void vaeenc_conv_down_kernel(const VaeDown a) 
         if (s + 1 < steps) {
             const int t1 = tap + 1 == 9 ? 0 : tap + 1, c1 = tap + 1 == 9 ? chunk + 1 : chunk;
             const int ky = t1 / 3, kx = t1 - ky * 3;
-            issue(s + 1, t1, (((int64_t)ky * a.W + kx) * a.cin + c1 * VD_BK) * 2, t1 * a.cin + c1 * VD_BK);
+            issue(s + 1, t1, (((int64_t)ky * a.W + kx) * a.cin + c1 * CT_BK) * 2, t1 * a.cin + c1 * CT_BK);
         }
         const char* pa = smem + (s & 1) * VD_A_BYTES + (wm * 64 + l31) * 64;
-        const char* pb = smem + 2 * VD_A_BYTES + (s & 1) * VD_B_BYTES + (wn * 64 + l31) * 64;
+        const char* pb = smem + 2 * VD_A_BYTES + (s & 1) * CT_B_BYTES + (wn * 64 + l31) * 64;
 #pragma unroll
-        for (int ks = 0; ks < VD_BK / 16; ++ks) {
+        for (int ks = 0; ks < CT_BK / 16; ++ks) {
             const int piece = ((ks * 2 + hi) ^ sw) * 16;
             half8_t px[2], wt[2];
 #pragma unroll
@@ -146,12 +114,11 @@ __global__ __launch_bounds__(256) void vaeenc_conv_down_kernel(const VaeDown a) 
         }
     }
 
-    // ---- epilogue: lane (l31, hi) holds pixel .. + l31 and, in registers 4 g .. 4 g + 3 of a block, channels
-    // 8 g + 4 hi .. + 3.  Every address is computed before the first store.
+    // ---- epilogue (conv_tile.h's map).  Every address is computed before the first store.
     int64_t opix[2];  // pixel index over all images, -1: outside the plane
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int r = wm * 64 + i * 32 + l31;
+        const int r = ct_row(wm, i, l31);
         const int yo = ty0 + (r >> 4), xo = tx0 + (r & 15);
         opix[i] = (yo < a.Ho && xo < a.Wo) ? ((int64_t)img * a.Ho + yo) * a.Wo + xo : -1;
     }
@@ -160,7 +127,7 @@ __global__ __launch_bounds__(256) void vaeenc_conv_down_kernel(const VaeDown a) 
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int co = co0 + wn * 64 + j * 32 + 8 * g + 4 * hi;
+                const int co = ct_channel(co0, wn, j, hi, 4 * g);
                 if (co >= a.cout) continue;
                 const floatx4 bv = *reinterpret_cast<const floatx4*>(a.bias + co);
 #pragma unroll
@@ -181,7 +148,7 @@ __global__ __launch_bounds__(256) void vaeenc_conv_down_kernel(const VaeDown a) 
                 if (opix[i] < 0) continue;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int co = co0 + wn * 64 + j * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
+                    const int co = ct_channel(co0, wn, j, hi, r);
                     if (co < a.cout) a.out[opix[i] * a.cout + co] = (half_t)(acc[j][i][r] + a.bias[co]);
                 }
             }
@@ -199,11 +166,7 @@ __global__ __launch_bounds__(256) void vaeenc_input_kernel(const half_t* __restr
         for (int e = 0; e < 8; ++e) o8[e] = (half_t)0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) o8[c] = img[(i * 3 + c) * hw + p];
-        half_t* row = out + idx * cpad;
-        *reinterpret_cast<half8_t*>(row) = o8;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o8[c] = (half_t)0.f;
-        for (int c = 8; c < cpad; c += 8) *reinterpret_cast<half8_t*>(row + c) = o8;
+        ct_store_padded_row(out + idx * cpad, o8, cpad);
     }
 }
 
@@ -256,8 +219,7 @@ extern "C" int vaeenc_conv_down(const void* x, const void* w, const float* bias,
                                 int cout, void* stream) {
     if (!x || !w || !bias || !out || n <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return FRESCO_EINVAL;
     if (!aligned_to(x, 16) || !aligned_to(w, 16) || !aligned_to(bias, 16) || !aligned_to(out, 8)) return FRESCO_EINVAL;
-    if (H < 2 || W < 2 || cin % VD_BK) return FRESCO_EUNSUPPORTED;
-    if (n > 65535 || (int64_t)n * H * W >= (int64_t)1 << 31) return FRESCO_EUNSUPPORTED;
+    if (H < 2 || W < 2 || !ct_supported(n, H, W, cin)) return FRESCO_EUNSUPPORTED;
     VaeDown a;
     a.x = static_cast<const half_t*>(x);
     a.w = static_cast<const half_t*>(w);
@@ -270,11 +232,11 @@ extern "C" int vaeenc_conv_down(const void* x, const void* w, const float* bias,
     a.Wo = W / 2;
     a.cin = cin;
     a.cout = cout;
-    a.tiles_x = (a.Wo + VD_TW - 1) / VD_TW;
-    a.tiles_per_img = a.tiles_x * ((a.Ho + VD_TH - 1) / VD_TH);
-    const int64_t grid = (int64_t)n * a.tiles_per_img * ((cout + VD_BN - 1) / VD_BN);
-    if (grid >= (int64_t)1 << 31) return FRESCO_EUNSUPPORTED;
-    hipLaunchKernelGGL(vaeenc_conv_down_kernel, dim3((unsigned)grid), dim3(256), VD_LDS, as_stream(stream), a);
+    a.tiles_x = ct_tiles_x(a.Wo);
+    a.tiles_per_img = ct_plane_tiles(a.Ho, a.Wo);
+    const unsigned grid = ct_grid(n, a.tiles_per_img, cout);
+    if (!grid) return FRESCO_EUNSUPPORTED;
+    hipLaunchKernelGGL(vaeenc_conv_down_kernel, dim3(grid), dim3(256), VD_LDS, as_stream(stream), a);
     return check_launch();
 }
 

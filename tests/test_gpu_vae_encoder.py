@@ -56,6 +56,9 @@ DOWN_SHAPES = {
     "even_sides_ragged_tiles": (1, 18, 34, 256, 256),         # both are read; several channel chunks
     "one_pixel_per_image": (3, 2, 2, 128, 128),
     "ragged_cout": (1, 20, 36, 128, 40),
+    # cout & 3 != 0: the one-element-per-store epilogue; one chunk, nine steps; cout below one MFMA block, so one wave column
+    # multiplies one block and the other none; 3 x 5 pixels inside one tile, pad row and column both read
+    "scalar_store_cout": (1, 6, 10, 32, 6),
 }
 
 

@@ -59,9 +59,10 @@ def test_lds_is_what_the_comments_say(listing):
     assert lds("gn_stats_kernel") == [2 * 512 * 8]          # two fp64 arrays of one entry per half quad
     assert lds("vae_softmax_kernel") == [4 * 4] and lds("vae_gn_apply_kernel") == [0] and lds("vae_input_kernel") == [0]
     src = open(os.path.join(CSRC, "vae.hip")).read()
-    consts = dict(re.findall(r"constexpr int (VC_[AB]_BYTES) = (\d+) \* 1024;", src))
-    dyn = 2 * int(consts["VC_A_BYTES"]) * 1024 + 2 * int(consts["VC_B_BYTES"]) * 1024
-    assert "constexpr int VC_LDS = 2 * VC_A_BYTES + 2 * VC_B_BYTES;" in src and "LDS (dynamic, 40 KiB)" in src
+    tile = open(os.path.join(CSRC, "conv_tile.h")).read()  # the weight slots are the shared tile's
+    consts = dict(re.findall(r"constexpr int (VC_A_BYTES|CT_B_BYTES) = (\d+) \* 1024;", src + tile))
+    dyn = 2 * int(consts["VC_A_BYTES"]) * 1024 + 2 * int(consts["CT_B_BYTES"]) * 1024
+    assert "constexpr int VC_LDS = 2 * VC_A_BYTES + 2 * CT_B_BYTES;" in src and "LDS (dynamic, 40 KiB)" in src
     assert dyn == 40 * 1024 and dyn <= LDS_LIMIT
     assert src.count("VC_LDS, as_stream(stream)") == 2 and "allow_dyn_lds(" not in src
 

@@ -52,9 +52,10 @@ def test_lds_is_what_the_comment_says(listing):
     _, kernels = listing
     assert [r["lds"] for r in kernels.values()] == [0, 0, 0, 0]  # no static LDS anywhere; the convolution's is dynamic
     src = open(os.path.join(CSRC, "vae_enc.hip")).read()
-    consts = dict(re.findall(r"constexpr int (VD_[AB]_BYTES) = (\d+) \* 1024;", src))
-    dyn = 2 * int(consts["VD_A_BYTES"]) * 1024 + 2 * int(consts["VD_B_BYTES"]) * 1024
-    assert "constexpr int VD_LDS = 2 * VD_A_BYTES + 2 * VD_B_BYTES;" in src and "LDS (dynamic, 32 KiB)" in src
+    tile = open(os.path.join(CSRC, "conv_tile.h")).read()  # the weight slots are the shared tile's
+    consts = dict(re.findall(r"constexpr int (VD_A_BYTES|CT_B_BYTES) = (\d+) \* 1024;", src + tile))
+    dyn = 2 * int(consts["VD_A_BYTES"]) * 1024 + 2 * int(consts["CT_B_BYTES"]) * 1024
+    assert "constexpr int VD_LDS = 2 * VD_A_BYTES + 2 * CT_B_BYTES;" in src and "LDS (dynamic, 32 KiB)" in src
     assert dyn == 32 * 1024 and dyn <= LDS_LIMIT
     launches = re.findall(r"hipLaunchKernelGGL\((\w+), [^;]*?dim3\(256\), (\w+), as_stream", src)
     assert sorted(launches) == sorted([("vaeenc_conv_down_kernel", "VD_LDS"), ("vaeenc_input_kernel", "0"),
