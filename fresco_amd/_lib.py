@@ -21,7 +21,8 @@ ERRORS = {
 F16, F32, BF16 = 0, 1, 2
 # what fresco_version() of the library these SIGNATURES describe reports: an older build exports the same names with other
 # argument lists
-VERSION = "0.5.0.3"  # (0.5.0.2: the fresco_egnet_* and fresco_canny_* entry points moved into this library; 0.5.0.3: unet_*)
+VERSION = "0.5.0.4"  # (0.5.0.2: the fresco_egnet_* and fresco_canny_* entry points moved into this library; 0.5.0.3: unet_*;
+# 0.5.0.4: unet_layernorm and unet_geglu)
 
 
 class FrescoHipError(RuntimeError):
@@ -180,6 +181,12 @@ UNET_SIGNATURES = {
     "unet_temb": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
+# what the UNet transformer blocks add to them (csrc/unet_tf.hip), declared in include/fresco_unet_tf.h: named unet_* too
+UNET_TF_SIGNATURES = {
+    "unet_layernorm": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i, _f, _vp]),
+    "unet_geglu": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i64, _vp]),
+}
+
 _lib = None
 
 
@@ -197,7 +204,8 @@ def load():
     except OSError as e:
         raise FrescoHipError("fresco_amd: cannot load %s: %s" % (LIB_PATH, e))
     for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
-            + list(MIDAS_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(VAE_ENC_SIGNATURES.items()) + list(UNET_SIGNATURES.items()):
+            + list(MIDAS_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(VAE_ENC_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) \
+            + list(UNET_TF_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

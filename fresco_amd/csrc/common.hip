@@ -119,5 +119,5 @@ extern "C" int fresco_prof_read(int max_records, int* tags, int* dims, float* ms
     return n;
 }
 
-extern "C" const char* fresco_version(void) { return "fresco_hip 0.5.0.3 gfx950"; }
+extern "C" const char* fresco_version(void) { return "fresco_hip 0.5.0.4 gfx950"; }
 extern "C" const char* fresco_last_error(void) { return fresco::g_last_error; }

@@ -1830,6 +1830,91 @@ def unet_temb(temb, weight, bias, conv_bias):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# what the UNet transformer blocks add (include/fresco_unet_tf.h): LayerNorm with the residual add, the fused GEGLU
+# ---------------------------------------------------------------------------------------------------------------------
+UNET_LN_MIN, UNET_LN_MAX, UNET_LN_STEP = 64, 2560, 8   # C of unet_layernorm: the multiples of 8 in this range
+UNET_GEGLU_STEP = 32                                   # K and inner of unet_geglu
+
+
+def unet_ln_channels(C):
+    return UNET_LN_MIN <= C <= UNET_LN_MAX and C % UNET_LN_STEP == 0
+
+
+def _strided_rows(t, name, C):
+    """(row stride, rows) of a fp16 (..., C) tensor whose rows are C dense values a fixed number of elements apart: a dense
+    tensor, or a column slice of one; 16-byte aligned rows"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: expected a tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != torch.float16:
+        raise TypeError("%s: dtype %s, expected %s" % (name, t.dtype, torch.float16))
+    if t.dim() < 2 or t.shape[-1] != C or t.numel() == 0:
+        raise ValueError("%s: shape %s, expected (..., %d)" % (name, tuple(t.shape), C))
+    rows = t.numel() // C
+    if t.is_contiguous():
+        ld = C
+    elif t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= C:
+        ld = t.stride(0)
+    else:
+        raise ValueError("%s: rows must be dense and uniformly strided (a dense tensor or a 2-D column slice)" % name)
+    if ld % 8 or t.data_ptr() % 16:
+        raise ValueError("%s: rows must be 16-byte aligned" % name)
+    return ld, rows
+
+
+def unet_layernorm(x, gamma, beta, eps=1e-5, residual=None, want_sum=False):
+    """LayerNorm(C, eps)(x [+ residual]) * gamma + beta on fp16 rows (..., C), C a multiple of 8 in 64 .. 2560; gamma / beta fp32
+    (C).  x and residual may be 2-D column slices (a row stride above C).  -> y fp16, dense, shaped like x; with want_sum,
+    (y, x + residual rounded once to fp16) (unet_layernorm)"""
+    if not isinstance(x, torch.Tensor) or x.dim() < 2 or not unet_ln_channels(x.shape[-1]):
+        raise ValueError("unet_layernorm: x must be (..., C), C a multiple of %d in %d .. %d, got %s"
+                         % (UNET_LN_STEP, UNET_LN_MIN, UNET_LN_MAX, tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)))
+    C = x.shape[-1]
+    ldx, rows = _strided_rows(x, "unet_layernorm: x", C)
+    ldr = 0
+    if residual is not None:
+        ldr, rrows = _strided_rows(residual, "unet_layernorm: residual", C)
+        if rrows != rows:
+            raise ValueError("unet_layernorm: residual of %d rows, x of %d" % (rrows, rows))
+    _dense(gamma, "unet_layernorm: gamma", torch.float32, (C,), align=16)
+    _dense(beta, "unet_layernorm: beta", torch.float32, (C,), align=16)
+    _need_gpu(x, residual, gamma, beta)
+    y = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+    total = torch.empty(x.shape, dtype=torch.float16, device=x.device) if want_sum else None
+    rc = _lib.load().unet_layernorm(x.data_ptr(), ldx, _ptr(residual), ldr, gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), C,
+                                    _ptr(total), C, rows, C, float(eps), _stream())
+    _lib.check(rc, "unet_layernorm(rows=%d,C=%d)" % (rows, C))
+    return (y, total) if want_sum else y
+
+
+def unet_geglu(x, w, bias, out=None):
+    """(x Wv^T + bv) * gelu(x Wg^T + bg), the exact GELU: x fp16 (..., K) dense, w fp16 (2 inner, K) and bias fp32 (2 inner) in
+    pack_geglu_weight's order, K % 32 == 0 and inner % 32 == 0 -> fp16 (..., inner), or into `out`, a 2-D (M, inner) tensor
+    that may be a column slice (unet_geglu)"""
+    _dense(x, "unet_geglu: x", torch.float16, align=16)
+    _dense(w, "unet_geglu: w", torch.float16, align=16)
+    if x.dim() < 2 or x.numel() == 0 or w.dim() != 2 or w.shape[1] != x.shape[-1] or w.shape[0] == 0 or w.shape[0] % 2:
+        raise ValueError("unet_geglu: x (..., K) and w (2 inner, K), got %s and %s" % (tuple(x.shape), tuple(w.shape)))
+    K, inner = x.shape[-1], w.shape[0] // 2
+    if K % UNET_GEGLU_STEP or inner % UNET_GEGLU_STEP:
+        raise ValueError("unet_geglu: K = %d and inner = %d must be multiples of %d" % (K, inner, UNET_GEGLU_STEP))
+    M = x.numel() // K
+    _dense(bias, "unet_geglu: bias", torch.float32, (2 * inner,), align=16)
+    if out is None:
+        out = torch.empty(x.shape[:-1] + (inner,), dtype=torch.float16, device=x.device)
+        ldo = inner
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float16 or out.dim() != 2 or tuple(out.shape) != (M, inner):
+            raise ValueError("unet_geglu: out must be a fp16 (%d, %d) tensor" % (M, inner))
+        ldo = inner if M == 1 else out.stride(0)
+        if out.stride(1) != 1 or ldo < inner or ldo % 4 or out.data_ptr() % 8:
+            raise ValueError("unet_geglu: out rows must be dense, 8-byte aligned and a multiple of 4 elements apart")
+    _need_gpu(x, w, bias, out)
+    rc = _lib.load().unet_geglu(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), M, K, inner, ldo, _stream())
+    _lib.check(rc, "unet_geglu(M=%d,K=%d,inner=%d)" % (M, K, inner))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # what the VAE encoder adds (include/fresco_vae_enc.h)
 # ---------------------------------------------------------------------------------------------------------------------
 def vaeenc_input(image, cpad=VAE_CIN_PAD):
