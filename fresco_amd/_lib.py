@@ -187,6 +187,12 @@ UNET_TF_SIGNATURES = {
     "unet_geglu": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i64, _vp]),
 }
 
+# flash attention at head dim 160 for the plain attention processor (csrc/unet_attn.hip), declared in
+# include/fresco_unet_attn.h: named unet_* too
+UNET_ATTN_SIGNATURES = {
+    "unet_attention": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _f, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -205,7 +211,7 @@ def load():
         raise FrescoHipError("fresco_amd: cannot load %s: %s" % (LIB_PATH, e))
     for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
             + list(MIDAS_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(VAE_ENC_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) \
-            + list(UNET_TF_SIGNATURES.items()):
+            + list(UNET_TF_SIGNATURES.items()) + list(UNET_ATTN_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -1915,6 +1915,63 @@ def unet_geglu(x, w, bias, out=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# flash attention at head dim 160 (include/fresco_unet_attn.h): the 1280-wide layers of the UNet and the ControlNet
+# ---------------------------------------------------------------------------------------------------------------------
+UNET_ATTN_HEAD_DIM = 160
+
+
+def _batched_rows(t, name, C):
+    """row stride of a fp16 (B, L, C) tensor whose row b L + i starts (b L + i) ld elements after its first: a dense tensor,
+    or a column slice of a dense (B, L, k C) one; nothing is copied, anything else raises"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: expected a tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != torch.float16:
+        raise TypeError("%s: dtype %s, expected %s (bf16 is not built)" % (name, t.dtype, torch.float16))
+    if t.dim() != 3 or t.shape[-1] != C or t.numel() == 0:
+        raise ValueError("%s: shape %s, expected (B, L, %d)" % (name, tuple(t.shape), C))
+    B, L, _ = t.shape
+    ld = t.stride(1) if L > 1 else (t.stride(0) if B > 1 else C)
+    if t.stride(2) != 1 or (B > 1 and t.stride(0) != L * ld):
+        raise ValueError("%s: rows must be dense and uniformly strided (a dense tensor or a column slice of one)" % name)
+    if ld < C or ld % 8 or t.data_ptr() % 16:
+        raise ValueError("%s: rows must be 16-byte aligned, a multiple of 8 elements and at least %d apart" % (name, C))
+    return ld
+
+
+def unet_attention(q, k, v, heads, scale, out=None):
+    """softmax(scale q k^T) v per (batch, head) at head dim 160: q (B, Lq, heads * 160), k and v (B, Lk, heads * 160), fp16;
+    each may be a column slice of a wider buffer (q | k | v of a fused projection), k and v with one row stride.  Any Lq and
+    Lk.  -> `out`, or a new dense (B, Lq, heads * 160) fp16 tensor (unet_attention).  Nothing is copied or made dense: what
+    the kernel would refuse raises here."""
+    if not isinstance(q, torch.Tensor) or q.dim() != 3:
+        raise ValueError("unet_attention: q must be (B, Lq, C), got %s" % (tuple(q.shape) if isinstance(q, torch.Tensor) else type(q),))
+    heads = int(heads)
+    B, Lq, C = q.shape
+    if heads <= 0 or C != heads * UNET_ATTN_HEAD_DIM:
+        raise NotImplementedError("unet_attention: head dim %s (%d channels on %d heads), only %d is built"
+                                  % (C // heads if heads > 0 and C % heads == 0 else "?", C, heads, UNET_ATTN_HEAD_DIM))
+    if not (float(scale) > 0 and math.isfinite(float(scale))):
+        raise ValueError("unet_attention: scale %r must be positive and finite" % (scale,))
+    q_ld = _batched_rows(q, "unet_attention: q", C)
+    kv_ld = _batched_rows(k, "unet_attention: k", C)
+    v_ld = _batched_rows(v, "unet_attention: v", C)
+    if k.shape != v.shape or k.shape[0] != B or v_ld != kv_ld:
+        raise ValueError("unet_attention: k %s and v %s must be (%d, Lk, %d) with one row stride (got %d and %d)"
+                         % (tuple(k.shape), tuple(v.shape), B, C, kv_ld, v_ld))
+    Lk = k.shape[1]
+    if out is None:
+        out = torch.empty(B, Lq, C, dtype=torch.float16, device=q.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, Lq, C):
+        raise ValueError("unet_attention: out must be a fp16 (%d, %d, %d) tensor" % (B, Lq, C))
+    out_ld = _batched_rows(out, "unet_attention: out", C)
+    _need_gpu(q, k, v, out)
+    rc = _lib.load().unet_attention(q.data_ptr(), q_ld, k.data_ptr(), v.data_ptr(), kv_ld, out.data_ptr(), out_ld, B, heads, Lq,
+                                    Lk, UNET_ATTN_HEAD_DIM, float(scale), _lib.F16, _stream())
+    _lib.check(rc, "unet_attention(B=%d,H=%d,Lq=%d,Lk=%d)" % (B, heads, Lq, Lk))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # what the VAE encoder adds (include/fresco_vae_enc.h)
 # ---------------------------------------------------------------------------------------------------------------------
 def vaeenc_input(image, cpad=VAE_CIN_PAD):
