@@ -22,6 +22,7 @@ import torch
 import torch.nn.functional as F
 
 import vae_model as M
+from conv_ref import check as _check, conv_ref as _conv_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -35,34 +36,9 @@ def _randn(*shape, seed=0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
 
-def _check(name, got, ref, bound):
-    got, ref, bound = (t.detach().to("cpu", torch.float64).numpy() if isinstance(t, torch.Tensor) else np.asarray(t, np.float64)
-                       for t in (got, ref, bound))
-    assert got.shape == ref.shape, (name, got.shape, ref.shape)
-    err = np.abs(got - ref)
-    print("%s: worst error / bound %.3f" % (name, float((err / bound).max())))
-    assert np.isfinite(got).all() and np.all(err <= bound), name
-
-
 # ---------------------------------------------------------------------------------------------------------------
 # vae_conv
 # ---------------------------------------------------------------------------------------------------------------
-def _conv_ref(x, w, up2):
-    """x (n, Hs, Ws, cin) fp16, w (cout, cin, k, k) fp16 on the GPU -> (float64 result, sum |x| |w|), both (n, H, W, cout):
-    im2col (F.unfold) and one float64 product"""
-    x64 = x.double().permute(0, 3, 1, 2)
-    if up2:
-        x64 = x64.repeat_interleave(2, 2).repeat_interleave(2, 3)
-    n, _, H, W = x64.shape
-    k = w.shape[2]
-    w64 = w.double().reshape(w.shape[0], -1)
-    outs = []
-    for xx, ww in ((x64, w64), (x64.abs(), w64.abs())):
-        cols = F.unfold(xx, k, padding=k // 2) if k == 3 else xx.reshape(n, -1, H * W)
-        outs.append((ww @ cols).transpose(1, 2).reshape(n, H, W, -1))
-    return outs
-
-
 CONV_SHAPES = {
     # name: (n, Hs, Ws, cin, cout, ksize, up2)
     "ragged_tile_two_images": (2, 10, 14, 128, 128, 3, False),
