@@ -1730,6 +1730,16 @@ def vae_conv(x, w, bias, n, H, W, cin, cout, ksize, up2=False, residual=None, ou
     return out
 
 
+def conv_rows(x, w, bias=None, residual=None):
+    """a linear layer on vae_conv's 1 x 1 form, all rows of all images as ONE run of rows (n = 1, H = rows, W = 1): x fp16
+    (..., K) dense, w fp16 (N, K) packed, bias fp32 (N), residual fp16 (..., N) -> [residual +] x w^T + bias, fp16 (..., N)"""
+    K = x.shape[-1]
+    if w.dim() != 2 or w.shape[1] != K:     # what vae_conv cannot see: it is handed K; everything else it checks itself
+        raise ValueError("conv_rows: x (..., K) and w (N, K), got %s and %s" % (tuple(x.shape), tuple(w.shape)))
+    N = w.shape[0]
+    return vae_conv(x, w, bias, 1, x.numel() // K, 1, K, N, 1, residual=residual).view(*x.shape[:-1], N)
+
+
 _vae_gn_ws = _PerStreamWorkspace()
 
 
@@ -1840,39 +1850,47 @@ def unet_ln_channels(C):
     return UNET_LN_MIN <= C <= UNET_LN_MAX and C % UNET_LN_STEP == 0
 
 
-def _strided_rows(t, name, C):
-    """(row stride, rows) of a fp16 (..., C) tensor whose rows are C dense values a fixed number of elements apart: a dense
-    tensor, or a column slice of one; 16-byte aligned rows"""
+def _uniform_rows(t, name, C, dims=None):
+    """(row stride ld, rows) of a fp16 (..., C) tensor (of `dims` dimensions, where given) whose row i starts i ld elements
+    after the first: the last stride is 1 and the leading dimensions nest without gaps -- a dense tensor, or a column slice of
+    a dense wider one -- with ld >= C, ld a multiple of 8 and a 16-byte aligned base.  Nothing is copied (_rows copies where
+    this raises): the kernels only see ld."""
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s: expected a tensor, got %s" % (name, type(t).__name__))
     if t.dtype != torch.float16:
-        raise TypeError("%s: dtype %s, expected %s" % (name, t.dtype, torch.float16))
-    if t.dim() < 2 or t.shape[-1] != C or t.numel() == 0:
-        raise ValueError("%s: shape %s, expected (..., %d)" % (name, tuple(t.shape), C))
-    rows = t.numel() // C
-    if t.is_contiguous():
-        ld = C
-    elif t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= C:
-        ld = t.stride(0)
-    else:
-        raise ValueError("%s: rows must be dense and uniformly strided (a dense tensor or a 2-D column slice)" % name)
-    if ld % 8 or t.data_ptr() % 16:
-        raise ValueError("%s: rows must be 16-byte aligned" % name)
-    return ld, rows
+        raise TypeError("%s: dtype %s, expected %s (bf16 is not built)" % (name, t.dtype, torch.float16))
+    if (t.dim() < 2 if dims is None else t.dim() != dims) or t.shape[-1] != C or t.numel() == 0:
+        raise ValueError("%s: shape %s, expected (%s, %d)" % (name, tuple(t.shape), "B, L" if dims == 3 else "...", C))
+    ld, ok = C, True
+    if not t.is_contiguous():
+        span = None
+        for size, stride in zip(t.shape[-2::-1], t.stride()[-2::-1]):   # outwards from the rows; a dimension of 1 says nothing
+            if size != 1:
+                if span is None:            # (not `not span`: a stride of 0, an expanded dimension, is a value like any other)
+                    ld = span = stride
+                ok = ok and stride == span
+                span *= size
+        ok = ok and t.stride(-1) == 1
+    if not ok:
+        raise ValueError("%s: rows must be dense and uniformly strided (a dense tensor or a column slice of one)" % name)
+    if ld < C or ld % 8 or t.data_ptr() % 16:
+        raise ValueError("%s: rows must be 16-byte aligned, a multiple of 8 elements and at least %d apart" % (name, C))
+    return ld, t.numel() // C
 
 
 def unet_layernorm(x, gamma, beta, eps=1e-5, residual=None, want_sum=False):
     """LayerNorm(C, eps)(x [+ residual]) * gamma + beta on fp16 rows (..., C), C a multiple of 8 in 64 .. 2560; gamma / beta fp32
-    (C).  x and residual may be 2-D column slices (a row stride above C).  -> y fp16, dense, shaped like x; with want_sum,
-    (y, x + residual rounded once to fp16) (unet_layernorm)"""
+    (C).  x and residual may be column slices of dense wider tensors, 2-D or with leading dimensions (a row stride above C: the
+    kernel only sees the stride).  -> y fp16, dense, shaped like x; with want_sum, (y, x + residual rounded once to fp16)
+    (unet_layernorm)"""
     if not isinstance(x, torch.Tensor) or x.dim() < 2 or not unet_ln_channels(x.shape[-1]):
         raise ValueError("unet_layernorm: x must be (..., C), C a multiple of %d in %d .. %d, got %s"
                          % (UNET_LN_STEP, UNET_LN_MIN, UNET_LN_MAX, tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)))
     C = x.shape[-1]
-    ldx, rows = _strided_rows(x, "unet_layernorm: x", C)
+    ldx, rows = _uniform_rows(x, "unet_layernorm: x", C)
     ldr = 0
     if residual is not None:
-        ldr, rrows = _strided_rows(residual, "unet_layernorm: residual", C)
+        ldr, rrows = _uniform_rows(residual, "unet_layernorm: residual", C)
         if rrows != rows:
             raise ValueError("unet_layernorm: residual of %d rows, x of %d" % (rrows, rows))
     _dense(gamma, "unet_layernorm: gamma", torch.float32, (C,), align=16)
@@ -1920,24 +1938,6 @@ def unet_geglu(x, w, bias, out=None):
 UNET_ATTN_HEAD_DIM = 160
 
 
-def _batched_rows(t, name, C):
-    """row stride of a fp16 (B, L, C) tensor whose row b L + i starts (b L + i) ld elements after its first: a dense tensor,
-    or a column slice of a dense (B, L, k C) one; nothing is copied, anything else raises"""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s: expected a tensor, got %s" % (name, type(t).__name__))
-    if t.dtype != torch.float16:
-        raise TypeError("%s: dtype %s, expected %s (bf16 is not built)" % (name, t.dtype, torch.float16))
-    if t.dim() != 3 or t.shape[-1] != C or t.numel() == 0:
-        raise ValueError("%s: shape %s, expected (B, L, %d)" % (name, tuple(t.shape), C))
-    B, L, _ = t.shape
-    ld = t.stride(1) if L > 1 else (t.stride(0) if B > 1 else C)
-    if t.stride(2) != 1 or (B > 1 and t.stride(0) != L * ld):
-        raise ValueError("%s: rows must be dense and uniformly strided (a dense tensor or a column slice of one)" % name)
-    if ld < C or ld % 8 or t.data_ptr() % 16:
-        raise ValueError("%s: rows must be 16-byte aligned, a multiple of 8 elements and at least %d apart" % (name, C))
-    return ld
-
-
 def unet_attention(q, k, v, heads, scale, out=None):
     """softmax(scale q k^T) v per (batch, head) at head dim 160: q (B, Lq, heads * 160), k and v (B, Lk, heads * 160), fp16;
     each may be a column slice of a wider buffer (q | k | v of a fused projection), k and v with one row stride.  Any Lq and
@@ -1952,9 +1952,9 @@ def unet_attention(q, k, v, heads, scale, out=None):
                                   % (C // heads if heads > 0 and C % heads == 0 else "?", C, heads, UNET_ATTN_HEAD_DIM))
     if not (float(scale) > 0 and math.isfinite(float(scale))):
         raise ValueError("unet_attention: scale %r must be positive and finite" % (scale,))
-    q_ld = _batched_rows(q, "unet_attention: q", C)
-    kv_ld = _batched_rows(k, "unet_attention: k", C)
-    v_ld = _batched_rows(v, "unet_attention: v", C)
+    q_ld = _uniform_rows(q, "unet_attention: q", C, 3)[0]
+    kv_ld = _uniform_rows(k, "unet_attention: k", C, 3)[0]
+    v_ld = _uniform_rows(v, "unet_attention: v", C, 3)[0]
     if k.shape != v.shape or k.shape[0] != B or v_ld != kv_ld:
         raise ValueError("unet_attention: k %s and v %s must be (%d, Lk, %d) with one row stride (got %d and %d)"
                          % (tuple(k.shape), tuple(v.shape), B, C, kv_ld, v_ld))
@@ -1963,7 +1963,7 @@ def unet_attention(q, k, v, heads, scale, out=None):
         out = torch.empty(B, Lq, C, dtype=torch.float16, device=q.device)
     elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, Lq, C):
         raise ValueError("unet_attention: out must be a fp16 (%d, %d, %d) tensor" % (B, Lq, C))
-    out_ld = _batched_rows(out, "unet_attention: out", C)
+    out_ld = _uniform_rows(out, "unet_attention: out", C, 3)[0]
     _need_gpu(q, k, v, out)
     rc = _lib.load().unet_attention(q.data_ptr(), q_ld, k.data_ptr(), v.data_ptr(), kv_ld, out.data_ptr(), out_ld, B, heads, Lq,
                                     Lk, UNET_ATTN_HEAD_DIM, float(scale), _lib.F16, _stream())

@@ -43,7 +43,8 @@ import weakref
 
 import torch
 
-from . import _lib, ops
+from . import _dropin, _lib, ops
+from ._dropin import rows16 as _rows16
 from .processor import FRESCOAttnProcessor2_0, _plain_linear
 
 HEAD_DIMS_FLASH = (40, 80)                 # ops.attention
@@ -135,23 +136,15 @@ class UNetAttnProcessor:
         params = [m.weight for m in mods]
         return self._pack(attn, "|".join(names), params, lambda: torch.cat([p.detach() for p in params], dim=0).contiguous())
 
-    @staticmethod
-    def _rows16(x):
-        """x as dense 16-byte aligned rows (itself where it is that already)"""
-        if not x.is_contiguous():
-            return x.contiguous()
-        return x.clone() if x.data_ptr() % 16 else x
-
     def _project(self, attn, x, names):
         """[attn.<name>(x) for name in names], bias-free, in one launch that reads x once -> tensors (B, L, C), column slices
         of one buffer on the vae_conv path"""
         mods = [getattr(attn, n) for n in names]
-        B, L, K = x.shape
         N = mods[0].out_features
         if all(_plain_linear(m, False, len(mods)) and m.weight.is_contiguous() and m.weight.data_ptr() % 16 == 0 for m in mods):
             return ops.linear(x, [m.weight.detach() for m in mods], None, None)
         w = self._stacked(attn, names)
-        out = ops.vae_conv(self._rows16(x), w, None, 1, B * L, 1, K, N * len(mods), 1).view(B, L, N * len(mods))
+        out = ops.conv_rows(_rows16(x), w)
         return [out[..., i * N:(i + 1) * N] for i in range(len(mods))]
 
     def _text_kv(self, attn, text):
@@ -161,8 +154,7 @@ class UNetAttnProcessor:
             hit = self._text.get(attn)
             if hit is not None and hit[0] is text and hit[1] == text._version and hit[2] is w:
                 return hit[3]
-        B, Lt, TW = text.shape
-        kv = ops.vae_conv(self._rows16(text), w, None, 1, B * Lt, 1, TW, w.shape[0], 1).view(B, Lt, w.shape[0])
+        kv = ops.conv_rows(_rows16(text), w)
         if self.cache_text_kv:
             self._text[attn] = (text, text._version, w, kv)
         return kv
@@ -172,16 +164,15 @@ class UNetAttnProcessor:
         if _plain_linear(lin, True, 1) and lin.weight.is_contiguous() and lin.weight.data_ptr() % 16 == 0 \
                 and lin.bias.is_contiguous():
             return ops.linear(hs, [lin.weight.detach()], [lin.bias.detach()])[0]
-        w = self._pack(attn, "to_out.w", [lin.weight], lambda: self._rows16(lin.weight.detach()))
+        w = self._pack(attn, "to_out.w", [lin.weight], lambda: _rows16(lin.weight.detach()))
         b = self._pack(attn, "to_out.b", [lin.bias], lambda: lin.bias.detach().to(torch.float32).contiguous())
-        B, L, C = hs.shape
-        return ops.vae_conv(self._rows16(hs), w, b, 1, B * L, 1, C, lin.out_features, 1).view(B, L, lin.out_features)
+        return ops.conv_rows(_rows16(hs), w, b)
 
     # ---- the call ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None):
         def refuse(why):
-            raise NotImplementedError("%s: %s; there is no fallback to PyTorch" % (_WHO, why))
+            raise _dropin.refusal(_WHO, "", why)
         if attention_mask is not None:
             refuse("an attention_mask is not supported (the pipeline passes None)")
         if not isinstance(hidden_states, torch.Tensor) or hidden_states.dim() != 3:
@@ -189,7 +180,7 @@ class UNetAttnProcessor:
                    % ("%d-D" % hidden_states.dim() if isinstance(hidden_states, torch.Tensor) else type(hidden_states).__name__))
         why = self.refusal(attn)
         if why:
-            refuse("the attention module %s" % why)
+            raise _dropin.refusal(_WHO, "the attention module", why)
         text = encoder_hidden_states
         if text is not None and (not isinstance(text, torch.Tensor) or text.dim() != 3 or text.shape[0] != hidden_states.shape[0]):
             refuse("encoder_hidden_states must be (batch, tokens, width) with the batch of hidden_states")
@@ -232,10 +223,6 @@ class UNetAttnProcessor:
         return hs
 
 
-def _attentions(model):
-    return [(name, m) for name, m in model.named_modules() if all(hasattr(m, p) for p in PARTS)]
-
-
 def _set(m, proc):
     if hasattr(m, "set_processor"):
         m.set_processor(proc)
@@ -251,15 +238,9 @@ def patch_unet_attention(model, include_fresco_cross=False, processor=None):
     one outside what the processor computes raises NotImplementedError with its name before anything is patched.  Returns the
     number of modules patched; call it after apply_FRESCO_attn.  unpatch_unet_attention puts the previous processors back."""
     unpatch_unet_attention(model)
-    chosen = []
-    for name, m in _attentions(model):
-        if isinstance(m.processor, FRESCOAttnProcessor2_0) and not (include_fresco_cross and name.endswith(".attn2")):
-            continue
-        chosen.append((name, m))
-    for name, m in chosen:
-        why = UNetAttnProcessor.refusal(m)
-        if why:
-            raise NotImplementedError("%s: %s %s; there is no fallback to PyTorch" % (_WHO, name or "the model", why))
+    chosen = [(name, m) for name, m in _dropin.find(model, PARTS)
+              if not isinstance(m.processor, FRESCOAttnProcessor2_0) or (include_fresco_cross and name.endswith(".attn2"))]
+    _dropin.check_all(_WHO, chosen, UNetAttnProcessor)
     proc = processor if processor is not None else UNetAttnProcessor()
     for _, m in chosen:
         m.__dict__[_ATTR] = m.processor

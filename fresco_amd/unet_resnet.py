@@ -26,16 +26,14 @@ are UNVERIFIED against the real module.
 """
 import torch
 
-from . import _lib, ops
+from . import _dropin, _lib, ops
+from ._dropin import f32 as _f32
 from .vae import pack_conv_weight
 
 GROUPS = 32
 PARTS = ("norm1", "conv1", "time_emb_proj", "norm2", "conv2")  # what makes a module a resnet block for patch_unet_resnets
 _ATTR = "_fresco_unet_resnet"
-
-
-def _f32(t, device):
-    return t.detach().to(device, torch.float32).contiguous()
+_WHO = "fresco_amd.unet_resnet"
 
 
 class UNetResnet:
@@ -43,17 +41,7 @@ class UNetResnet:
 
     def __init__(self, state_dict, prefix, cin, cout, temb_channels=1280, eps=1e-5, device=None,
                  memory_format=torch.channels_last):
-        if prefix and not prefix.endswith("."):
-            prefix += "."
-        sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
-        what = "fresco_amd.unet_resnet: %s" % (prefix[:-1] or "the block")
-        need = [p + s for p in PARTS for s in (".weight", ".bias")]
-        missing = [k for k in need if k not in sd]
-        if missing:
-            raise ValueError("%s: missing parameters %s" % (what, missing[:4]))
-        for k in need:
-            if sd[k].dtype != torch.float16:
-                raise TypeError("%s: fp16 blocks only (%s is %s); bf16 and fp32 UNets are not supported" % (what, k, sd[k].dtype))
+        sd, what = _dropin.intake(state_dict, prefix, [p + s for p in PARTS for s in (".weight", ".bias")], _WHO, "the block")
         if not (ops.unet_gn_channels(cin) and ops.unet_gn_channels(cout)):
             raise NotImplementedError("%s: %d -> %d channels; the GroupNorm kernel takes multiples of %d in %d .. %d"
                                       % (what, cin, cout, ops.UNET_GN_STEP, ops.UNET_GN_MIN, ops.UNET_GN_MAX))
@@ -67,12 +55,7 @@ class UNetResnet:
             raise ValueError("%s: conv_shortcut %s at %d -> %d" % (what, "present" if has else "missing", cin, cout))
         if has:
             shapes.update({"conv_shortcut.weight": (cout, cin, 1, 1), "conv_shortcut.bias": (cout,)})
-        for k, shp in shapes.items():
-            if k not in sd or tuple(sd[k].shape) != shp:
-                raise ValueError("%s: %s is %s, expected %s" % (what, k, tuple(sd[k].shape) if k in sd else None, shp))
-        extra = sorted(k for k in sd if k not in shapes)
-        if extra:
-            raise ValueError("%s: unexpected parameters %s" % (what, extra[:4]))
+        _dropin.check_shapes(sd, shapes, what, only=True)
         dev = torch.device(device) if device is not None else sd["conv1.weight"].device
         self.cin, self.cout, self.temb_channels, self.eps = int(cin), int(cout), int(temb_channels), float(eps)
         self.device, self.memory_format = dev, memory_format
@@ -125,7 +108,7 @@ class UNetResnet:
     def from_module(cls, block, device=None, memory_format=torch.channels_last, name="the block"):
         why = cls.refusal(block)
         if why:
-            raise NotImplementedError("fresco_amd.unet_resnet: %s %s; there is no fallback to PyTorch" % (name, why))
+            raise _dropin.refusal(_WHO, name, why)
         w1 = block.conv1.weight
         return cls(block.state_dict(), "", int(w1.shape[1]), int(w1.shape[0]), int(block.time_emb_proj.weight.shape[1]),
                    float(block.norm1.eps), device=device, memory_format=memory_format)
@@ -144,10 +127,10 @@ class UNetResnet:
         n, _, H, W = x.shape
         if tuple(temb.shape) != (n, self.temb_channels):
             raise ValueError("fresco_amd.unet_resnet: temb must be (%d, %d), got %s" % (n, self.temb_channels, tuple(temb.shape)))
+        fmt = self.memory_format if memory_format is None else memory_format
+        _dropin.check_format(_WHO, fmt)
         ops._need_gpu(x, temb)
-        xn = x.permute(0, 2, 3, 1)          # NHWC: a view of a channels_last tensor, a copy of any other
-        if not xn.is_contiguous() or xn.data_ptr() % 16:
-            xn = xn.contiguous() if not xn.is_contiguous() else xn.clone()
+        xn = _dropin.nhwc(x)
         h = ops.unet_groupnorm(xn, self.g1, self.b1, self.eps, silu=True)
         h = ops.vae_conv(h, self.w1, None, n, H, W, self.cin, self.cout, 3)
         add = ops.unet_temb(temb.contiguous(), self.wt, self.bt, self.cb1)
@@ -155,17 +138,7 @@ class UNetResnet:
             taps["conv1_temb"] = h.float() + add[:, None, None, :]
         h = ops.unet_groupnorm(h, self.g2, self.b2, self.eps, silu=True, addend=add)
         skip = xn if self.ws is None else ops.vae_conv(xn, self.ws, self.cbs, n, H * W, 1, self.cin, self.cout, 1)
-        out = ops.vae_conv(h, self.w2, self.cb2, n, H, W, self.cout, self.cout, 3, residual=skip).permute(0, 3, 1, 2)
-        fmt = self.memory_format if memory_format is None else memory_format
-        if fmt == torch.channels_last:
-            return out
-        if fmt != torch.contiguous_format:
-            raise ValueError("fresco_amd.unet_resnet: memory_format must be channels_last or contiguous_format")
-        return out.contiguous()
-
-
-def _resnet_blocks(model):
-    return [(name, m) for name, m in model.named_modules() if all(hasattr(m, p) for p in PARTS)]
+        return _dropin.nchw(ops.vae_conv(h, self.w2, self.cb2, n, H, W, self.cout, self.cout, 3, residual=skip), fmt)
 
 
 def patch_unet_resnets(model, memory_format=torch.channels_last):
@@ -173,27 +146,9 @@ def patch_unet_resnets(model, memory_format=torch.channels_last):
     conv2 by a UNetResnet built from it; returns the number of blocks patched.  A matching block outside the supported
     configuration raises NotImplementedError with its name, before anything is patched.  The modules' own methods stay on
     their class: unpatch_unet_resnets removes the bindings.  The weights are copied: patch again after loading others."""
-    if memory_format not in (torch.channels_last, torch.contiguous_format):
-        raise ValueError("fresco_amd.unet_resnet: memory_format must be channels_last or contiguous_format")
-    unpatch_unet_resnets(model)
-    blocks = _resnet_blocks(model)
-    for name, m in blocks:
-        why = UNetResnet.refusal(m)
-        if why:
-            raise NotImplementedError("fresco_amd.unet_resnet: %s %s; there is no fallback to PyTorch" % (name or "the model", why))
-    for name, m in blocks:
-        native = UNetResnet.from_module(m, memory_format=memory_format, name=name)
-        m.__dict__[_ATTR] = native
-        m.__dict__["forward"] = native
-    return len(blocks)
+    return _dropin.patch(model, UNetResnet, PARTS, _WHO, _ATTR, memory_format)
 
 
 def unpatch_unet_resnets(model):
     """the modules' own forwards again; returns the number of blocks restored"""
-    count = 0
-    for _, m in model.named_modules():
-        if _ATTR in vars(m):
-            del m.__dict__[_ATTR]
-            m.__dict__.pop("forward", None)
-            count += 1
-    return count
+    return _dropin.unpatch(model, _ATTR)

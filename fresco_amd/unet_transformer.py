@@ -36,7 +36,8 @@ where this package is built and tested: the parameter names, the attributes and 
 """
 import torch
 
-from . import _lib, ops
+from . import _dropin, _lib, ops
+from ._dropin import f32 as _f32
 from .vae import pack_conv_weight
 
 GROUPS = 32
@@ -44,10 +45,6 @@ PARTS = ("norm", "proj_in", "transformer_blocks", "proj_out")    # what makes a 
 BLOCK_PARTS = ("norm1", "attn1", "norm2", "attn2", "norm3", "ff")
 _ATTR = "_fresco_unet_transformer"
 _WHO = "fresco_amd.unet_transformer"
-
-
-def _f32(t, device):
-    return t.detach().to(device, torch.float32).contiguous()
 
 
 def pack_geglu_weight(weight, bias):
@@ -86,24 +83,15 @@ class UNetTransformer:
 
     def __init__(self, state_dict, prefix, attentions, norm_eps=1e-6, ln_eps=1e-5, device=None,
                  memory_format=torch.channels_last):
-        if prefix and not prefix.endswith("."):
-            prefix += "."
-        sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
-        what = "%s: %s" % (_WHO, prefix[:-1] or "the transformer")
         attentions = list(attentions)
-        if not attentions or any(len(p) != 2 or not callable(p[0]) or not callable(p[1]) for p in attentions):
-            raise ValueError("%s: attentions must be a list of (attn1, attn2) modules, one pair per block" % what)
         names = ["norm", "proj_in", "proj_out"]
         for i in range(len(attentions)):
             b = "transformer_blocks.%d." % i
             names += [b + "norm1", b + "norm2", b + "norm3", b + "ff.net.0.proj", b + "ff.net.2"]
-        need = [p + s for p in names for s in (".weight", ".bias")]
-        missing = [k for k in need if k not in sd]
-        if missing:
-            raise ValueError("%s: missing parameters %s" % (what, missing[:4]))
-        for k in need:
-            if sd[k].dtype != torch.float16:
-                raise TypeError("%s: fp16 modules only (%s is %s); bf16 and fp32 UNets are not supported" % (what, k, sd[k].dtype))
+        sd, what = _dropin.intake(state_dict, prefix, [p + s for p in names for s in (".weight", ".bias")], _WHO,
+                                  "the transformer")
+        if not attentions or any(len(p) != 2 or not callable(p[0]) or not callable(p[1]) for p in attentions):
+            raise ValueError("%s: attentions must be a list of (attn1, attn2) modules, one pair per block" % what)
         if sd["proj_in.weight"].dim() != 4 or tuple(sd["proj_in.weight"].shape[2:]) != (1, 1):
             raise NotImplementedError("%s: proj_in is not a 1 x 1 convolution (use_linear_projection?)" % what)
         D, C = (int(v) for v in sd["proj_in.weight"].shape[:2])
@@ -119,9 +107,7 @@ class UNetTransformer:
                 shapes.update({b + nm + ".weight": (D,), b + nm + ".bias": (D,)})
             shapes.update({b + "ff.net.0.proj.weight": (2 * inner, D), b + "ff.net.0.proj.bias": (2 * inner,),
                            b + "ff.net.2.weight": (D, inner), b + "ff.net.2.bias": (D,)})
-        for k, shp in shapes.items():
-            if tuple(sd[k].shape) != shp:
-                raise ValueError("%s: %s is %s, expected %s" % (what, k, tuple(sd[k].shape), shp))
+        _dropin.check_shapes(sd, shapes, what, only=False)
         dev = torch.device(device) if device is not None else sd["proj_in.weight"].device
         self.channels, self.width, self.inner = C, D, inner
         self.norm_eps, self.ln_eps = float(norm_eps), float(ln_eps)
@@ -217,7 +203,7 @@ class UNetTransformer:
     def from_module(cls, tf, device=None, memory_format=torch.channels_last, name="the transformer"):
         why = cls.refusal(tf)
         if why:
-            raise NotImplementedError("%s: %s %s; there is no fallback to PyTorch" % (_WHO, name, why))
+            raise _dropin.refusal(_WHO, name, why)
         sd = {k: v for k, v in tf.state_dict().items() if ".attn1." not in k and ".attn2." not in k}
         return cls(sd, "", [(b.attn1, b.attn2) for b in tf.transformer_blocks], float(tf.norm.eps),
                    float(tf.transformer_blocks[0].norm1.eps), device=device, memory_format=memory_format)
@@ -227,11 +213,7 @@ class UNetTransformer:
         if not isinstance(a, torch.Tensor) or a.dtype != torch.float16 or tuple(a.shape) != shape:
             raise TypeError("%s: an attention module returned %s, expected a fp16 tensor of %s"
                             % (_WHO, (a.dtype, tuple(a.shape)) if isinstance(a, torch.Tensor) else type(a).__name__, shape))
-        if not a.is_contiguous():
-            a = a.contiguous()
-        elif a.data_ptr() % 16:
-            a = a.clone()
-        return a
+        return _dropin.rows16(a)
 
     @torch.no_grad()
     def __call__(self, hidden_states, encoder_hidden_states=None, timestep=None, class_labels=None, cross_attention_kwargs=None,
@@ -242,8 +224,7 @@ class UNetTransformer:
         for v, nm in ((timestep, "timestep"), (class_labels, "class_labels"), (attention_mask, "attention_mask"),
                       (encoder_attention_mask, "encoder_attention_mask")):
             if v is not None:
-                raise NotImplementedError("%s: %s is not supported (the pipeline passes None); there is no fallback to PyTorch"
-                                          % (_WHO, nm))
+                raise _dropin.refusal(_WHO, nm, "is not supported (the pipeline passes None)")
         x = hidden_states
         if not isinstance(x, torch.Tensor):
             raise TypeError("%s: hidden_states must be a tensor" % _WHO)
@@ -252,18 +233,14 @@ class UNetTransformer:
         if x.dim() != 4 or x.shape[1] != self.channels or x.numel() == 0:
             raise ValueError("%s: hidden_states must be (n, %d, H, W), got %s" % (_WHO, self.channels, tuple(x.shape)))
         fmt = self.memory_format if memory_format is None else memory_format
-        if fmt not in (torch.channels_last, torch.contiguous_format):
-            raise ValueError("%s: memory_format must be channels_last or contiguous_format" % _WHO)
+        _dropin.check_format(_WHO, fmt)
         ops._need_gpu(x)
         kw = dict(cross_attention_kwargs) if cross_attention_kwargs is not None else {}
         n, C, H, W = x.shape
-        D, M = self.width, n * H * W
-        xn = x.permute(0, 2, 3, 1)          # NHWC: a view of a channels_last tensor, a copy of any other
-        if not xn.is_contiguous() or xn.data_ptr() % 16:
-            xn = xn.contiguous() if not xn.is_contiguous() else xn.clone()
+        xn = _dropin.nhwc(x)
         h = ops.unet_groupnorm(xn, self.gn_g, self.gn_b, self.norm_eps, silu=False)
-        h = ops.vae_conv(h, self.w_in, self.b_in, 1, M, 1, C, D, 1).view(n, H * W, D)
-        shape = (n, H * W, D)
+        shape = (n, H * W, self.width)
+        h = ops.conv_rows(h.view(n, H * W, C), self.w_in, self.b_in)      # tokens: all rows of all images as one run of rows
         for i, blk in enumerate(self.blocks):
             y = ops.unet_layernorm(h, blk.ln[0][0], blk.ln[0][1], self.ln_eps)
             a = self._attend(blk.attn1, y, None, kw, shape)
@@ -273,12 +250,10 @@ class UNetTransformer:
             g = ops.unet_geglu(y, blk.w_ff1, blk.b_ff1)
             if taps is not None and i == 0:
                 taps["geglu"] = g
-            h = ops.vae_conv(g, blk.w_ff2, blk.b_ff2, 1, M, 1, self.inner, D, 1, residual=h).view(n, H * W, D)
+            h = ops.conv_rows(g, blk.w_ff2, blk.b_ff2, residual=h)
         if taps is not None:
             taps["tokens"] = h
-        out = ops.vae_conv(h, self.w_out, self.b_out, 1, M, 1, D, C, 1, residual=xn).view(n, H, W, C).permute(0, 3, 1, 2)
-        if fmt == torch.contiguous_format:
-            out = out.contiguous()
+        out = _dropin.nchw(ops.conv_rows(h.view(n, H, W, self.width), self.w_out, self.b_out, residual=xn), fmt)
         return UNetTransformerOutput(out) if return_dict else (out,)
 
 
@@ -294,37 +269,15 @@ def _width_refusal(C, D, inner):
     return None
 
 
-def _transformers(model):
-    return [(name, m) for name, m in model.named_modules() if all(hasattr(m, p) for p in PARTS)]
-
-
 def patch_unet_transformers(model, memory_format=torch.channels_last):
     """replace `forward` on every module of `model` (pipe.unet, a ControlNet) that has norm, proj_in, transformer_blocks and
     proj_out by a UNetTransformer built from it; returns the number of modules patched.  The blocks' attention modules stay
     as they are and are called with whatever processor is set on them at call time.  A matching module outside the supported
     configuration raises NotImplementedError with its name, before anything is patched.  The modules' own methods stay on
     their class: unpatch_unet_transformers removes the bindings.  The weights are copied: patch again after loading others."""
-    if memory_format not in (torch.channels_last, torch.contiguous_format):
-        raise ValueError("%s: memory_format must be channels_last or contiguous_format" % _WHO)
-    unpatch_unet_transformers(model)
-    found = _transformers(model)
-    for name, m in found:
-        why = UNetTransformer.refusal(m)
-        if why:
-            raise NotImplementedError("%s: %s %s; there is no fallback to PyTorch" % (_WHO, name or "the model", why))
-    for name, m in found:
-        native = UNetTransformer.from_module(m, memory_format=memory_format, name=name)
-        m.__dict__[_ATTR] = native
-        m.__dict__["forward"] = native
-    return len(found)
+    return _dropin.patch(model, UNetTransformer, PARTS, _WHO, _ATTR, memory_format)
 
 
 def unpatch_unet_transformers(model):
     """the modules' own forwards again; returns the number of modules restored"""
-    count = 0
-    for _, m in model.named_modules():
-        if _ATTR in vars(m):
-            del m.__dict__[_ATTR]
-            m.__dict__.pop("forward", None)
-            count += 1
-    return count
+    return _dropin.unpatch(model, _ATTR)

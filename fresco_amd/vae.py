@@ -206,8 +206,8 @@ class _Half:
         Lp = (L + 31) // 32 * 32  # the key axis is P V's K: padded to the kernel's chunk with zero probabilities
         a = self.attn
         h = ops.vae_groupnorm(x, self.attn_norm.g, self.attn_norm.b, EPS, silu=False)
-        q = ops.vae_conv(h, a["to_q"].w, a["to_q"].b, 1, n * L, 1, C, C, 1)
-        k = ops.vae_conv(h, a["to_k"].w, a["to_k"].b, 1, n * L, 1, C, C, 1)
+        q = ops.conv_rows(h, a["to_q"].w, a["to_q"].b)
+        k = ops.conv_rows(h, a["to_k"].w, a["to_k"].b)
         # V^T = W_v x^T: to_v's weight is the kernel's pixel operand there, its bias a per-row one
         vt = torch.zeros(n, C, Lp, dtype=torch.float16, device=x.device)
         ops.vae_conv(a["to_v"].w, h, a["to_v"].b, n, C, 1, C, L, 1, x_img_stride=0, w_img_stride=L * C, bias_rows=True,
@@ -216,7 +216,7 @@ class _Half:
         ops.vae_conv(q, k, None, n, L, 1, C, L, 1, out_kind=_lib.VAE_OUT_F32, w_img_stride=L * C, ldo=Lp, out=scores)
         p = ops.vae_softmax(scores, L, float(C) ** -0.5, ld_out=Lp)
         o = ops.vae_conv(p, vt, None, n, L, 1, Lp, C, 1, w_img_stride=C * Lp)
-        return ops.vae_conv(o, a["to_out.0"].w, a["to_out.0"].b, 1, n * L, 1, C, C, 1, residual=x).view(n, H, W, C)
+        return ops.conv_rows(o, a["to_out.0"].w, a["to_out.0"].b, residual=x).view(n, H, W, C)
 
     def _mid(self, x, n, H, W):
         x = self._resnet(x, self.mid[0], n, H, W)

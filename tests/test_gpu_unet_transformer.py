@@ -101,6 +101,21 @@ def test_layernorm_row_strides_and_leading_shapes():
            16 * E * ((xs.abs() + mean.abs()) * rstd * gamma.double().abs() + beta.double().abs()) + 1e-6 + H11 * ref.abs())
     x3 = x.contiguous().view(1, rows, C)
     assert torch.equal(ops.unet_layernorm(x3, gamma, beta, eps, residual=r.contiguous().view(1, rows, C)).view(rows, C), y)
+    # a 3-D column slice: 10 rows of 64 at a stride of 192, the leading dimensions nested
+    C = 64
+    gamma, beta = (_randn(C, seed=5) * 0.5 + 1.0).to(DEV), _randn(C, seed=6).to(DEV)
+    wide = (_randn(2, 5, 192, seed=7) * 2.0 + 0.5).half().to(DEV)
+    x, keep = wide[..., 64:128], wide.clone()
+    assert x.shape == (2, 5, C) and x.stride() == (960, 192, 1) and not x.is_contiguous()
+    y = ops.unet_layernorm(x, gamma, beta, eps)
+    assert y.shape == (2, 5, C) and y.dtype == torch.float16 and y.is_contiguous() and torch.equal(wide, keep)
+    assert torch.equal(y, ops.unet_layernorm(x.contiguous(), gamma, beta, eps))
+    xs = x.double()
+    mean = xs.mean(-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(xs.var(-1, unbiased=False, keepdim=True) + eps)
+    ref = (xs - mean) * rstd * gamma.double() + beta.double()
+    _check("layernorm 3-D column slice C=64 rows=10 ld=192", y, ref,
+           16 * E * ((xs.abs() + mean.abs()) * rstd * gamma.double().abs() + beta.double().abs()) + 1e-6 + H11 * ref.abs())
 
 
 # ---------------------------------------------------------------------------------------------------------------

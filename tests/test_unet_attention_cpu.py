@@ -120,6 +120,17 @@ def test_ops_check_before_the_library_is_asked():
         ops.unet_attention(torch.zeros(2, 5, 324, dtype=torch.float16)[..., 4:], q, q, 2, 0.1)
     with pytest.raises(ValueError, match="out must be"):
         ops.unet_attention(q, q, q, 2, 0.1, out=torch.zeros(2, 4, 320, dtype=torch.float16))
+    # an expanded dimension: strides (640, 0, 1) over 1280 elements.  Ten rows 640 apart would leave the storage -- as `out`,
+    # in a write
+    expanded = torch.zeros(2, 1, 640, dtype=torch.float16)[..., :320].expand(2, 5, 320)
+    assert expanded.stride() == (640, 0, 1)
+    for bad in ((expanded, q, q), (q, expanded, q), (q, q, expanded)):
+        with pytest.raises(ValueError, match="uniformly strided"):
+            ops.unet_attention(*bad, 2, 0.1)
+    with pytest.raises(ValueError, match="out: rows must be dense and uniformly strided"):
+        ops.unet_attention(q, q, q, 2, 0.1, out=expanded)
+    with pytest.raises(ValueError, match="at least 320 apart"):         # every row the same row
+        ops.unet_attention(expanded[:1], q[:1], q[:1], 2, 0.1)
     # slices of one (rows, 3 C) buffer pass every check: only the GPU is missing
     qkv = torch.zeros(2, 5, 960, dtype=torch.float16)
     with pytest.raises(FrescoHipError, match="GPU only"):
@@ -285,9 +296,10 @@ class _Ops:
     def __init__(self):
         self.convs = []
 
-    def vae_conv(self, x, w, bias, n, H, W, cin, cout, ksize, **kw):
-        self.convs.append((x.data_ptr(), w.data_ptr(), H, cin, cout))
-        return (x.reshape(H, cin).float() @ w.float().t()).half().view(1, H, 1, cout)
+    def conv_rows(self, x, w, bias=None, residual=None):
+        cin, cout = x.shape[-1], w.shape[0]
+        self.convs.append((x.data_ptr(), w.data_ptr(), x.numel() // cin, cin, cout))
+        return (x.reshape(-1, cin).float() @ w.float().t()).half().view(x.shape[:-1] + (cout,))
 
 
 @pytest.fixture

@@ -236,9 +236,9 @@ def test_call_time_refusals_and_return_dict():
             return xn
 
         @staticmethod
-        def vae_conv(x, w, bias, n, H, W, cin, cout, ksize, residual=None):
+        def conv_rows(x, w, bias=None, residual=None):
             calls.append("conv")
-            return torch.zeros(n, H, W, cout, dtype=torch.float16)
+            return torch.zeros(x.shape[:-1] + (w.shape[0],), dtype=torch.float16)
 
         @staticmethod
         def unet_layernorm(x, g, b, eps, residual=None, want_sum=False):
@@ -356,6 +356,29 @@ def test_ops_check_before_the_library_is_asked():
         ops.unet_layernorm(x, g, g, residual=x[:2])
     with pytest.raises(ValueError, match="16-byte aligned"):
         ops.unet_layernorm(torch.zeros(4, 324, dtype=torch.float16)[:, :320], g, g)
+    # three dimensions whose leading two do not nest: images 512 apart, 3 rows of 128 each.  (The whole [:, ::2] of the same
+    # tensor DOES nest, 4 x 128 = 512: it is 8 uniformly strided rows and passes this check.)
+    g64 = torch.ones(64)
+    with pytest.raises(ValueError, match="uniformly strided"):
+        ops.unet_layernorm(torch.zeros(2, 8, 64, dtype=torch.float16)[:, :6:2], g64, g64)
+    with pytest.raises(ValueError, match="uniformly strided"):
+        ops.unet_layernorm(torch.zeros(2, 8, 64, dtype=torch.float16)[:, :3], g64, g64)
+    with pytest.raises(FrescoHipError, match="GPU only"):
+        ops.unet_layernorm(torch.zeros(2, 8, 64, dtype=torch.float16)[:, ::2], g64, g64)
+    # an expanded dimension: strides (256, 0, 1) over 512 elements.  Eight rows 256 apart would leave the storage
+    wide = torch.zeros(2, 1, 256, dtype=torch.float16)
+    expanded = wide[..., :64].expand(2, 4, 64)
+    assert expanded.stride() == (256, 0, 1)
+    with pytest.raises(ValueError, match="uniformly strided"):
+        ops.unet_layernorm(expanded, g64, g64)
+    with pytest.raises(ValueError, match="uniformly strided"):
+        ops.unet_layernorm(torch.zeros(2, 4, 64, dtype=torch.float16), g64, g64, residual=expanded)
+    with pytest.raises(ValueError, match="at least 64 apart"):          # every row the same row
+        ops.unet_layernorm(wide[0, :, :64].expand(4, 64), g64, g64)
+    with pytest.raises(ValueError, match="at least 64 apart"):
+        ops.unet_layernorm(torch.zeros(2, 1, 64, dtype=torch.float16).expand(2, 4, 64)[:1], g64, g64)
+    with pytest.raises(FrescoHipError, match="GPU only"):     # a 3-D column slice passes every check: only the GPU is missing
+        ops.unet_layernorm(torch.zeros(2, 5, 192, dtype=torch.float16)[..., 64:128], g64, g64)
     w, b = torch.zeros(128, 320, dtype=torch.float16), torch.zeros(128)
     with pytest.raises(FrescoHipError, match="GPU only"):
         ops.unet_geglu(x, w, b)
@@ -365,3 +388,55 @@ def test_ops_check_before_the_library_is_asked():
         ops.unet_geglu(x, torch.zeros(128, 64, dtype=torch.float16), b)
     with pytest.raises(ValueError, match=r"out must be a fp16 \(4, 64\)"):
         ops.unet_geglu(x, w, b, out=torch.zeros(4, 32, dtype=torch.float16))
+
+
+def test_uniform_rows_is_its_definition():
+    """accepted exactly where row i starts i ld elements after the first, ld >= C and a multiple of 8, the values dense: over
+    every (a, b, 64) view of one buffer with these strides, a stride of 0 (an expanded dimension) among them"""
+    import itertools
+    from fresco_amd import ops
+    C, buf, accepted = 64, torch.zeros(1 << 13, dtype=torch.float16), 0
+    for shape in itertools.product((1, 2, 3), (1, 2, 4)):
+        for st in itertools.product((0, 64, 128, 256, 384, 512, 1024), (0, 8, 64, 72, 128, 256), (1, 2)):
+            starts = [a * st[0] + b * st[1] for a in range(shape[0]) for b in range(shape[1])]
+            ld = starts[1] - starts[0] if len(starts) > 1 else C
+            want = st[2] == 1 and starts == [i * ld for i in range(len(starts))] and ld >= C and ld % 8 == 0
+            try:
+                got = ops._uniform_rows(buf.as_strided(shape + (C,), st), "t", C)
+            except ValueError:
+                got = None
+            assert got == ((ld, len(starts)) if want else None), (shape, st, got)
+            accepted += want
+    assert accepted == 182
+
+
+def test_conv_rows_asks_vae_conv_for_one_run_of_rows(monkeypatch):
+    """the flat-row form: n, H, W, cin, cout, ksize = 1, rows, 1, K, N, 1, whatever the leading shape"""
+    from fresco_amd import _lib, ops
+    asked = []
+
+    class Lib:
+        @staticmethod
+        def vae_conv(x, x_img_stride, w, w_img_stride, bias, residual, out, n, H, W, cin, cout, ksize, up2, out_kind,
+                     bias_rows, ldo, stream):
+            asked.append((n, H, W, cin, cout, ksize, x_img_stride, w_img_stride, bool(bias), bool(residual), up2, out_kind,
+                          bias_rows, ldo))
+            return 0
+    monkeypatch.setattr(_lib, "load", lambda: Lib)
+    monkeypatch.setattr(ops, "_need_gpu", lambda *a: None)
+    monkeypatch.setattr(ops, "_stream", lambda: None)
+    x, w = torch.zeros(2, 3, 64, dtype=torch.float16), torch.zeros(96, 64, dtype=torch.float16)
+    out = ops.conv_rows(x, w)
+    assert out.shape == (2, 3, 96) and out.dtype == torch.float16 and out.is_contiguous()
+    assert asked == [(1, 6, 1, 64, 96, 1, 6 * 64, 0, False, False, 0, _lib.VAE_OUT_F16, 0, 96)]
+    r = torch.zeros(2, 3, 96, dtype=torch.float16)
+    assert ops.conv_rows(x, w, torch.zeros(96), residual=r).shape == (2, 3, 96)
+    assert asked[1] == (1, 6, 1, 64, 96, 1, 6 * 64, 0, True, True, 0, _lib.VAE_OUT_F16, 0, 96)
+    assert ops.conv_rows(x.view(6, 64), w).shape == (6, 96) and asked[2] == asked[0]
+    with pytest.raises(ValueError, match="conv_rows"):
+        ops.conv_rows(x, torch.zeros(96, 32, dtype=torch.float16))
+    with pytest.raises(ValueError, match="conv_rows"):
+        ops.conv_rows(x, torch.zeros(96 * 64, dtype=torch.float16))
+    with pytest.raises(ValueError, match="contiguous"):
+        ops.conv_rows(torch.zeros(2, 3, 128, dtype=torch.float16)[..., :64], w)
+    assert len(asked) == 3
