@@ -10,7 +10,8 @@ namespace {
 
 // One thread per (output pixel, four channels): 16 threads per pixel.  The window of output (oy, ox) starts at input
 // (2 oy + ORIGIN, 2 ox + ORIGIN) and is clipped to the map: what lies outside never wins (-inf), and every window holds at
-// least one pixel of the map (the launcher's output size sees to that).
+// least one pixel of the map (the launcher's output size sees to that).  A NaN in a window never wins either (fmaxf), so it
+// raises the range flag on its own: the planes stay finite and would be wrong without a word.
 //   ORIGIN = -1: MaxPool2d(3, 2, padding 1, ceil_mode=True) (EGNet);  ORIGIN = 0: MaxPool2dSame(3, 2) at even sizes (MiDaS)
 template <int ORIGIN>
 __global__ __launch_bounds__(256) void pool3s2_kernel(const float* __restrict__ x, float* __restrict__ out,
@@ -34,7 +35,10 @@ __global__ __launch_bounds__(256) void pool3s2_kernel(const float* __restrict__ 
                 if ((ORIGIN < 0 && ix < 0) || ix >= W) continue;
                 const floatx4 t = *reinterpret_cast<const floatx4*>(x + ((img * H + iy) * W + ix) * C + c);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], t[e]);
+                for (int e = 0; e < 4; ++e) {
+                    v[e] = fmaxf(v[e], t[e]);
+                    sat |= t[e] != t[e];  // fmaxf drops a NaN: the maximum stays finite, so the flag has to say it
+                }
             }
         }
         if (out) {

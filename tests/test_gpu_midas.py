@@ -167,9 +167,9 @@ def test_pool_windows_start_at_the_even_pixel(shape):
         assert not torch.equal(ceil_mode, want)  # (EGNet's pool starts one pixel earlier)
 
 
-def test_layernorm_768():
+def _layernorm_against_float64(M_, C):
+    """-> ((x, gamma, beta), fp32 rows, planes) of the both-outputs run, after its comparison with float64"""
     from fresco_amd import ops
-    M_, C = 37, 768  # 37 rows: ten workgroups of four, the last one with one row
     x = _randn(M_, C, seed=1) * 4.0 + _randn(M_, 1, seed=2) * 10.0
     gamma, beta = _randn(C, seed=3) * 0.3 + 1.0, _randn(C, seed=4)
     x64 = x.double()
@@ -179,35 +179,57 @@ def test_layernorm_768():
     bound = 2.0 ** -18 * (np.abs(ref - b64) + np.abs(b64)) + 2.0 ** -20 * x64.abs().max(1, keepdim=True)[0].numpy() * rstd \
         * np.abs(gamma.double().numpy())
     y, planes = ops.midas_layernorm(x.to(DEV), gamma.to(DEV), beta.to(DEV), eps=1e-6, want_f32=True, want_split=True)
-    _check("layernorm fp32", _np64(y), ref, bound)
-    _check("layernorm planes", _planes64(planes), ref, bound + 2.0 ** -21 * np.abs(ref))
+    _check("layernorm (%d, %d) fp32" % (M_, C), _np64(y), ref, bound)
+    _check("layernorm (%d, %d) planes" % (M_, C), _planes64(planes), ref, bound + 2.0 ** -21 * np.abs(ref))
+    return (x, gamma, beta), y, planes
 
 
-def test_tokens_and_head_merge():
+def test_layernorm_768():
+    _layernorm_against_float64(37, 768)  # 37 rows: ten workgroups of four, the last one with one row
+
+
+def _tokens_equal(n, L, C):
     from fresco_amd import ops
-    n, L, C, heads = 2, 25, 768, 12
     grid, cls, pos = _randn(n, L - 1, C, seed=5), _randn(C, seed=6), _randn(L, C, seed=7)
     tok = ops.midas_tokens(grid.to(DEV), cls.to(DEV), pos.to(DEV))
     want = torch.cat([cls.expand(n, 1, C), grid], 1) + pos
+    print("tokens (%d, %d, %d): %d values differ" % (n, L, C, int((tok.cpu() != want).sum())))
     assert torch.equal(tok.cpu(), want)
+
+
+def _head_merge_equal(n, L, heads):
+    from fresco_amd import ops
     o = _randn(heads * n, L, 64, seed=8) * 20.0
     merged, planes = ops.midas_head_merge(o.to(DEV), n, want_f32=True, want_split=True)
     want = o.view(heads, n, L, 64).permute(1, 2, 0, 3).reshape(n * L, heads * 64)
+    print("head merge (%d, %d, %d): %d values differ" % (heads * n, L, 64, int((merged.cpu() != want).sum())))
     assert torch.equal(merged.cpu(), want)
     ref = want.double().numpy()
     _check("head merge planes", _planes64(planes), ref, 2.0 ** -21 * np.abs(ref) + 2.0 ** -25)
 
 
-def test_readout_row_bias():
+def test_tokens_and_head_merge():
+    _tokens_equal(2, 25, 768)
+    _head_merge_equal(2, 25, 12)
+
+
+def _readout_against_float64(n, rows, C, spread=0.0):
+    """spread: how far apart the images' bias rows lie (row i is shifted by spread * (i - (n - 1) / 2)).
+    -> (x, rowbias, fp32 result, float64 reference, bound)"""
     from fresco_amd import ops
-    n, rows, C = 3, 24, 768
     x, rb = _randn(n * rows, C, seed=9) * 2.0, _randn(n, C, seed=10) * 2.0
+    rb = rb + spread * (torch.arange(n, dtype=torch.float32)[:, None] - 0.5 * (n - 1))
     t = x.double() + rb.double().repeat_interleave(rows, 0)
     ref = F.gelu(t).numpy()
     bound = 16 * E * (np.abs(t.numpy()) + np.abs(ref)) + 1e-6
     out, planes = ops.midas_rowbias_gelu(x.to(DEV), rb.to(DEV), rows, want_f32=True, want_split=True)
     _check("readout fp32", _np64(out), ref, bound)
     _check("readout planes", _planes64(planes), ref, bound + 2.0 ** -21 * np.abs(ref))
+    return x, rb, out, ref, bound
+
+
+def test_readout_row_bias():
+    _readout_against_float64(3, 24, 768)
 
 
 def _tail_frames():
@@ -223,21 +245,28 @@ def _tail_frames():
     return np.stack([f0, f1, f2])
 
 
-def test_tail_matches_the_numpy_restatement():
+def _tail_against_numpy(d, cond_dtype):
+    """ops.midas_tail of the frames d (n, H, W) float32 numpy: both uint8 maps equal to midas_model.tail frame by frame, the
+    condition equal to the torch expression -> (depth images, normal images)"""
     from fresco_amd import ops
-    d = _tail_frames()
-    dimg, nimg, cond = ops.midas_tail(_gpu(d), M.A, M.BG_TH, cond_dtype=torch.float16)
+    dimg, nimg, cond = ops.midas_tail(_gpu(d), M.A, M.BG_TH, cond_dtype=cond_dtype)
     for f in range(d.shape[0]):
         want_d, want_n = M.tail(d[f])
         got_d, got_n = dimg[f].cpu().numpy(), nimg[f].cpu().numpy()
-        print("tail frame %d: depth image differs in %d values, normal image in %d" % (f, (got_d != want_d).sum(),
-                                                                                      (got_n != want_n).sum()))
+        print("tail %s %s frame %d: depth image differs in %d values, normal image in %d"
+              % (d.shape, cond_dtype, f, (got_d != want_d).sum(), (got_n != want_n).sum()))
         assert np.array_equal(got_d, want_d) and np.array_equal(got_n, want_n)
+    want = (dimg.float()[:, None].repeat(1, 3, 1, 1) / 255.0 * 2 - 1) * 0.5 + 0.5
+    assert cond.dtype == cond_dtype and torch.equal(cond, want.to(cond_dtype))
+    return dimg, nimg
+
+
+def test_tail_matches_the_numpy_restatement():
+    d = _tail_frames()
+    dimg, nimg = _tail_against_numpy(d, torch.float16)
     assert d[0].min() > 3 and (dimg[1].cpu().numpy()[8:24, 10:30] == 0).all()
     assert (nimg[1].cpu().numpy()[10:22, 12:28] == (127, 127, 255)).all()      # masked: the flat normal
     assert not dimg[2].any() and (nimg[2].cpu().numpy() == (127, 127, 255)).all()  # the constant frame
-    want = (dimg.float()[:, None].repeat(1, 3, 1, 1) / 255.0 * 2 - 1) * 0.5 + 0.5
-    assert torch.equal(cond, want.half())
 
 
 # ---------------------------------------------------------------------------------------------------------------
