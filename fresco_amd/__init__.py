@@ -27,6 +27,8 @@ from .vae import (VAEDecoder, VAEEncoder, patch_vae, patch_vae_decode, patch_vae
 from .unet_resnet import UNetResnet, patch_unet_resnets, unpatch_unet_resnets
 from .unet_transformer import UNetTransformer, patch_unet_transformers, unpatch_unet_transformers
 from .unet_attention import UNetAttnProcessor, patch_unet_attention, unpatch_unet_attention
+from .unet_shell import (ControlNetCondEmbedding, UNetConvIn, UNetConvOut, UNetDownsample, UNetTimeEmbedding, UNetUpsample,
+                         UNetZeroConv, patch_unet_shell, unpatch_unet_shell)
 from .keyframe import (frame_errors, get_keyframe_ind, patch_keyframe_selection, resize_frames, resize_image, resize_size,
                        select_keyframes)
 from .paras import (correlation_matrices, forward_backward_consistency_check, get_flow_and_interframe_paras,
@@ -49,6 +51,8 @@ __all__ = [
     "UNetResnet", "patch_unet_resnets", "unpatch_unet_resnets",
     "UNetTransformer", "patch_unet_transformers", "unpatch_unet_transformers",
     "UNetAttnProcessor", "patch_unet_attention", "unpatch_unet_attention",
+    "UNetDownsample", "UNetUpsample", "UNetConvIn", "UNetConvOut", "UNetTimeEmbedding", "ControlNetCondEmbedding",
+    "UNetZeroConv", "patch_unet_shell", "unpatch_unet_shell",
     "get_keyframe_ind", "frame_errors", "select_keyframes", "resize_frames", "resize_image", "resize_size",
     "patch_keyframe_selection",
 ]

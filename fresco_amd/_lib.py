@@ -193,6 +193,16 @@ UNET_ATTN_SIGNATURES = {
     "unet_attention": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _i, _f, _i, _vp]),
 }
 
+# what is left of the UNet and the ControlNet around those (csrc/unet_shell.hip), declared in include/fresco_unet_shell.h:
+# named unet_* too
+UNET_SHELL_SIGNATURES = {
+    "unet_conv3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "unet_input": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "unet_time_linear": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+}
+UNET_ACT_NONE, UNET_ACT_SILU = 0, 1            # UNET_ACT_* of the header
+UNET_SRC_TIMESTEPS, UNET_SRC_SILU_ROWS = 0, 1  # UNET_SRC_* of the header
+
 _lib = None
 
 
@@ -211,7 +221,7 @@ def load():
         raise FrescoHipError("fresco_amd: cannot load %s: %s" % (LIB_PATH, e))
     for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
             + list(MIDAS_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(VAE_ENC_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) \
-            + list(UNET_TF_SIGNATURES.items()) + list(UNET_ATTN_SIGNATURES.items()):
+            + list(UNET_TF_SIGNATURES.items()) + list(UNET_ATTN_SIGNATURES.items()) + list(UNET_SHELL_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

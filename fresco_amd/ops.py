@@ -2036,3 +2036,75 @@ def vaeenc_sample(parameters, noise, scale=1.0):
     rc = _lib.load().vaeenc_sample(parameters.data_ptr(), noise.data_ptr(), out.data_ptr(), n, hh, ww, float(scale), _stream())
     _lib.check(rc, "vaeenc_sample(n=%d,h=%d,w=%d)" % (n, hh, ww))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# what is left of the UNet and the ControlNet (include/fresco_unet_shell.h): the padded 3 x 3 convolution at both strides,
+# the NCHW -> padded NHWC input, the time-embedding linear layers
+# ---------------------------------------------------------------------------------------------------------------------
+UNET_TIME_MAX_N = 64
+
+
+def unet_conv3(x, w, bias, stride=1, silu=False):
+    """Conv2d(cin, cout, 3, stride, padding 1) [+ SiLU]: x (n, H, W, cin) fp16 NHWC, w (cout, 9 cin) fp16 with k = (ky, kx, ci),
+    bias (cout) fp32 -> (n, (H - 1) // stride + 1, (W - 1) // stride + 1, cout) fp16 NHWC (unet_conv3)"""
+    _dense(x, "unet_conv3: x", torch.float16, align=16)
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError("unet_conv3: x must be (n, H, W, cin), got %s" % (tuple(x.shape),))
+    n, H, W, cin = x.shape
+    _dense(w, "unet_conv3: w", torch.float16, align=16)
+    if w.dim() != 2 or w.shape[0] == 0 or w.shape[1] != 9 * cin:
+        raise ValueError("unet_conv3: w must be (cout, %d), got %s" % (9 * cin, tuple(w.shape)))
+    cout = w.shape[0]
+    _dense(bias, "unet_conv3: bias", torch.float32, (cout,), align=16)
+    if stride not in (1, 2):
+        raise ValueError("unet_conv3: stride %r, only 1 or 2" % (stride,))
+    _need_gpu(x, w, bias)
+    out = torch.empty(n, (H - 1) // stride + 1, (W - 1) // stride + 1, cout, dtype=torch.float16, device=x.device)
+    rc = _lib.load().unet_conv3(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), n, H, W, cin, cout, stride,
+                                _lib.UNET_ACT_SILU if silu else _lib.UNET_ACT_NONE, _stream())
+    _lib.check(rc, "unet_conv3(n=%d,H=%d,W=%d,cin=%d,cout=%d,stride=%d,silu=%d)" % (n, H, W, cin, cout, stride, bool(silu)))
+    return out
+
+
+def unet_input(x, cpad=VAE_CIN_PAD):
+    """x (n, c, H, W) fp16 NCHW, c <= cpad -> (n, H, W, cpad) fp16 NHWC, channels c .. zero (unet_input)"""
+    _dense(x, "unet_input: x", torch.float16)
+    if x.dim() != 4 or x.numel() == 0 or x.shape[1] > cpad:
+        raise ValueError("unet_input: x must be (n, c <= %d, H, W), got %s" % (cpad, tuple(x.shape)))
+    _need_gpu(x)
+    n, c, H, W = x.shape
+    out = torch.empty(n, H, W, cpad, dtype=torch.float16, device=x.device)
+    rc = _lib.load().unet_input(x.data_ptr(), out.data_ptr(), n, c, H, W, cpad, _stream())
+    _lib.check(rc, "unet_input(n=%d,c=%d,H=%d,W=%d,cpad=%d)" % (n, c, H, W, cpad))
+    return out
+
+
+def unet_time_linear(src, weight, bias, want_sin=False):
+    """round16(bias + f(src) W^T) -> fp16 (n, cout), n <= 64 (unet_time_linear).  src fp32 (n): the timesteps, f their
+    sinusoid of K = weight.shape[1] columns ([cos | sin], flip_sin_to_cos, no frequency shift) rounded to fp16; with want_sin
+    -> (out, sinusoid fp16 (n, K)).  src fp16 (n, K): f = SiLU."""
+    _dense(weight, "unet_time_linear: weight", torch.float16, align=16)
+    if weight.dim() != 2 or weight.numel() == 0:
+        raise ValueError("unet_time_linear: weight must be (cout, K), got %s" % (tuple(weight.shape),))
+    cout, K = weight.shape
+    _dense(bias, "unet_time_linear: bias", torch.float32, (cout,))
+    if isinstance(src, torch.Tensor) and src.dtype == torch.float32:
+        _dense(src, "unet_time_linear: timesteps", torch.float32)
+        if src.dim() != 1 or src.numel() == 0:
+            raise ValueError("unet_time_linear: timesteps must be (n), got %s" % (tuple(src.shape),))
+        kind, n = _lib.UNET_SRC_TIMESTEPS, src.shape[0]
+    else:
+        _dense(src, "unet_time_linear: rows", torch.float16, align=16)
+        if src.dim() != 2 or src.numel() == 0 or src.shape[1] != K:
+            raise ValueError("unet_time_linear: rows must be (n, %d), got %s" % (K, tuple(src.shape)))
+        if want_sin:
+            raise ValueError("unet_time_linear: want_sin goes with timesteps")
+        kind, n = _lib.UNET_SRC_SILU_ROWS, src.shape[0]
+    _need_gpu(src, weight, bias)
+    out = torch.empty(n, cout, dtype=torch.float16, device=src.device)
+    sin = torch.empty(n, K, dtype=torch.float16, device=src.device) if want_sin else None
+    rc = _lib.load().unet_time_linear(src.data_ptr(), kind, weight.data_ptr(), bias.data_ptr(), out.data_ptr(), _ptr(sin), n, K,
+                                      cout, _stream())
+    _lib.check(rc, "unet_time_linear(kind=%d,n=%d,K=%d,cout=%d)" % (kind, n, K, cout))
+    return (out, sin) if want_sin else out
