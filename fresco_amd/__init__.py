@@ -29,6 +29,7 @@ from .unet_transformer import UNetTransformer, patch_unet_transformers, unpatch_
 from .unet_attention import UNetAttnProcessor, patch_unet_attention, unpatch_unet_attention
 from .unet_shell import (ControlNetCondEmbedding, UNetConvIn, UNetConvOut, UNetDownsample, UNetTimeEmbedding, UNetUpsample,
                          UNetZeroConv, patch_unet_shell, unpatch_unet_shell)
+from .text_encoder import CLIPTextEncoder, patch_text_encoder, unpatch_text_encoder
 from .keyframe import (frame_errors, get_keyframe_ind, patch_keyframe_selection, resize_frames, resize_image, resize_size,
                        select_keyframes)
 from .paras import (correlation_matrices, forward_backward_consistency_check, get_flow_and_interframe_paras,
@@ -53,6 +54,7 @@ __all__ = [
     "UNetAttnProcessor", "patch_unet_attention", "unpatch_unet_attention",
     "UNetDownsample", "UNetUpsample", "UNetConvIn", "UNetConvOut", "UNetTimeEmbedding", "ControlNetCondEmbedding",
     "UNetZeroConv", "patch_unet_shell", "unpatch_unet_shell",
+    "CLIPTextEncoder", "patch_text_encoder", "unpatch_text_encoder",
     "get_keyframe_ind", "frame_errors", "select_keyframes", "resize_frames", "resize_image", "resize_size",
     "patch_keyframe_selection",
 ]

@@ -203,6 +203,14 @@ UNET_SHELL_SIGNATURES = {
 UNET_ACT_NONE, UNET_ACT_SILU = 0, 1            # UNET_ACT_* of the header
 UNET_SRC_TIMESTEPS, UNET_SRC_SILU_ROWS = 0, 1  # UNET_SRC_* of the header
 
+# the CLIP text model's kernels (csrc/text.hip), declared in include/fresco_text.h: named clip_*, beside the pinned surfaces;
+# bound on the same handle
+TEXT_SIGNATURES = {
+    "clip_embed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "clip_attention": (_i, [_vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _f, _i, _vp]),
+    "clip_fc1": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i64, _vp]),
+}
+
 _lib = None
 
 
@@ -221,7 +229,8 @@ def load():
         raise FrescoHipError("fresco_amd: cannot load %s: %s" % (LIB_PATH, e))
     for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
             + list(MIDAS_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(VAE_ENC_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) \
-            + list(UNET_TF_SIGNATURES.items()) + list(UNET_ATTN_SIGNATURES.items()) + list(UNET_SHELL_SIGNATURES.items()):
+            + list(UNET_TF_SIGNATURES.items()) + list(UNET_ATTN_SIGNATURES.items()) + list(UNET_SHELL_SIGNATURES.items()) \
+            + list(TEXT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -1972,6 +1972,99 @@ def unet_attention(q, k, v, heads, scale, out=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the CLIP text model (include/fresco_text.h): token + position embedding, causal attention at head dim 64, quick-GELU fc1
+# ---------------------------------------------------------------------------------------------------------------------
+CLIP_ATTN_HEAD_DIM = 64
+CLIP_ATTN_MAX_L = 128
+CLIP_FC1_K_STEP, CLIP_FC1_N_STEP = 32, 64
+
+
+def clip_embed(ids, tok, pos):
+    """tok[ids] + pos[:L], fp16 + fp16 rounded once: ids int64 (B, L) dense, tok fp16 (vocab, C) and pos fp16 (>= L, C) dense
+    and read where they live, C a multiple of 8 -> fp16 (B, L, C).  An id outside [0, vocab) gives a NaN row (clip_embed)."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.dim() != 2 or ids.numel() == 0:
+        raise ValueError("clip_embed: ids must be an int64 (B, L) tensor, got %s"
+                         % ((ids.dtype, tuple(ids.shape)) if isinstance(ids, torch.Tensor) else type(ids).__name__,))
+    _dense(ids, "clip_embed: ids", torch.int64, align=8)
+    _dense(tok, "clip_embed: tok", torch.float16, align=16)
+    _dense(pos, "clip_embed: pos", torch.float16, align=16)
+    B, L = ids.shape
+    if tok.dim() != 2 or pos.dim() != 2 or tok.shape[0] == 0 or tok.shape[1] != pos.shape[1] or tok.shape[1] % 8 or tok.shape[1] == 0:
+        raise ValueError("clip_embed: tok (vocab, C) and pos (positions, C), C a multiple of 8, got %s and %s"
+                         % (tuple(tok.shape), tuple(pos.shape)))
+    if pos.shape[0] < L:
+        raise ValueError("clip_embed: %d tokens, the position table has %d rows" % (L, pos.shape[0]))
+    vocab, C = tok.shape
+    _need_gpu(ids, tok, pos)
+    out = torch.empty(B, L, C, dtype=torch.float16, device=tok.device)
+    rc = _lib.load().clip_embed(tok.data_ptr(), pos.data_ptr(), ids.data_ptr(), out.data_ptr(), B, L, C, vocab, _stream())
+    _lib.check(rc, "clip_embed(B=%d,L=%d,C=%d,vocab=%d)" % (B, L, C, vocab))
+    return out
+
+
+def clip_attention(q, k, v, heads, scale, out=None):
+    """causal softmax(scale q k^T) v per (sequence, head) at head dim 64: q, k, v (B, L, heads * 64) fp16 with ONE row stride
+    -- dense, or the column slices of one (B, L, 3 heads 64) q | k | v buffer; 1 <= L <= 128.  -> `out`, or a new dense
+    (B, L, heads * 64) fp16 tensor (clip_attention).  Nothing is copied or made dense: what the kernel would refuse raises
+    here."""
+    if not isinstance(q, torch.Tensor) or q.dim() != 3:
+        raise ValueError("clip_attention: q must be (B, L, C), got %s" % (tuple(q.shape) if isinstance(q, torch.Tensor) else type(q),))
+    heads = int(heads)
+    B, L, C = q.shape
+    if heads <= 0 or C != heads * CLIP_ATTN_HEAD_DIM:
+        raise NotImplementedError("clip_attention: head dim %s (%d channels on %d heads), only %d is built"
+                                  % (C // heads if heads > 0 and C % heads == 0 else "?", C, heads, CLIP_ATTN_HEAD_DIM))
+    if L > CLIP_ATTN_MAX_L:
+        raise NotImplementedError("clip_attention: %d tokens, at most %d" % (L, CLIP_ATTN_MAX_L))
+    if B > 65535 or heads > 65535:
+        raise NotImplementedError("clip_attention: %d sequences on %d heads, at most 65535 of each" % (B, heads))
+    if not (float(scale) > 0 and math.isfinite(float(scale))):
+        raise ValueError("clip_attention: scale %r must be positive and finite" % (scale,))
+    lds = [_uniform_rows(t, "clip_attention: " + nm, C, 3)[0] for t, nm in ((q, "q"), (k, "k"), (v, "v"))]
+    if k.shape != q.shape or v.shape != q.shape or len(set(lds)) != 1:
+        raise ValueError("clip_attention: q %s, k %s and v %s must have one shape and one row stride (got %s)"
+                         % (tuple(q.shape), tuple(k.shape), tuple(v.shape), lds))
+    if out is None:
+        out = torch.empty(B, L, C, dtype=torch.float16, device=q.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, L, C):
+        raise ValueError("clip_attention: out must be a fp16 (%d, %d, %d) tensor" % (B, L, C))
+    out_ld = _uniform_rows(out, "clip_attention: out", C, 3)[0]
+    _need_gpu(q, k, v, out)
+    rc = _lib.load().clip_attention(q.data_ptr(), k.data_ptr(), v.data_ptr(), lds[0], out.data_ptr(), out_ld, B, heads, L,
+                                    CLIP_ATTN_HEAD_DIM, float(scale), _lib.F16, _stream())
+    _lib.check(rc, "clip_attention(B=%d,H=%d,L=%d)" % (B, heads, L))
+    return out
+
+
+def clip_fc1(x, w, bias, out=None):
+    """quick_gelu(x w^T + bias), quick_gelu(g) = g sigmoid(1.702 g): x fp16 (..., K) dense, w fp16 (N, K) dense and read where
+    it lives, bias fp32 (N); K % 32 == 0 and N % 64 == 0 -> fp16 (..., N), or into `out`, a 2-D (M, N) tensor that may be a
+    column slice (clip_fc1)"""
+    _dense(x, "clip_fc1: x", torch.float16, align=16)
+    _dense(w, "clip_fc1: w", torch.float16, align=16)
+    if x.dim() < 2 or x.numel() == 0 or w.dim() != 2 or w.shape[1] != x.shape[-1] or w.shape[0] == 0:
+        raise ValueError("clip_fc1: x (..., K) and w (N, K), got %s and %s" % (tuple(x.shape), tuple(w.shape)))
+    K, N = x.shape[-1], w.shape[0]
+    if K % CLIP_FC1_K_STEP or N % CLIP_FC1_N_STEP:
+        raise ValueError("clip_fc1: K = %d must be a multiple of %d and N = %d of %d" % (K, CLIP_FC1_K_STEP, N, CLIP_FC1_N_STEP))
+    M = x.numel() // K
+    _dense(bias, "clip_fc1: bias", torch.float32, (N,), align=16)
+    if out is None:
+        out = torch.empty(x.shape[:-1] + (N,), dtype=torch.float16, device=x.device)
+        ldo = N
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float16 or out.dim() != 2 or tuple(out.shape) != (M, N):
+            raise ValueError("clip_fc1: out must be a fp16 (%d, %d) tensor" % (M, N))
+        ldo = N if M == 1 else out.stride(0)
+        if out.stride(1) != 1 or ldo < N or ldo % 4 or out.data_ptr() % 8:
+            raise ValueError("clip_fc1: out rows must be dense, 8-byte aligned and a multiple of 4 elements apart")
+    _need_gpu(x, w, bias, out)
+    rc = _lib.load().clip_fc1(x.data_ptr(), w.data_ptr(), bias.data_ptr(), out.data_ptr(), M, K, N, ldo, _stream())
+    _lib.check(rc, "clip_fc1(M=%d,K=%d,N=%d)" % (M, K, N))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # what the VAE encoder adds (include/fresco_vae_enc.h)
 # ---------------------------------------------------------------------------------------------------------------------
 def vaeenc_input(image, cpad=VAE_CIN_PAD):
