@@ -13,6 +13,7 @@ from .warp import Dilate, adaptive_instance_normalization, calc_mean_std, flow_w
 from .hook import apply_FRESCO_opt, disable_FRESCO_opt, patch_reference
 from .mapping import cross_frame_masks, get_mapping_ind, get_single_mapping_ind
 from .step import predict_x0, step
+from .loop import inference, tensor2numpy
 from .ebsynth import ebsynth_run, ebsynth_run_batch
 from . import blend
 from .flowcalc import FlowCalc, patch_flow_calc
@@ -39,7 +40,7 @@ __all__ = [
     "AttentionControl", "FRESCOAttnProcessor2_0", "apply_FRESCO_attn", "optimize_feature",
     "warp_tensor", "flow_warp", "adaptive_instance_normalization", "calc_mean_std", "Dilate", "apply_FRESCO_opt",
     "disable_FRESCO_opt", "patch_reference", "get_mapping_ind", "get_single_mapping_ind", "cross_frame_masks",
-    "step", "predict_x0", "get_flow_and_interframe_paras", "get_intraframe_paras", "interframe_paras_from_flows",
+    "step", "predict_x0", "inference", "tensor2numpy", "get_flow_and_interframe_paras", "get_intraframe_paras", "interframe_paras_from_flows",
     "forward_backward_consistency_check", "correlation_matrices",
     "ebsynth_run", "ebsynth_run_batch", "blend", "FlowCalc", "patch_flow_calc", "FrescoHipError", "LIB_PATH",
     "Fourier_filter", "register_free_upblock2d", "register_free_crossattn_upblock2d", "apply_freeu", "patch_free_lunch",

@@ -211,6 +211,14 @@ TEXT_SIGNATURES = {
     "clip_fc1": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i64, _vp]),
 }
 
+# the denoising loop's glue (csrc/loop.hip), declared in include/fresco_loop.h: named loop_*, beside the pinned surfaces; bound
+# on the same handle.  The version string did not move for them: a library built before them is refused because it does not
+# export them, and the error names the symbol
+LOOP_SIGNATURES = {
+    "loop_update": (_i, [_vp] * 8 + [_i, _i64, _i64, _i64, _i] + [_f] * 6 + [_i, _vp]),
+    "loop_image_to_frames": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+}
+
 _lib = None
 
 
@@ -230,7 +238,7 @@ def load():
     for name, (res, args) in list(SIGNATURES.items()) + list(KEYFRAME_SIGNATURES.items()) + list(RESIZE_SIGNATURES.items()) \
             + list(MIDAS_SIGNATURES.items()) + list(VAE_SIGNATURES.items()) + list(VAE_ENC_SIGNATURES.items()) + list(UNET_SIGNATURES.items()) \
             + list(UNET_TF_SIGNATURES.items()) + list(UNET_ATTN_SIGNATURES.items()) + list(UNET_SHELL_SIGNATURES.items()) \
-            + list(TEXT_SIGNATURES.items()):
+            + list(TEXT_SIGNATURES.items()) + list(LOOP_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -11,6 +11,7 @@
 // a smooth flow stay within a few cache lines of the plane).
 #include "common.h"
 #include "flow_consistency.h"
+#include "ddpm_math.h"
 
 namespace fresco {
 
@@ -330,9 +331,9 @@ __global__ __launch_bounds__(256) void ddpm_x0_kernel(const T* __restrict__ xt, 
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     float e = (float)eps_u[i];
-    if (eps_c) e = e + guidance * ((float)eps_c[i] - e);
+    if (eps_c) e = ddpm_guided_eps(e, (float)eps_c[i], guidance);
     if (eps_out) eps_out[i] = (T)e;
-    x0[i] = (T)(((float)xt[i] - sqrt_beta * e) / sqrt_alpha);
+    x0[i] = (T)ddpm_pred_x0((float)xt[i], e, sqrt_beta, sqrt_alpha);
 }
 
 template <typename T>
@@ -342,8 +343,7 @@ __global__ __launch_bounds__(256) void ddpm_prev_kernel(const T* __restrict__ x0
                                                          float sigma) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float mean = c_x0 * (float)x0[i] + c_xt * (float)xt[i];
-    out[i] = (T)(mean + sigma * (float)noise[i % noise_period]);
+    out[i] = (T)ddpm_posterior((float)x0[i], (float)xt[i], (float)noise[i % noise_period], c_x0, c_xt, sigma);
 }
 }  // namespace fresco
 

@@ -13,7 +13,9 @@ collected decoder features to the tuple output -- so it works with any diffusers
   * if timestep in steps and i in layers: optimize_feature(...), then warp_tensor(..., 2) when a
     saliency map is given                                                        (775-779)
 `timestep in steps` is evaluated once per forward on the host (one sync instead of the reference's
-four tensor membership tests per UNet pass).
+four tensor membership tests per UNet pass).  fresco_amd.inference knows every step's timestep as a host
+integer and hands it over before each UNet call (`_OptState.host_timestep`, consumed by that call's
+latch), so under it the latch reads no device tensor at all.
 """
 import torch
 
@@ -38,13 +40,18 @@ class _OptState:
         self.saliency = saliency
         self.shard = None  # fresco_amd.dist.FrameShard: set on unet._fresco_opt_state for frame-parallel runs
         self.active = False
+        self.host_timestep = None  # the next UNet call's timestep as a host int (fresco_amd/loop.py), or None
         self.up_samples = ()
         self.handles = []
 
     def latch(self, timestep):
         self.up_samples = ()
         self.active = False
+        host, self.host_timestep = self.host_timestep, None  # (one call's worth: a later direct call reads its own argument)
         if self.step_set:
+            if host is not None:
+                self.active = host in self.step_set
+                return
             t = int(timestep) if not torch.is_tensor(timestep) or timestep.numel() == 1 else None
             if t is None:
                 raise ValueError("fresco_amd hook: one timestep per UNet call expected")
