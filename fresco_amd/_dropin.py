@@ -18,23 +18,35 @@ def refusal(who, name, why):
     return NotImplementedError("%s: %s; there is no fallback to PyTorch" % (who, (name + " " + why).lstrip()))
 
 
-def check_all(who, found, cls):
+DTYPE_NAMES = {torch.float16: "fp16", torch.bfloat16: "bf16"}
+
+
+def dtype_name(who, dtype):
+    """"fp16" / "bf16" for a drop-in's `dtype` argument (the pipeline's torch_dtype); anything else is refused"""
+    if dtype not in DTYPE_NAMES:
+        raise TypeError("%s: dtype must be torch.float16 or torch.bfloat16, got %s" % (who, dtype))
+    return DTYPE_NAMES[dtype]
+
+
+def check_all(who, found, cls, dtype=torch.float16):
     """refuse, by name, the first of `found` that cls.refusal objects to: call it before anything is patched"""
     for name, m in found:
-        why = cls.refusal(m)
+        why = cls.refusal(m) if dtype == torch.float16 else cls.refusal(m, dtype=dtype)
         if why:
             raise refusal(who, name or "the model", why)
 
 
-def patch(model, cls, parts, who, attr, memory_format):
+def patch(model, cls, parts, who, attr, memory_format, dtype=torch.float16):
     """bind cls.from_module(m) as `forward` (and under `attr`) in the __dict__ of every module of `model` that has `parts`;
-    every module is checked first.  The modules' own methods stay on their class.  -> the number of modules patched"""
+    every module is checked first.  The modules' own methods stay on their class.  dtype: the pipeline's dtype; a drop-in
+    that has no bf16 form is not handed the argument (the default).  -> the number of modules patched"""
     check_format(who, memory_format)
+    extra = {} if dtype == torch.float16 else {"dtype": dtype}
     unpatch(model, attr)
     found = find(model, parts)
-    check_all(who, found, cls)
+    check_all(who, found, cls, dtype)
     for name, m in found:
-        native = cls.from_module(m, memory_format=memory_format, name=name)
+        native = cls.from_module(m, memory_format=memory_format, name=name, **extra)
         m.__dict__[attr] = native
         m.__dict__["forward"] = native
     return len(found)
@@ -51,10 +63,11 @@ def unpatch(model, attr):
     return count
 
 
-def intake(state_dict, prefix, need, who, default):
+def intake(state_dict, prefix, need, who, default, dtype=torch.float16):
     """the entries of `state_dict` under `prefix`, without it -> (sd, what), `what` the prefix of the caller's messages
     ("<who>: <prefix, or `default`>").  Every name in `need` must be there (the first four missing ones are reported) and
-    fp16.  Entries that `need` does not name are kept as they are: check_shapes decides about them."""
+    of `dtype` (fp16 unless the caller has a bf16 form).  Entries that `need` does not name are kept as they are: check_shapes
+    decides about them."""
     if prefix and not prefix.endswith("."):
         prefix += "."
     sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
@@ -63,8 +76,10 @@ def intake(state_dict, prefix, need, who, default):
     if missing:
         raise ValueError("%s: missing parameters %s" % (what, missing[:4]))
     for k in need:
-        if sd[k].dtype != torch.float16:
-            raise TypeError("%s: fp16 parameters only (%s is %s); bf16 and fp32 UNets are not supported" % (what, k, sd[k].dtype))
+        if sd[k].dtype != dtype:
+            if dtype == torch.float16:
+                raise TypeError("%s: fp16 parameters only (%s is %s); bf16 and fp32 UNets are not supported" % (what, k, sd[k].dtype))
+            raise TypeError("%s: %s parameters only with dtype=%s (%s is %s)" % (what, DTYPE_NAMES[dtype], dtype, k, sd[k].dtype))
     return sd, what
 
 

@@ -164,6 +164,8 @@ VAE_SIGNATURES = {
     "vae_softmax": (_i, [_vp, _vp, _i64, _i, _i64, _i64, _f, _vp]),
 }
 VAE_OUT_F16, VAE_OUT_F32, VAE_OUT_F16_NCHW = 0, 1, 2  # VAE_OUT_* of the header
+# VAE_ELEM_BF16 (OR-ed into vae_conv's out_kind) = UNET_ELEM_BF16 (into unet_groupnorm's silu word): bf16 operands
+ELEM_BF16 = 0x100
 
 # what the VAE encoder adds to them (csrc/vae_enc.hip), declared in include/fresco_vae_enc.h: named vaeenc_*
 VAE_ENC_SIGNATURES = {
@@ -179,6 +181,7 @@ UNET_SIGNATURES = {
     "unet_groupnorm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _f, _i, _vp]),
     "unet_groupnorm_lds_form": (_i, [_i, _i, _i]),
     "unet_temb": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "unet_temb_dt": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),   # + dtype: F16 or BF16
 }
 
 # what the UNet transformer blocks add to them (csrc/unet_tf.hip), declared in include/fresco_unet_tf.h: named unet_* too

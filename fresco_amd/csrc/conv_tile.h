@@ -1,5 +1,6 @@
-// The plain-fp16 implicit-GEMM convolution tile that vae.hip (vae_conv_kernel<TAPS>) and vae_enc.hip
-// (vaeenc_conv_down_kernel) share.  Each kernel keeps how its pixels reach LDS, its output kinds, and the MFMA step and
+// The plain-fp16 implicit-GEMM convolution tile that vae.hip (vae_conv_kernel<TAPS, T> of vae_conv_body.h, which net_bf16.hip
+// instantiates for bf16 too: nothing below but the MFMA and the fragment types depends on the 2-byte element type) and
+// vae_enc.hip (vaeenc_conv_down_kernel) share.  Each kernel keeps how its pixels reach LDS, its output kinds, and the MFMA step and
 // half4_t store written out (see below): whoever changes the swizzle, the fragment layout or the channel map changes it here.
 //
 // Plain fp16 operands, one v_mfma_f32_32x32x16_f16 per product, fp32 accumulators.  A workgroup of four waves owns 128
@@ -29,6 +30,8 @@ namespace fresco {
 constexpr int CT_BM = 128, CT_BN = 128, CT_BK = 32;  // pixels, channels, K chunk of a tile
 constexpr int CT_TH = 8, CT_TW = 16;                 // the 128 pixels of a tile in a plane
 constexpr int CT_B_BYTES = 8 * 1024;                 // 128 weight rows of 64 bytes
+// (vae_conv_body.h's window slot, here so that vae.hip and net_bf16.hip add up one pair of constants)
+constexpr int VC_A_BYTES = 12 * 1024;  // 12 pieces of 64 lanes x 16 bytes = 192 window rows of 64 bytes (180 used)
 
 namespace {
 // what the LDS-DMA reads where there is nothing to read
@@ -59,8 +62,10 @@ __device__ __forceinline__ void ct_gemm_slot(int wave, int p, int lane, int& R, 
     pc = (slot & 3) ^ ((R >> 2) & 3);
 }
 
-// weight row co0 + R at column 0 (w: this image's (cout, K) matrix), null for rows >= cout
-__device__ __forceinline__ const char* ct_weight_src(const half_t* w, int co0, int R, int pc, int cout, int K) {
+// weight row co0 + R at column 0 (w: this image's (cout, K) matrix of 2-byte elements), null for rows >= cout
+template <typename T>
+__device__ __forceinline__ const char* ct_weight_src(const T* w, int co0, int R, int pc, int cout, int K) {
+    static_assert(sizeof(T) == 2, "a piece is eight 2-byte elements");
     return co0 + R < cout ? reinterpret_cast<const char*>(w + (int64_t)(co0 + R) * K + pc * 8) : nullptr;
 }
 

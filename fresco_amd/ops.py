@@ -1665,6 +1665,25 @@ def midas_tail(depth, a, bg_th, cond_dtype=None):
 # the VAE decoder's kernels (include/fresco_vae.h): fp16 NHWC activations, plain-fp16 implicit-GEMM convolutions
 # ---------------------------------------------------------------------------------------------------------------------
 VAE_GN_CHANNELS = (128, 256, 512)
+# vae_conv, unet_groupnorm and unet_temb take fp16 or bf16 operands: the flag OR-ed into the C call's int argument
+# (VAE_ELEM_BF16 / UNET_ELEM_BF16 of the headers) and unet_temb_dt's dtype code
+_ELEM16_FLAG = {torch.float16: 0, torch.bfloat16: _lib.ELEM_BF16}
+_ELEM16_CODE = {torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+
+
+def _elem16(x, name):
+    """the element type of a call, taken from its first operand: fp16 or bf16"""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("%s: expected a tensor, got %s" % (name, type(x).__name__))
+    if x.dtype not in _ELEM16_FLAG:
+        raise TypeError("%s: dtype %s, expected torch.float16 or torch.bfloat16" % (name, x.dtype))
+    return x.dtype
+
+
+def _same_elem(t, name, et, first):
+    """a 16-bit operand of another type than the call's first one: both types are named"""
+    if isinstance(t, torch.Tensor) and t.dtype != et and t.dtype in _ELEM16_FLAG:
+        raise TypeError("%s: dtype %s, but %s is %s: one element type per call" % (name, t.dtype, first, et))
 VAE_CIN_PAD = 32  # conv_in's four input channels padded to the convolution's K chunk
 
 
@@ -1686,13 +1705,15 @@ def vae_input(z, weight, bias, cpad=VAE_CIN_PAD):
 
 def vae_conv(x, w, bias, n, H, W, cin, cout, ksize, up2=False, residual=None, out_kind=_lib.VAE_OUT_F16, x_img_stride=None,
              w_img_stride=0, bias_rows=False, ldo=None, out=None):
-    """out = [residual +] conv(x) + bias on the plain-fp16 implicit GEMM (vae_conv of include/fresco_vae.h).  x: fp16, ksize 3:
-    (n, H, W, cin) NHWC, or (n, H / 2, W / 2, cin) with up2; ksize 1: H * W rows of cin per image, x_img_stride elements
-    apart (default H W cin; 0 = shared).  w: fp16 (cout, ksize^2 cin) with k = (ky, kx, ci), or n such matrices w_img_stride
-    elements apart.  -> `out`, or a new (n, H, W, cout) fp16 / fp32 tensor of row stride ldo, (n, cout, H, W) for
-    VAE_OUT_F16_NCHW."""
-    _dense(x, "vae_conv: x", torch.float16, align=16)
-    _dense(w, "vae_conv: w", torch.float16, align=16)
+    """out = [residual +] conv(x) + bias on the plain 16-bit implicit GEMM (vae_conv of include/fresco_vae.h).  x: fp16 or
+    bf16 (the element type of the call: w, residual and a 16-bit out must have it too), ksize 3: (n, H, W, cin) NHWC, or
+    (n, H / 2, W / 2, cin) with up2; ksize 1: H * W rows of cin per image, x_img_stride elements apart (default H W cin;
+    0 = shared).  w: (cout, ksize^2 cin) with k = (ky, kx, ci), or n such matrices w_img_stride elements apart.  -> `out`,
+    or a new (n, H, W, cout) tensor of x's type / fp32 (VAE_OUT_F32) of row stride ldo, (n, cout, H, W) for VAE_OUT_F16_NCHW."""
+    et = _elem16(x, "vae_conv: x")
+    _dense(x, "vae_conv: x", et, align=16)
+    _same_elem(w, "vae_conv: w", et, "x")
+    _dense(w, "vae_conv: w", et, align=16)
     if bias is not None:
         _dense(bias, "vae_conv: bias", torch.float32, align=16)
     K = ksize * ksize * cin
@@ -1706,7 +1727,7 @@ def vae_conv(x, w, bias, n, H, W, cin, cout, ksize, up2=False, residual=None, ou
     if bias is not None and bias.numel() < (H * W if bias_rows else cout):
         raise ValueError("vae_conv: bias of %d values" % bias.numel())
     ldo = cout if ldo is None else int(ldo)
-    odt = torch.float32 if out_kind == _lib.VAE_OUT_F32 else torch.float16
+    odt = torch.float32 if out_kind == _lib.VAE_OUT_F32 else et
     if out is None:
         if out_kind == _lib.VAE_OUT_F16_NCHW:
             out = torch.empty(n, cout, H, W, dtype=odt, device=x.device)
@@ -1715,24 +1736,28 @@ def vae_conv(x, w, bias, n, H, W, cin, cout, ksize, up2=False, residual=None, ou
         else:
             out = torch.empty(n, H * W, ldo, dtype=odt, device=x.device)
     else:
+        if odt is et:
+            _same_elem(out, "vae_conv: out", et, "x")
         _dense(out, "vae_conv: out", odt, align=8)
     if out.numel() < n * H * W * (cout if out_kind == _lib.VAE_OUT_F16_NCHW else ldo):
         raise ValueError("vae_conv: out holds %d elements" % out.numel())
     if residual is not None:
-        _dense(residual, "vae_conv: residual", torch.float16, align=8)
+        _same_elem(residual, "vae_conv: residual", et, "x")
+        _dense(residual, "vae_conv: residual", et, align=8)
         if residual.numel() < n * H * W * ldo:
             raise ValueError("vae_conv: residual holds %d elements" % residual.numel())
     _need_gpu(x, w, bias, residual, out)
     rc = _lib.load().vae_conv(x.data_ptr(), x_img_stride, w.data_ptr(), w_img_stride, _ptr(bias), _ptr(residual),
-                              out.data_ptr(), n, H, W, cin, cout, ksize, int(bool(up2)), out_kind, int(bool(bias_rows)), ldo,
-                              _stream())
+                              out.data_ptr(), n, H, W, cin, cout, ksize, int(bool(up2)), out_kind | _ELEM16_FLAG[et],
+                              int(bool(bias_rows)), ldo, _stream())
     _lib.check(rc, "vae_conv(n=%d,H=%d,W=%d,cin=%d,cout=%d,k=%d,up2=%d,kind=%d)" % (n, H, W, cin, cout, ksize, up2, out_kind))
     return out
 
 
 def conv_rows(x, w, bias=None, residual=None):
-    """a linear layer on vae_conv's 1 x 1 form, all rows of all images as ONE run of rows (n = 1, H = rows, W = 1): x fp16
-    (..., K) dense, w fp16 (N, K) packed, bias fp32 (N), residual fp16 (..., N) -> [residual +] x w^T + bias, fp16 (..., N)"""
+    """a linear layer on vae_conv's 1 x 1 form, all rows of all images as ONE run of rows (n = 1, H = rows, W = 1): x fp16 or
+    bf16 (..., K) dense, w (N, K) packed and residual (..., N) of x's type, bias fp32 (N) -> [residual +] x w^T + bias, of
+    x's type (..., N)"""
     K = x.shape[-1]
     if w.dim() != 2 or w.shape[1] != K:     # what vae_conv cannot see: it is handed K; everything else it checks itself
         raise ValueError("conv_rows: x (..., K) and w (N, K), got %s and %s" % (tuple(x.shape), tuple(w.shape)))
@@ -1795,9 +1820,10 @@ def unet_gn_channels(C):
 
 
 def unet_groupnorm(x, gamma, beta, eps=1e-5, silu=False, addend=None):
-    """[SiLU] GroupNorm(32, C, eps)(x + addend) on x (n, ..., C) fp16 NHWC, C a multiple of 64 in 64 .. 2560; gamma / beta fp32
-    (C); addend: fp32 (n, C), one term per image and channel, or None -> fp16 like x (unet_groupnorm)"""
-    _dense(x, "unet_groupnorm: x", torch.float16, align=16)
+    """[SiLU] GroupNorm(32, C, eps)(x + addend) on x (n, ..., C) fp16 or bf16 NHWC, C a multiple of 64 in 64 .. 2560; gamma /
+    beta fp32 (C); addend: fp32 (n, C), one term per image and channel, or None -> like x, in x's type (unet_groupnorm)"""
+    et = _elem16(x, "unet_groupnorm: x")
+    _dense(x, "unet_groupnorm: x", et, align=16)
     if x.dim() < 3 or x.numel() == 0 or not unet_gn_channels(x.shape[-1]):
         raise ValueError("unet_groupnorm: x must be (n, ..., C), C a multiple of %d in %d .. %d, got %s"
                          % (UNET_GN_STEP, UNET_GN_MIN, UNET_GN_MAX, tuple(x.shape)))
@@ -1813,19 +1839,21 @@ def unet_groupnorm(x, gamma, beta, eps=1e-5, silu=False, addend=None):
     ws = _unet_gn_ws.get(nbytes, x.device)
     y = torch.empty_like(x)
     rc = lib.unet_groupnorm(x.data_ptr(), _ptr(addend), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), ws.data_ptr(), nbytes,
-                            n, P, C, float(eps), int(bool(silu)), _stream())
+                            n, P, C, float(eps), int(bool(silu)) | _ELEM16_FLAG[et], _stream())
     _lib.check(rc, "unet_groupnorm(n=%d,P=%d,C=%d)" % (n, P, C))
     return y
 
 
 def unet_temb(temb, weight, bias, conv_bias):
-    """bias + conv_bias + SiLU(temb) W^T: temb fp16 (n, K), n <= 64, weight fp16 (cout, K), bias / conv_bias fp32 (cout) -> fp32
-    (n, cout) (unet_temb)"""
-    _dense(temb, "unet_temb: temb", torch.float16, align=16)
+    """bias + conv_bias + SiLU(temb) W^T: temb fp16 or bf16 (n, K), n <= 64, weight (cout, K) of temb's type, bias / conv_bias
+    fp32 (cout) -> fp32 (n, cout) (unet_temb_dt)"""
+    et = _elem16(temb, "unet_temb: temb")
+    _dense(temb, "unet_temb: temb", et, align=16)
     if temb.dim() != 2 or temb.numel() == 0:
         raise ValueError("unet_temb: temb must be (n, K), got %s" % (tuple(temb.shape),))
     n, K = temb.shape
-    _dense(weight, "unet_temb: weight", torch.float16, align=16)
+    _same_elem(weight, "unet_temb: weight", et, "temb")
+    _dense(weight, "unet_temb: weight", et, align=16)
     if weight.dim() != 2 or weight.shape[1] != K or weight.shape[0] == 0:
         raise ValueError("unet_temb: weight must be (cout, %d), got %s" % (K, tuple(weight.shape)))
     cout = weight.shape[0]
@@ -1833,8 +1861,8 @@ def unet_temb(temb, weight, bias, conv_bias):
     _dense(conv_bias, "unet_temb: conv_bias", torch.float32, (cout,))
     _need_gpu(temb, weight, bias, conv_bias)
     out = torch.empty(n, cout, dtype=torch.float32, device=temb.device)
-    rc = _lib.load().unet_temb(temb.data_ptr(), weight.data_ptr(), bias.data_ptr(), conv_bias.data_ptr(), out.data_ptr(), n, K,
-                               cout, _stream())
+    rc = _lib.load().unet_temb_dt(temb.data_ptr(), weight.data_ptr(), bias.data_ptr(), conv_bias.data_ptr(), out.data_ptr(), n,
+                                  K, cout, _ELEM16_CODE[et], _stream())
     _lib.check(rc, "unet_temb(n=%d,K=%d,cout=%d)" % (n, K, cout))
     return out
 

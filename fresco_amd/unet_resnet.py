@@ -1,7 +1,11 @@
-"""ResnetBlock2D of the SD-1.5 UNet and ControlNet on this package's kernels, for fp16 pipelines.
+"""ResnetBlock2D of the SD-1.5 UNet and ControlNet on this package's kernels, for fp16 and bf16 pipelines (DESIGN.md
+section 19).
 
 `UNetResnet(state_dict, prefix, cin, cout)` packs one block's weights; `UNetResnet.from_module(block)` reads them from a
-module; `patch_unet_resnets(model)` replaces `forward` on every resnet block of `pipe.unet` or of the ControlNet.  A call is
+module; `patch_unet_resnets(model)` replaces `forward` on every resnet block of `pipe.unet` or of the ControlNet.  All three
+take `dtype=` (default torch.float16): the pipeline's dtype, as `torch_dtype=` is in `from_pretrained`; with
+`dtype=torch.bfloat16` the parameters, x, temb and the result are bf16 and the same launches run the kernels' bf16 forms
+(csrc/net_bf16.hip; the norms' scales and every bias are fp32 either way).  A call is
 six launches into libfresco_hip.so, seven with a shortcut (include/fresco_unet.h, include/fresco_vae.h):
 
   1. unet_groupnorm(x, SiLU)                    norm1 + swish
@@ -13,14 +17,14 @@ six launches into libfresco_hip.so, seven with a shortcut (include/fresco_unet.h
 
 This is diffusers 0.19.3's `ResnetBlock2D.forward` with 32 groups, swish, `time_embedding_norm="default"`,
 `output_scale_factor=1.0`, no up or down sampling inside the block and a 1 x 1 `conv_shortcut` iff cin != cout.  Against
-PyTorch's fp16 module the intermediate `conv1 + temb` is rounded to fp16 once (conv1's output without its bias) instead of
-twice: bias and time embedding are added in fp32 inside the second norm.
+PyTorch's fp16 (bf16) module the intermediate `conv1 + temb` is rounded to fp16 (bf16) once (conv1's output without its bias)
+instead of twice: bias and time embedding are added in fp32 inside the second norm.
 
 Layout: tensors are logical NCHW, as diffusers passes them, and NHWC in memory.  An input that is `channels_last`-contiguous
 is read in place, any other is converted once; the output is `(n, cout, H, W)` in `torch.channels_last` unless
 `memory_format=torch.contiguous_format` asks for the plain layout (one more copy).
 
-There is no fallback: a block outside this configuration, not fp16 or not on the GPU raises.  diffusers is not installed where
+There is no fallback: a block outside this configuration, not of `dtype` or not on the GPU raises.  diffusers is not installed where
 this package is built and tested: the parameter names and the forward come from its published source (models/resnet.py) and
 are UNVERIFIED against the real module.
 """
@@ -40,8 +44,10 @@ class UNetResnet:
     """One ResnetBlock2D (cin -> cout channels, a time embedding of temb_channels) on HIP kernels."""
 
     def __init__(self, state_dict, prefix, cin, cout, temb_channels=1280, eps=1e-5, device=None,
-                 memory_format=torch.channels_last):
-        sd, what = _dropin.intake(state_dict, prefix, [p + s for p in PARTS for s in (".weight", ".bias")], _WHO, "the block")
+                 memory_format=torch.channels_last, dtype=torch.float16):
+        self.dtype, self.dtype_name = dtype, _dropin.dtype_name(_WHO, dtype)
+        sd, what = _dropin.intake(state_dict, prefix, [p + s for p in PARTS for s in (".weight", ".bias")], _WHO, "the block",
+                                  dtype=dtype)
         if not (ops.unet_gn_channels(cin) and ops.unet_gn_channels(cout)):
             raise NotImplementedError("%s: %d -> %d channels; the GroupNorm kernel takes multiples of %d in %d .. %d"
                                       % (what, cin, cout, ops.UNET_GN_STEP, ops.UNET_GN_MIN, ops.UNET_GN_MAX))
@@ -61,24 +67,25 @@ class UNetResnet:
         self.device, self.memory_format = dev, memory_format
         self.g1, self.b1 = _f32(sd["norm1.weight"], dev), _f32(sd["norm1.bias"], dev)
         self.g2, self.b2 = _f32(sd["norm2.weight"], dev), _f32(sd["norm2.bias"], dev)
-        self.w1 = pack_conv_weight(sd["conv1.weight"]).to(dev)
+        self.w1 = pack_conv_weight(sd["conv1.weight"], dtype=dtype).to(dev)
         self.cb1 = _f32(sd["conv1.bias"], dev)
-        self.wt = sd["time_emb_proj.weight"].detach().to(dev, torch.float16).contiguous()
+        self.wt = sd["time_emb_proj.weight"].detach().to(dev, dtype).contiguous()
         self.bt = _f32(sd["time_emb_proj.bias"], dev)
-        self.w2 = pack_conv_weight(sd["conv2.weight"]).to(dev)
+        self.w2 = pack_conv_weight(sd["conv2.weight"], dtype=dtype).to(dev)
         self.cb2 = _f32(sd["conv2.bias"], dev)
-        self.ws = pack_conv_weight(sd["conv_shortcut.weight"]).to(dev) if has else None
+        self.ws = pack_conv_weight(sd["conv_shortcut.weight"], dtype=dtype).to(dev) if has else None
         self.cbs = _f32(sd["conv_shortcut.bias"], dev) if has else None
 
     @staticmethod
-    def refusal(block):
-        """why `block` (a module with PARTS) is outside the supported configuration, or None"""
+    def refusal(block, dtype=torch.float16):
+        """why `block` (a module with PARTS) is outside the supported configuration of a `dtype` pipeline, or None"""
+        want = _dropin.dtype_name(_WHO, dtype)
         for part in PARTS:
             if getattr(block, part, None) is None:
                 return "has no %s" % part
         dtypes = {p.dtype for p in block.parameters()}
-        if dtypes != {torch.float16}:
-            return "is %s, fp16 blocks only" % "/".join(sorted(str(d) for d in dtypes))
+        if dtypes != {dtype}:
+            return "is %s, %s blocks only" % ("/".join(sorted(str(d) for d in dtypes)), want)
         ten = getattr(block, "time_embedding_norm", "default")
         if ten != "default":
             return "time_embedding_norm is %r, only \"default\"" % (ten,)
@@ -105,23 +112,24 @@ class UNetResnet:
         return None
 
     @classmethod
-    def from_module(cls, block, device=None, memory_format=torch.channels_last, name="the block"):
-        why = cls.refusal(block)
+    def from_module(cls, block, device=None, memory_format=torch.channels_last, name="the block", dtype=torch.float16):
+        why = cls.refusal(block, dtype)
         if why:
             raise _dropin.refusal(_WHO, name, why)
         w1 = block.conv1.weight
         return cls(block.state_dict(), "", int(w1.shape[1]), int(w1.shape[0]), int(block.time_emb_proj.weight.shape[1]),
-                   float(block.norm1.eps), device=device, memory_format=memory_format)
+                   float(block.norm1.eps), device=device, memory_format=memory_format, dtype=dtype)
 
     @torch.no_grad()
     def __call__(self, x, temb, *args, memory_format=None, taps=None, **kwargs):
-        """x (n, cin, H, W) fp16 on the GPU, temb (n, temb_channels) fp16 -> (n, cout, H, W) fp16.  taps: a dict that
-        receives "conv1_temb" (n, H, W, cout) fp32 = conv1's fp16 output + the addend, what the second norm normalises."""
+        """x (n, cin, H, W) on the GPU and temb (n, temb_channels), both of the block's dtype (fp16 or bf16) -> (n, cout, H, W)
+        of that dtype.  taps: a dict that receives "conv1_temb" (n, H, W, cout) fp32 = conv1's 16-bit output + the addend,
+        what the second norm normalises."""
         for t, name in ((x, "x"), (temb, "temb")):
             if not isinstance(t, torch.Tensor):
                 raise TypeError("fresco_amd.unet_resnet: %s must be a tensor" % name)
-            if t.dtype != torch.float16:
-                raise TypeError("fresco_amd.unet_resnet: fp16 %s only (got %s)" % (name, t.dtype))
+            if t.dtype != self.dtype:
+                raise TypeError("fresco_amd.unet_resnet: %s %s only (got %s)" % (self.dtype_name, name, t.dtype))
         if x.dim() != 4 or x.shape[1] != self.cin or x.numel() == 0:
             raise ValueError("fresco_amd.unet_resnet: x must be (n, %d, H, W), got %s" % (self.cin, tuple(x.shape)))
         n, _, H, W = x.shape
@@ -141,12 +149,14 @@ class UNetResnet:
         return _dropin.nchw(ops.vae_conv(h, self.w2, self.cb2, n, H, W, self.cout, self.cout, 3, residual=skip), fmt)
 
 
-def patch_unet_resnets(model, memory_format=torch.channels_last):
+def patch_unet_resnets(model, memory_format=torch.channels_last, dtype=torch.float16):
     """replace `forward` on every module of `model` (pipe.unet, a ControlNet) that has norm1, conv1, time_emb_proj, norm2 and
-    conv2 by a UNetResnet built from it; returns the number of blocks patched.  A matching block outside the supported
-    configuration raises NotImplementedError with its name, before anything is patched.  The modules' own methods stay on
+    conv2 by a UNetResnet built from it; returns the number of blocks patched.  dtype: the pipeline's dtype, torch.float16 or
+    torch.bfloat16.  A matching block outside the supported configuration, or whose parameters are not of `dtype`, raises
+    NotImplementedError with its name, before anything is patched.  The modules' own methods stay on
     their class: unpatch_unet_resnets removes the bindings.  The weights are copied: patch again after loading others."""
-    return _dropin.patch(model, UNetResnet, PARTS, _WHO, _ATTR, memory_format)
+    _dropin.dtype_name(_WHO, dtype)
+    return _dropin.patch(model, UNetResnet, PARTS, _WHO, _ATTR, memory_format, dtype=dtype)
 
 
 def unpatch_unet_resnets(model):

@@ -63,9 +63,11 @@ def canonical_state_dict(sd, prefixes=("decoder.", "post_quant_conv.")):
     return out
 
 
-def pack_conv_weight(w, cin_pad=None):
-    """(cout, cin, kh, kw) or (cout, cin) -> fp16 (cout, kh kw cin') row-major with k = (ky, kx, ci), the input channels
-    zero-padded to cin' = cin_pad: the weight matrix vae_conv reads"""
+def pack_conv_weight(w, cin_pad=None, dtype=torch.float16):
+    """(cout, cin, kh, kw) or (cout, cin) -> `dtype` (fp16, or bf16 for vae_conv's bf16 form) (cout, kh kw cin') row-major with
+    k = (ky, kx, ci), the input channels zero-padded to cin' = cin_pad: the weight matrix vae_conv reads"""
+    if dtype not in (torch.float16, torch.bfloat16):
+        raise TypeError("pack_conv_weight: dtype %s, expected torch.float16 or torch.bfloat16" % (dtype,))
     w = w.detach()
     if w.dim() == 2:
         w = w[:, :, None, None]
@@ -73,7 +75,7 @@ def pack_conv_weight(w, cin_pad=None):
     w = w.permute(0, 2, 3, 1)
     if cin_pad is not None and cin_pad > cin:
         w = torch.nn.functional.pad(w, (0, cin_pad - cin))
-    return w.reshape(cout, -1).to(torch.float16).contiguous()
+    return w.reshape(cout, -1).to(dtype).contiguous()
 
 
 def up2_source_index(y, x, H, W):

@@ -21,6 +21,8 @@
  *       layout.  VAE_OUT_F32: fp32 rows of stride ldo (the attention scores).  VAE_OUT_F16_NCHW: (n, cout, H, W) fp16 (the
  *       image; ldo = cout).  bias (optional, fp32): per output channel, or with bias_rows = 1 (ksize 1) per row of the image.
  *     cin % 32 == 0; any cout (a ragged last column tile reads zero weights and stores nothing beyond cout).
+ *     With VAE_ELEM_BF16 OR-ed into out_kind, x, W and residual are bf16 on v_mfma_f32_32x32x16_bf16 and the 16-bit outputs
+ *     bf16 (the UNet's resnet blocks of bf16 pipelines); bias and VAE_OUT_F32 stay fp32.
  *   vae_groupnorm_workspace_bytes / vae_groupnorm : GroupNorm(32, C, eps) [+ SiLU] on x (n, P, C) fp16, C in {128, 256, 512}
  *     -> y fp16.  Statistics as midas_groupnorm_stats: fp64 partial sums per workgroup of 256 pixels, a second launch adds
  *     them in chunk order; the third launch applies in fp32.
@@ -48,6 +50,11 @@ extern "C" {
 #define VAE_OUT_F16 0
 #define VAE_OUT_F32 1
 #define VAE_OUT_F16_NCHW 2
+/* OR-ed into vae_conv's out_kind: x, w and residual are bf16 instead of fp16, on v_mfma_f32_32x32x16_bf16, and VAE_OUT_F16 /
+ * VAE_OUT_F16_NCHW then mean bf16 output ("16-bit, the operands' type"); bias stays fp32 and VAE_OUT_F32 stays fp32.  Strides
+ * are in elements of 2 bytes either way.  Every check answers as without the bit; any other bit is FRESCO_EINVAL.  Only
+ * vae_conv takes it: the other vae_* functions are fp16. */
+#define VAE_ELEM_BF16 0x100
 
 int vae_input(const void* z, const float* weight, const float* bias, void* out, int n, int h, int w, int cpad, void* stream);
 int vae_conv(const void* x, int64_t x_img_stride, const void* w, int64_t w_img_stride, const float* bias /* may be NULL */,

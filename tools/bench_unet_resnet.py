@@ -18,6 +18,12 @@ is fixed in advance: the comparison is against the PyTorch fp16 module measured 
 PyTorch wins is listed as such.
 
     python tools/bench_unet_resnet.py [--out profiles/unet_resnet_bench.json]
+
+--dtype bf16 (--out profiles/unet_resnet_bf16_bench.json): the same 32 blocks with bf16 weights and activations, three
+children: the native bf16 blocks (csrc/net_bf16.hip's kernels), the native fp16 blocks of the same run, and PyTorch's bf16
+module.  bf16 moves the same bytes as fp16 and the dense MFMA rate is the same for both types, so what is tested is parity:
+per shape the bf16 median against the spread (smallest and largest) of the fp16 leg's five timed blocks.  The launch kinds
+are not timed again: they are the fp16 kernels' text.
 """
 import argparse
 import json
@@ -35,7 +41,8 @@ from bench_vae import PEAK_F16_DENSE, timed  # noqa: E402
 N = 16
 HBM_PEAK = 8.0e12  # bytes / s, MI355X specification
 MODES = ("native", "pytorch", "kinds")
-LIMITS = dict(native=240, pytorch=420, kinds=240)  # seconds per child
+BF16_MODES = ("native", "native_fp16", "pytorch")  # --dtype bf16
+LIMITS = dict(native=240, native_fp16=240, pytorch=420, kinds=240)  # seconds per child
 # (cin, cout, side, how many the UNet runs, how many the ControlNet runs)
 SHAPES = (
     (320, 320, 64, 2, 2), (320, 640, 32, 1, 1), (640, 640, 32, 1, 1), (640, 1280, 16, 1, 1), (1280, 1280, 16, 1, 1),
@@ -71,7 +78,7 @@ def queued_us(fn, reps=40):
     return e0.elapsed_time(e1) / reps * 1e3
 
 
-def child(mode):
+def child(mode, dtype="fp16"):
     import torch
     import fresco_amd
     from fresco_amd import _lib, ops
@@ -81,16 +88,17 @@ def child(mode):
     dev = "cuda:0"
     g = torch.Generator().manual_seed(0)
     res = dict(mode=mode, device=torch.cuda.get_device_name(0))
-    if mode in ("native", "pytorch"):
+    dt = torch.bfloat16 if dtype == "bf16" and mode != "native_fp16" else torch.float16
+    if mode in ("native", "native_fp16", "pytorch"):
         rows = []
         for cin, cout, side, _, _ in SHAPES:
-            mod = M.build(cin, cout, torch.float16).to(dev)
-            x = torch.randn(N, cin, side, side, generator=g).half().to(dev)
-            temb = torch.randn(N, M.TEMB_CHANNELS, generator=g).half().to(dev)
+            mod = M.build(cin, cout, dt).to(dev)
+            x = torch.randn(N, cin, side, side, generator=g).to(dt).to(dev)
+            temb = torch.randn(N, M.TEMB_CHANNELS, generator=g).to(dt).to(dev)
             x_cl = x.contiguous(memory_format=torch.channels_last)
             row = dict(shape=_name(cin, cout, side))
-            if mode == "native":
-                blk = fresco_amd.UNetResnet.from_module(mod)
+            if mode != "pytorch":
+                blk = fresco_amd.UNetResnet.from_module(mod, dtype=dt)
                 row["ms"], row["blocks_ms"] = timed(lambda: blk(x_cl, temb), _iters(cin, cout, side))
             else:
                 with torch.no_grad():
@@ -155,21 +163,49 @@ def child(mode):
     print(json.dumps(res), flush=True)
 
 
+def report_bf16(got, out):
+    """per shape: native bf16 against PyTorch's bf16 module and against the native fp16 leg's five timed blocks"""
+    shapes, tot = [], dict(native_bf16_ms=0.0, native_fp16_ms=0.0, pytorch_bf16_ms=0.0)
+    for (cin, cout, side, u, c), nat, f16, pt in zip(SHAPES, got["native"]["rows"], got["native_fp16"]["rows"], got["pytorch"]["rows"]):
+        lo, hi = min(f16["blocks_ms"]), max(f16["blocks_ms"])
+        shapes.append(dict(shape=nat["shape"], unet_count=u, controlnet_count=c, native_bf16_ms=nat["ms"], native_bf16_blocks_ms=nat["blocks_ms"],
+                           native_fp16_ms=f16["ms"], native_fp16_blocks_ms=f16["blocks_ms"], bf16_over_fp16=nat["ms"] / f16["ms"],
+                           bf16_within_fp16_spread=bool(lo <= nat["ms"] <= hi), pytorch_bf16_ms=pt["ms"],
+                           pytorch_contiguous_ms=pt["contiguous_ms"], pytorch_channels_last_ms=pt["channels_last_ms"],
+                           pytorch_over_native=pt["ms"] / nat["ms"], pytorch_wins=bool(pt["ms"] < nat["ms"])))
+        tot["native_bf16_ms"] += (u + c) * nat["ms"]
+        tot["native_fp16_ms"] += (u + c) * f16["ms"]
+        tot["pytorch_bf16_ms"] += (u + c) * pt["ms"]
+    tot["pytorch_over_native"] = tot["pytorch_bf16_ms"] / tot["native_bf16_ms"]
+    tot["bf16_over_fp16"] = tot["native_bf16_ms"] / tot["native_fp16_ms"]
+    result = dict(bench="unet_resnet_bf16", device=got["native"]["device"], batch=N, image=512, dtype="bfloat16", shapes=shapes,
+                  all_32_blocks=tot, shapes_where_pytorch_wins=[s["shape"] for s in shapes if s["pytorch_wins"]],
+                  shapes_outside_fp16_spread=[s["shape"] for s in shapes if not s["bf16_within_fp16_spread"]])
+    print(json.dumps(result))
+    if out:
+        with open(out, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="write the result as JSON here as well")
-    ap.add_argument("--mode", choices=MODES, default=None, help="(internal) run one mode in this process")
+    ap.add_argument("--mode", choices=MODES + BF16_MODES, default=None, help="(internal) run one mode in this process")
+    ap.add_argument("--dtype", choices=("fp16", "bf16"), default="fp16", help="bf16: the bf16 blocks against the fp16 leg and PyTorch")
     args = ap.parse_args()
     if args.mode:
-        return child(args.mode)
+        return child(args.mode, args.dtype)
     got = {}
-    for mode in MODES:
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode], stdout=subprocess.PIPE,
-                           timeout=LIMITS[mode], text=True)
+    for mode in (BF16_MODES if args.dtype == "bf16" else MODES):
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--mode", mode, "--dtype", args.dtype],
+                           stdout=subprocess.PIPE, timeout=LIMITS[mode], text=True)
         if p.returncode != 0:
             sys.exit("bench_unet_resnet.py: mode %s ended with status %d; nothing further is started" % (mode, p.returncode))
         got[mode] = json.loads(p.stdout.strip().splitlines()[-1])
         print(mode, got[mode], flush=True)
+    if args.dtype == "bf16":
+        return report_bf16(got, args.out)
     shapes, unet_ms, cnet_ms, t_unet_ms, t_cnet_ms = [], 0.0, 0.0, 0.0, 0.0
     for (cin, cout, side, u, c), nat, pt in zip(SHAPES, got["native"]["rows"], got["pytorch"]["rows"]):
         shapes.append(dict(shape=nat["shape"], unet_count=u, controlnet_count=c, native_ms=nat["ms"], pytorch_ms=pt["ms"],
