@@ -26,14 +26,10 @@ import vae_encoder_model as EM  # noqa: E402
 from make_vae_golden import Peak  # noqa: E402
 
 
-def main():
-    net64 = EM.build(torch.float64)
-    net32 = EM.build(torch.float32)
-    with open(os.path.join(HERE, EM.NAMES_FILE), "w") as f:
-        for name, shape in EM.encoder_names_shapes(net64):
-            f.write("%s %s\n" % (name, "x".join(map(str, shape))))
+def record(net64, net32, cases):
+    """the arrays of the module docstring for every case"""
     out = {}
-    for case in EM.CASES:
+    for case in cases:
         key = EM.case_key(case)
         x = EM.images(case)
         peak, peak32 = Peak(net64), Peak(net32)
@@ -62,6 +58,16 @@ def main():
         print("%s: activation peak %.1f; fp16-rounded layers vs float64: worst tap %.2e (%s), parameters %.2e; logvar in "
               "[%.2f, %.2f]" % (key, max(peak.peak, peak32.peak), max(noise[:-1]), EM.TAPS[int(np.argmax(noise[:-1]))], noise[-1],
                                 float(p64[:, 4:].min()), float(p64[:, 4:].max())))
+    return out
+
+
+def main():
+    net64 = EM.build(torch.float64)
+    net32 = EM.build(torch.float32)
+    with open(os.path.join(HERE, EM.NAMES_FILE), "w") as f:
+        for name, shape in EM.encoder_names_shapes(net64):
+            f.write("%s %s\n" % (name, "x".join(map(str, shape))))
+    out = record(net64, net32, EM.CASES)
     path = os.path.join(HERE, EM.GOLDEN_FILE)
     np.savez_compressed(path, **out)
     print("wrote %s (%d bytes, %d arrays)" % (path, os.path.getsize(path), len(out)))

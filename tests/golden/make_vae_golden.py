@@ -40,15 +40,10 @@ class Peak:
             h.remove()
 
 
-def main():
-    net64 = M.build(torch.float64)
-    net32 = M.build(torch.float32)
-    names_shapes = M.module_names_shapes(net64)
-    with open(os.path.join(HERE, M.NAMES_FILE), "w") as f:
-        for name, shape in names_shapes:
-            f.write("%s %s\n" % (name, "x".join(map(str, shape))))
+def record(net64, net32, cases, whole_u8=lambda case: True):
+    """the arrays of the module docstring for every case; whole_u8(case) false: without that case's whole uint8 image"""
     out = {}
-    for case in M.CASES:
+    for case in cases:
         key = M.case_key(case)
         z = M.latents(case)
         peak = Peak(net64)
@@ -78,10 +73,22 @@ def main():
         out[key + "_peak"] = np.array(peaks, np.float64)
         out[key + "_u8_share"] = np.array(share, np.float64)
         out[key + "_image"] = M.thin_image(img64)
-        out[key + "_image_u8"] = u64
+        if whole_u8(case):
+            out[key + "_image_u8"] = u64
         print("%s: activation peak %.1f; fp16-rounded layers vs float64: worst tap %.2e (%s), image %.2e; uint8 one apart %.3f %%; "
               "clipped %.1f %%" % (key, max(peak.peak, peak32.peak), max(noise[:-1]), M.TAPS[int(np.argmax(noise[:-1]))],
                                    noise[-1], 100 * share, 100 * float(((u64 == 0) | (u64 == 255)).mean())))
+    return out
+
+
+def main():
+    net64 = M.build(torch.float64)
+    net32 = M.build(torch.float32)
+    names_shapes = M.module_names_shapes(net64)
+    with open(os.path.join(HERE, M.NAMES_FILE), "w") as f:
+        for name, shape in names_shapes:
+            f.write("%s %s\n" % (name, "x".join(map(str, shape))))
+    out = record(net64, net32, M.CASES)
     path = os.path.join(HERE, M.GOLDEN_FILE)
     np.savez_compressed(path, **out)
     print("wrote %s (%d bytes, %d arrays)" % (path, os.path.getsize(path), len(out)))

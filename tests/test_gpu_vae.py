@@ -164,6 +164,7 @@ def _groupnorm_against_float64(n, H, W, C, silu):
     y = ops.vae_groupnorm(x.to(DEV), gamma.to(DEV), beta.to(DEV), 1e-6, silu=silu)
     assert y.dtype == torch.float16 and y.shape == x.shape
     _check("groupnorm C=%d%s" % (C, " + SiLU" if silu else ""), y, ref, bound)
+    assert torch.equal(y, ops.vae_groupnorm(x.to(DEV), gamma.to(DEV), beta.to(DEV), 1e-6, silu=silu))
 
 
 @pytest.mark.parametrize("silu", [True, False], ids=["silu", "plain"])
@@ -226,19 +227,22 @@ def decoder(vae16):
     return VAEDecoder.from_vae(vae16)
 
 
-@pytest.mark.parametrize("case", M.CASES, ids=M.case_key)
-def test_decoder_matches_the_record(case, gold, vae16, decoder):
+def decoder_against_record(case, gold, vae16, decoder):
+    """every tap and the image of decode(latents(case)) against the record `gold`, the uint8 rule where the record holds the
+    whole uint8 image, and a second call's bits -> the image (tests/test_gpu_vae_fullsize.py runs its own records through
+    this).  vae16 None: without PyTorch's module beside ours"""
     key = M.case_key(case)
     z = M.latents(case).to(DEV)
     taps, ttaps = {}, {}
     img = decoder.decode(z, taps=taps).sample
     with torch.no_grad():
-        timg = vae16(z, ttaps)  # PyTorch's own kernels in fp16: printed beside ours for context, nothing asserted on it
+        # PyTorch's own kernels in fp16: printed beside ours for context, nothing asserted on it
+        timg = vae16(z, ttaps) if vae16 is not None else torch.full_like(img, float("nan"))
     noise, peak = gold[key + "_noise"], gold[key + "_peak"]
     worst = []
     for i, t in enumerate(M.TAPS + ("image",)):
         ours = M.thin(taps[t].double()) if t != "image" else M.thin_image(img.double())
-        theirs = M.thin(ttaps[t].double()) if t != "image" else M.thin_image(timg.double())
+        theirs = M.thin(ttaps[t].double()) if t in ttaps else M.thin_image(timg.double()) if t == "image" else np.nan
         rec = gold["%s_%s" % (key, t)]
         assert ours.shape == rec.shape, (t, ours.shape, rec.shape)
         bar = 4 * noise[i] * peak[i]
@@ -247,16 +251,24 @@ def test_decoder_matches_the_record(case, gold, vae16, decoder):
               % (key, t, noise[i], peak[i], ratio, tratio))
         worst.append((ratio, t))
     assert img.shape == (case[0], 3, 8 * case[1], 8 * case[2]) and img.dtype == torch.float16
-    assert max(worst)[0] <= 1.0, max(worst)
-    u8, rec8 = M.tensor2numpy(img), gold[key + "_image_u8"]
-    d = np.abs(u8.astype(int) - rec8.astype(int))
-    td = np.abs(M.tensor2numpy(timg).astype(int) - rec8.astype(int))
-    share, allowed = float((d == 1).mean()), 2 * float(gold[key + "_u8_share"]) + 0.005
-    print("%s uint8 image: largest difference %d, one apart %.3f %% (allowed %.3f %%)   (PyTorch fp16 module: %d, %.3f %%)"
-          % (key, d.max(), 100 * share, 100 * allowed, td.max(), 100 * float((td == 1).mean())))
-    assert d.max() <= 1 and share <= allowed
+    assert all(ratio <= 1.0 for ratio, _ in worst), worst  # (a NaN ratio fails here; max() of the pairs would step over it)
+    if key + "_image_u8" in gold:
+        u8, rec8 = M.tensor2numpy(img), gold[key + "_image_u8"]
+        d = np.abs(u8.astype(int) - rec8.astype(int))
+        td = np.abs(M.tensor2numpy(timg).astype(int) - rec8.astype(int))
+        share, allowed = float((d == 1).mean()), 2 * float(gold[key + "_u8_share"]) + 0.005
+        print("%s uint8 image: largest difference %d, one apart %.3f %% (allowed %.3f %%)   (PyTorch fp16 module: %d, %.3f %%)"
+              % (key, d.max(), 100 * share, 100 * allowed, td.max(), 100 * float((td == 1).mean())))
+        assert d.max() <= 1 and share <= allowed
     again = decoder.decode(z, return_dict=False)[0]
     assert torch.equal(img, again)
+    return img
+
+
+@pytest.mark.parametrize("case", M.CASES, ids=M.case_key)
+def test_decoder_matches_the_record(case, gold, vae16, decoder):
+    assert M.case_key(case) + "_image_u8" in gold  # these records hold the whole uint8 image: its rule is applied
+    decoder_against_record(case, gold, vae16, decoder)
 
 
 def test_patched_pipe_decodes_natively(vae16, decoder, monkeypatch):

@@ -173,8 +173,9 @@ def encoder(vae16):
     return VAEEncoder.from_vae(vae16)
 
 
-@pytest.mark.parametrize("case", EM.CASES, ids=EM.case_key)
-def test_encoder_matches_the_record(case, gold, vae16, encoder):
+def encoder_against_record(case, gold, vae16, encoder):
+    """every tap and the parameters of encode(images(case)) against the record `gold`, and a second call's bits -> the
+    parameters (tests/test_gpu_vae_encoder_fullsize.py runs its own records through this)"""
     key = EM.case_key(case)
     x = EM.images(case).to(DEV)
     taps, ttaps = {}, {}
@@ -195,9 +196,15 @@ def test_encoder_matches_the_record(case, gold, vae16, encoder):
         worst.append((ratio, t))
     n, H, W = case
     assert dist.parameters.shape == (n, 8, H // 8, W // 8) and dist.parameters.dtype == torch.float16
-    assert max(worst)[0] <= 1.0, max(worst)
+    assert all(ratio <= 1.0 for ratio, _ in worst), worst  # (a NaN ratio fails here; max() of the pairs would step over it)
     again = encoder.encode(x, return_dict=False)[0]
     assert torch.equal(dist.parameters, again.parameters)
+    return dist.parameters
+
+
+@pytest.mark.parametrize("case", EM.CASES, ids=EM.case_key)
+def test_encoder_matches_the_record(case, gold, vae16, encoder):
+    encoder_against_record(case, gold, vae16, encoder)
 
 
 def test_latent_dist_is_the_modules_distribution(encoder):

@@ -34,6 +34,8 @@ from vae_model import ACT_LIMIT, BLOCK_CHANNELS, Attention, MidBlock, Resnet, ro
 
 CASES = [(2, 64, 96), (1, 128, 64), (1, 160, 224), (1, 68, 100)]  # images (n, H, W); the last one's third level is 17 x 25
 GOLDEN_FILE = "vae_encoder_golden.npz"
+FULLSIZE_CASES = [(2, 192, 192), (1, 512, 512)]  # tests/golden/make_vae_encoder_fullsize_golden.py: vae_model.FULLSIZE_CASES' images
+FULLSIZE_GOLDEN_FILE = "vae_encoder_fullsize_golden.npz"
 NAMES_FILE = "vae_encoder_names.txt"
 TAPS = ("conv_in", "down0", "down1", "down2", "down3", "mid", "norm_out")
 PREFIXES = ("encoder.", "quant_conv.")
@@ -44,8 +46,8 @@ def case_key(case):
     return "vaeenc_%dx%dx%d" % case
 
 
-def load_golden(golden_dir):
-    return dict(np.load(os.path.join(golden_dir, GOLDEN_FILE)))
+def load_golden(golden_dir, name=GOLDEN_FILE):
+    return dict(np.load(os.path.join(golden_dir, name)))
 
 
 def images(case, dtype=torch.float16):

@@ -31,6 +31,10 @@ import torch.nn.functional as F
 
 CASES = [(2, 8, 12), (1, 16, 8), (1, 20, 28)]  # latents (n, h, w): 96, 128 and 560 tokens in the mid block
 GOLDEN_FILE = "vae_golden.npz"
+# tests/golden/make_vae_fullsize_golden.py: 576 tokens in the mid block with two images, and GroupNorm past one grid pass of
+# its apply kernel at every width; the real 512 x 512 frame (4096 tokens), recorded without its whole uint8 image
+FULLSIZE_CASES = [(2, 24, 24), (1, 64, 64)]
+FULLSIZE_GOLDEN_FILE = "vae_fullsize_golden.npz"
 NAMES_FILE = "vae_decoder_names.txt"
 TAPS = ("conv_in", "mid", "up0", "up1", "up2", "up3", "norm_out")
 TAP_STRIDE = 16     # the golden file keeps every 16th channel of a tap ...
@@ -45,8 +49,8 @@ def case_key(case):
     return "vae_%dx%dx%d" % case
 
 
-def load_golden(golden_dir):
-    return dict(np.load(os.path.join(golden_dir, GOLDEN_FILE)))
+def load_golden(golden_dir, name=GOLDEN_FILE):
+    return dict(np.load(os.path.join(golden_dir, name)))
 
 
 def _picks(size, stride):
