@@ -6,7 +6,14 @@ Every numeric bar is the project's drop-in bar, read from the golden file: |got 
 the recorded distance of the reference arithmetic (fp32, every layer's output rounded to fp16, resp. bf16) from its float64
 run.  Each comparison prints its ratio to the bar beside the ratio of the unpatched fp16 model on PyTorch's kernels (for
 `fresco` and `bf16`: PyTorch's modules around the native FRESCO sites).  Nothing is compared with the code's own earlier output except
-bit for bit.  The models are stand-ins with stand-in weights: diffusers' modules and a checkpoint stay unchecked."""
+bit for bit.  The models are stand-ins with stand-in weights: diffusers' modules and a checkpoint stay unchecked.
+
+The second half drives what a keyframe run does around those calls, against tests/golden/unet_composed_seq_golden.npz:
+fresco_amd.get_intraframe_paras (the store pass: one UNet call without residuals), the call with the spatial-guided pass on
+top of cross-frame and temporal attention (`full`), and fresco_amd.inference with the real AttentionControl going through the
+reference's sequence (`seq`).  What they pin is the order and the number of `attn1` calls under the patches: the store pass
+appends one tensor per self-attention call of up_blocks.2 / up_blocks.3 and the cyclic read index advances once per such
+call."""
 import os
 import types
 
@@ -72,6 +79,17 @@ class Rig:
         fresco_amd.apply_FRESCO_opt(self.pipe, steps=[HOOK_STEP], layers=[0, 1, 2, 3], flows=self.flows, occs=self.occs,
                                     correlation_matrix=[], iters=0, saliency=self.saliency)
 
+    def full_on(self, steps=(HOOK_STEP,), correlation_matrix=()):
+        """run_fresco.py:231-234: enable_controller (intra too: it stays off on an empty store) and the hook, iters = 0"""
+        import fresco_amd
+        self.ctrl.enable_controller(self.inter, self.cf_masks)
+        fresco_amd.apply_FRESCO_opt(self.pipe, steps=steps, layers=[0, 1, 2, 3], flows=self.flows, occs=self.occs,
+                                    correlation_matrix=list(correlation_matrix), iters=0, saliency=self.saliency)
+
+    def flags(self):
+        c = self.ctrl
+        return (int(c.use_intraattn), int(c.use_interattn), int(c.use_cfattn), int(c.index))
+
     def fresco_off(self):
         from fresco_amd import hook
         self.ctrl.disable_controller()
@@ -134,10 +152,10 @@ def ratios(gold, case, rec):
             for i, k in enumerate(M.CALL_KEYS)]
 
 
-def report(what, got, own=None, own_label="PyTorch fp16"):
-    line = "%s |got - record| / (4 x noise x peak): %s" % (what, "  ".join("%s %.3f" % kv for kv in zip(M.CALL_KEYS, got)))
+def report(what, got, own=None, own_label="PyTorch fp16", keys=M.CALL_KEYS):
+    line = "%s |got - record| / (4 x noise x peak): %s" % (what, "  ".join("%s %.3f" % kv for kv in zip(keys, got)))
     if own is not None:
-        line += "   (%s: %s)" % (own_label, "  ".join("%s %.3f" % kv for kv in zip(M.CALL_KEYS, own)))
+        line += "   (%s: %s)" % (own_label, "  ".join("%s %.3f" % kv for kv in zip(keys, own)))
     print(line)
     return line
 
@@ -427,3 +445,244 @@ def test_bf16_pair(gold):
     got = ratios(gold, "bf16", rec)
     line = report("bf16", got, ratios(gold, "bf16", own), "PyTorch bf16 around the native FRESCO processors")
     assert np.isfinite(rec["out"]).all() and max(got) <= 1.0, line
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the store pass, the spatial-guided call and the controller as the loop drives it
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def seq_gold():
+    return M.seq_golden(GOLDEN)
+
+
+class keyframe:
+    """patched(rig, order) -- order None: the unpatched models -- whose exit also empties the controller's store and puts
+    the processor's switches back"""
+
+    def __init__(self, rig, order="NOPQ"):
+        self.rig, self.inner = rig, None if order is None else patched(rig, order)
+
+    def __enter__(self):
+        return None if self.inner is None else self.inner.__enter__()
+
+    def __exit__(self, *exc):
+        if self.inner is not None:
+            self.inner.__exit__(*exc)
+        else:
+            self.rig.fresco_off()
+            self.rig.place()
+        self.rig.ctrl.clear_store()
+        self.rig.proc.fuse_kv_pack = self.rig.proc.sparse_kv_projection = True
+        self.rig.unet.on_call = None
+
+
+def device_pipe(rig):
+    """unet_composed_model.Pipe around the rig's models with what a diffusers pipeline has and loop_model.Pipe lacks for
+    get_intraframe_paras: the scheduler's timesteps on the device (set_timesteps(n, device=...)), the controller"""
+    pipe = M.Pipe(DEV, torch.float16, rig.unet, rig.cn)
+    pipe.frescoProc = types.SimpleNamespace(controller=rig.ctrl)
+    pipe.scheduler.timesteps = pipe.scheduler.timesteps.to(DEV)
+    return pipe
+
+
+def store_pass(rig, seed=M.STORE_SEED):
+    """fresco_amd.get_intraframe_paras on the rig's UNet with the record's images and its one draw -> the Gram targets"""
+    import fresco_amd
+    imgs, draw = M.store_inputs(seed)
+    pipe = device_pipe(rig)
+    keep, torch.randn = torch.randn, L.replay_randn([draw.to(DEV)], DEV)
+    try:
+        return fresco_amd.get_intraframe_paras(pipe, imgs.to(DEV), pipe.frescoProc, rig.inputs()[2], seed=0)
+    finally:
+        torch.randn = keep
+
+
+def stored(rig):
+    return rig.ctrl.stored_attn["decoder_attn"]
+
+
+def store_ratios(seq_gold, tensors, corr):
+    """per STORE_KEYS entry |got - record| / (4 x noise x peak)"""
+    got = {"attn%d" % i: M.thin_tokens(t.double().cpu()) for i, t in enumerate(tensors)}
+    got.update({"gram%d" % i: M.thin_gram(c.double().cpu()) for i, c in enumerate(corr)})
+    return [M.distance(got[k], seq_gold["store_" + k]) / bar for k, bar in zip(M.STORE_KEYS, M.store_bars(seq_gold))]
+
+
+def test_store_pass_under_the_four_patches(rig, seq_gold):
+    ctrl = rig.ctrl
+    x, t, text, _ = rig.inputs()
+    with keyframe(rig, None):        # PyTorch's modules around the native processor
+        corr = store_pass(rig)       # (clear_store() makes a new list: read it after the pass)
+        own = store_ratios(seq_gold, stored(rig), corr)
+    with keyframe(rig):
+        ctrl.enable_interattn(rig.inter)      # the call must switch both off
+        ctrl.enable_cfattn(rig.cf_masks)
+        corr = store_pass(rig)
+        kept = stored(rig)
+        assert len(kept) == M.STORED
+        n = 2 * M.FRAMES
+        assert [tuple(k.shape) for k in kept] == [(n, 64, 640), (n, 256, 320), (n, 256, 320)]
+        assert all(k.dtype == torch.float16 and k.is_contiguous() for k in kept)
+        assert ctrl.store is False and rig.flags() == (0, 0, 0, 0)
+        assert [tuple(c.shape) for c in corr] == [(n, 4, 4), (n, 16, 16), (n, 64, 64), (n, 256, 256)]
+        assert all(c.dtype == torch.float32 for c in corr)
+        got = store_ratios(seq_gold, kept, corr)
+        line = report("store", got, own, "PyTorch fp16 around the native processor", keys=M.STORE_KEYS)
+        assert max(got) <= 1.0 and max(own) <= 1.0, line
+        # each tensor owns its memory: no two overlap, and further calls (the loop's form with residuals, then the store pass's
+        # form without) leave every bit as it was
+        spans = sorted((k.data_ptr(), k.data_ptr() + k.numel() * k.element_size()) for k in kept)
+        assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), spans
+        bits = [k.clone() for k in kept]
+        first = call(rig)[0]
+        with torch.no_grad():
+            second = rig.unet(x, t, encoder_hidden_states=text, cross_attention_kwargs=None, return_dict=False)
+        assert len(second) == 5 and len(stored(rig)) == M.STORED     # disable_FRESCO_opt's hook keeps collecting; nothing stored
+        assert all(k is s for k, s in zip(kept, stored(rig))) and all(torch.equal(k, b) for k, b in zip(kept, bits))
+        assert M.distance(first.double().cpu().numpy(), second[0].double().cpu().numpy()) > 0      # (the residuals were live)
+
+
+def test_full_holds_the_bar(rig, gold, seq_gold):
+    ctrl = rig.ctrl
+    inputs = rig.inputs()
+    with keyframe(rig, None):
+        store_pass(rig)
+        rig.full_on()
+        own = M.call_record(rig.unet, rig.cn, torch.float16, inputs=inputs)
+    with keyframe(rig):
+        plain_bits = flat(call(rig, inputs))
+        rig.fresco_on()
+        fresco_bits = flat(call(rig, inputs))
+        rig.fresco_off()
+        # enable_intraattn() on an empty store: use_intraattn stays False and the call is `fresco`'s
+        assert len(stored(rig)) == 0
+        rig.full_on()
+        assert rig.flags() == (0, 1, 1, 0)
+        assert torch.equal(flat(call(rig, inputs)), fresco_bits)
+        rig.fresco_off()
+        # the store pass, everything on, the call
+        store_pass(rig)
+        rig.full_on()
+        assert rig.flags() == (1, 1, 1, 0) and len(stored(rig)) == M.STORED
+        kept = [k.clone() for k in stored(rig)]
+        rec = M.call_record(rig.unet, rig.cn, torch.float16, inputs=inputs)
+        assert rig.flags() == (1, 1, 1, 0)                      # three reads: the index is back at 0
+        bits = flat(call(rig, inputs))
+        assert rig.flags() == (1, 1, 1, 0)
+        assert torch.equal(flat(call(rig, inputs)), bits)       # a second call: the same bits
+        assert all(torch.equal(k, s) for k, s in zip(kept, stored(rig)))
+        got = ratios(seq_gold, "full", rec)
+        line = report("full", got, ratios(seq_gold, "full", own), "PyTorch fp16 around the native FRESCO sites")
+        assert np.isfinite(rec["out"]).all() and max(got) <= 1.0, line
+        bar = 4 * float(seq_gold["full_noise"][0]) * float(seq_gold["full_peak"][0])
+        assert M.distance(rec["out"], gold["fresco_out"]) > 2 * bar      # the spatial pass was live
+        assert not torch.equal(bits, fresco_bits)
+        # the unfused routes behind the spatial pass
+        for switch in ("fuse_kv_pack", "sparse_kv_projection"):
+            setattr(rig.proc, switch, False)
+            r = ratios(seq_gold, "full", M.call_record(rig.unet, rig.cn, torch.float16, inputs=inputs))
+            line = report("full, %s off" % switch, r)
+            assert max(r) <= 1.0 and rig.flags() == (1, 1, 1, 0), line
+        rig.proc.fuse_kv_pack = rig.proc.sparse_kv_projection = True
+        assert torch.equal(flat(call(rig, inputs)), bits)
+        # the controller and the hook off again, the store still filled: plain's bits
+        rig.fresco_off()
+        assert len(stored(rig)) == M.STORED and torch.equal(flat(call(rig, inputs)), plain_bits)
+    for order in ORDERS[1:]:
+        with keyframe(rig, order):
+            store_pass(rig)
+            rig.full_on()
+            assert torch.equal(flat(call(rig, inputs)), bits), order
+
+
+def test_full_runs_natively(rig):
+    inputs = rig.inputs()
+    with keyframe(rig):
+        store_pass(rig)
+        rig.full_on()
+        call(rig, inputs)        # (the caches of the text, of the condition and of the index tables fill)
+        names = _kernel_names(lambda: call(rig, inputs))
+        assert rig.flags() == (1, 1, 1, 0)
+    print("full, patched: %s" % (names,))
+    for k in names:
+        if "fresco" in k:
+            continue
+        assert any(a in k for a in ALLOWED) and not any(s in k for s in NOT_OURS), k
+    assert any("unet_attention" in k or "unet_attn" in k for k in names), names
+
+
+def seq_ratio(seq_gold, steps, final):
+    d = max(M.distance(steps.double().cpu().numpy(), seq_gold["seq_steps"]), M.distance(final.double().cpu().numpy(), seq_gold["seq_final"]))
+    return d / (4 * float(seq_gold["seq_noise"][0]) * float(seq_gold["seq_peak"][0]))
+
+
+def seq_run(rig, seq_gold, loop, on_call=None):
+    """the store pass, everything switched on as run_fresco.py does (the hook on timesteps[:END_OPT_STEP] with the store pass's
+    Gram targets and iters = 0), then `loop` -- fresco_amd.inference or its restatement -- with the recorded draws replayed
+    -> (every UNet input's first half, the final latents, the controller's flags at each UNet call)"""
+    corr = store_pass(rig)
+    pipe = device_pipe(rig)
+    timesteps = pipe.scheduler.timesteps
+    if loop is L.inference_model:      # (the restatement indexes the scheduler's host tables)
+        timesteps = pipe.scheduler.timesteps = timesteps.cpu()
+    rig.full_on(steps=timesteps[:M.END_OPT_STEP], correlation_matrix=corr)
+    seen = []
+
+    def observe():
+        seen.append(rig.flags())
+        if on_call is not None:
+            on_call()
+    rig.unet.on_call = observe
+    keep, torch.randn = torch.randn, L.replay_randn([torch.from_numpy(z).to(DEV, torch.float16) for z in seq_gold["seq_draws"]], DEV)
+    try:
+        final = loop(pipe, pipe.controlnet, pipe.frescoProc, *M.loop_inputs(DEV, torch.float16), timesteps,
+                     flows=rig.flows, occs=rig.occs, saliency=rig.saliency, **M.SEQ_KW)
+    finally:
+        torch.randn, rig.unet.on_call = keep, None
+        torch.cuda.set_sync_debug_mode("default")
+    return torch.stack([x[:M.FRAMES] for x in rig.unet.inputs]), final, tuple(seen)
+
+
+def test_inference_drives_the_real_controller(rig, seq_gold):
+    """`seq`: intra + temporal + cross-frame at 601, temporal + cross-frame at 451, cross-frame at 301 and 151.  The index
+    tables of the masks and of the trajectory maps are built and checked on the host once per table, at their first use
+    (processor._sel_rows, ops._check_once); the restated loop on the unpatched models, which runs first, is that first use,
+    and from the first UNet call of fresco_amd.inference on nothing synchronises"""
+    import fresco_amd
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        try:
+            torch.ones(1, device=DEV).item()
+            raised = False
+        except RuntimeError:
+            raised = True
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    assert raised, "torch.cuda.set_sync_debug_mode('error') does not make .item() raise on this build"
+    ctrl = rig.ctrl
+    with keyframe(rig, None):
+        s_own, f_own, flags_own = seq_run(rig, seq_gold, L.inference_model)
+    with keyframe(rig):
+        kept = []
+
+        def on_call():
+            if not kept:
+                kept.extend((k, k.clone()) for k in stored(rig))
+            torch.cuda.set_sync_debug_mode("error")
+        steps, final, flags = seq_run(rig, seq_gold, fresco_amd.inference, on_call)
+        torch.cuda.synchronize()
+        ratio = seq_ratio(seq_gold, steps, final)
+        line = "seq: %.3f of the bar (noise %.2e, peak %.3g); fp16 torch ops on the unpatched model: %.3f" % (
+            ratio, float(seq_gold["seq_noise"][0]), float(seq_gold["seq_peak"][0]), seq_ratio(seq_gold, s_own, f_own))
+        print(line)
+        assert steps.shape[0] == len(M.STEPS2) and final.shape == (M.FRAMES, 4, M.LAT, M.LAT) and ratio <= 1.0, line
+        bar = 4 * float(seq_gold["seq_noise"][0]) * float(seq_gold["seq_peak"][0])
+        for i in range(len(M.STEPS2)):
+            assert M.distance(steps[i].double().cpu().numpy(), seq_gold["seq_steps"][i]) <= bar, i
+        # the controller went through the reference's sequence, the index back at 0 at every call
+        recorded = tuple(map(tuple, seq_gold["seq_flags"].tolist()))
+        assert flags == recorded == M.SEQ_FLAGS and flags_own == recorded, (flags, flags_own)
+        assert rig.flags() == (0, 0, 1, 0) and ctrl.store is False
+        # the store is untouched by the loop
+        assert len(kept) == M.STORED == len(stored(rig))
+        assert all(k is s and torch.equal(k, b) for (k, b), s in zip(kept, stored(rig)))

@@ -53,7 +53,10 @@ output end, the time MLP, the condition embedding, five zero convolutions and th
   * `fresco`: a `Fresco` object switches the UNet's FRESCO sites on for the record: oracle.fresco_oracle's
     fresco_attention on `attn1` of up_blocks.2 / up_blocks.3 (cross-frame keys and the temporal pass), and adain +
     warp_tensor at the input of every up block (optimize_feature with iters = 0 is its AdaIN epilogue).  All three run in
-    the dtype they are given: float64 for the record;
+    the dtype they are given: float64 for the record.  The same object is the restatement's controller: the store pass
+    (`store_pass`, what get_intraframe_paras does) fills its list of reference features, the spatial-guided pass reads them
+    through a cyclic index, and loop_model.inference_model switches it as the reference's loop switches AttentionControl
+    (`SeqModels`, `derive_seq`: the records `store`, `full` and `seq` of unet_composed_seq_golden.npz);
   * `fault`: one planted fault of FAULTS, for the discrimination checks of tests/test_unet_composed_cpu.py.
 """
 import os
@@ -105,7 +108,10 @@ def _call(m, q, *args, **kw):
 # ---------------------------------------------------------------------------------------------------------------------
 class Fresco:
     """what the record's FRESCO sites read: flows / occs / saliency of the hook, per token count the cross-frame mask and
-    the trajectory map of the processor, and the two switches of the controller"""
+    the trajectory map of the processor, and the controller: its three switches, and the store of the spatial-guided pass --
+    a list of reference features, a read index and a store switch that behave as fresco_amd/control.py's do (append when
+    storing; read store[index], advance, wrap to 0), under the method names the loop calls.
+    hook_steps: the timesteps the hook is active on (None: on every call), as apply_FRESCO_opt's `steps`."""
 
     def __init__(self, flows, occs, saliency, cf_masks, fwd_maps, tmasks):
         self.flows, self.occs, self.saliency = flows, occs, saliency
@@ -113,11 +119,56 @@ class Fresco:
         self.fwd_maps = {f.shape[2]: f[:, 0] for f in fwd_maps}
         self.tmasks = {f.shape[2]: t[:, 0] for f, t in zip(fwd_maps, tmasks)}
         self.use_cfattn = self.use_interattn = self.hook = True
+        self.use_intraattn = self.store = False
+        self.stored, self.index = [], 0
+        self.intra_scale, self.intra_bias = 0.2, 0.0     # AttentionControl's intraattn_scale_factor and intraattn_bias
+        self.hook_steps = None
+        self.own_refs = False                            # the planted fault "own_refs"
+
+    def flags(self):
+        return (int(self.use_intraattn), int(self.use_interattn), int(self.use_cfattn), int(self.index))
+
+    def clear_store(self):
+        self.stored = []
+        self.disable_intraattn()
+
+    def enable_store(self):
+        self.store = True
+
+    def disable_store(self):
+        self.store = False
+
+    def enable_intraattn(self):
+        self.index, self.store = 0, False
+        self.use_intraattn = len(self.stored) > 0        # nothing recorded: stays off
+
+    def disable_intraattn(self):
+        self.index, self.use_intraattn, self.store = 0, False, False
+
+    def disable_interattn(self):
+        self.use_interattn = False
+
+    def disable_controller(self):
+        self.disable_intraattn()
+        self.use_interattn = self.use_cfattn = False
+
+    def enable_controller(self):
+        self.enable_intraattn()
+        self.use_interattn = self.use_cfattn = True
+
+    def read(self):
+        """AttentionControl.forward(None) with use_intraattn on"""
+        ref = self.stored[self.index]
+        self.index += 1
+        if self.index >= len(self.stored):
+            self.index, self.store = 0, False
+        return ref
 
 
 class OracleFrescoProcessor:
     """FRESCOAttnProcessor2_0 restated through the oracle: self-attention is fresco_oracle.fresco_attention with whatever
-    `fresco` has switched on; cross-attention is the plain processor"""
+    `fresco` has switched on (the spatial-guided pass reads the next stored reference); while `fresco` stores, the
+    self-attention input is appended first (diffusion_hacked.py:206-207); cross-attention is the plain processor"""
 
     def __init__(self, fresco, q=_ident):
         self.fresco, self.q, self.plain = fresco, q, A.RefProcessor(q)
@@ -125,12 +176,20 @@ class OracleFrescoProcessor:
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None):
         from oracle import fresco_oracle as O
         f = self.fresco
-        if encoder_hidden_states is not None or not (f.use_cfattn or f.use_interattn):
+        if encoder_hidden_states is None and f.store:
+            f.stored.append(hidden_states.detach().clone())
+        if encoder_hidden_states is not None or not (f.use_cfattn or f.use_interattn or f.use_intraattn):
             return self.plain(attn, hidden_states, encoder_hidden_states, attention_mask, temb)
         assert attention_mask is None
         hw = hidden_states.shape[1]
         dt = hidden_states.dtype
         kw = {}
+        if f.use_intraattn:
+            ref = f.read()
+            if f.own_refs:
+                ref = hidden_states
+            assert ref.shape == hidden_states.shape, (tuple(ref.shape), tuple(hidden_states.shape))
+            kw.update(ref=ref.to(dt), intra_scale=f.intra_scale, intra_bias=f.intra_bias)
         if f.use_cfattn:
             kw.update(use_cf=True, cf_mask=f.cf_masks[hw])
         if f.use_interattn:
@@ -289,6 +348,7 @@ class UNet(_Model):
         self.conv_out = nn.Conv2d(320, 4, 3, padding=1)
         self.fresco = None
         self.taps = None          # a dict that receives TAPS
+        self.ups = None           # a list that receives every up block's input, before the hook (:773-774, :811-812)
         self.inputs = []          # every call's sample, as loop_model.UNet keeps them
         self.on_call = None
 
@@ -325,7 +385,9 @@ class UNet(_Model):
         for i, blk in enumerate(self.up_blocks):                           # :762-800
             n = len(blk.resnets)
             res, skips = skips[-n:], skips[:-n]
-            sample = self._hook(sample, q)                                 # :773-779
+            if self.ups is not None:
+                self.ups.append(sample)
+            sample = self._hook(sample, q, timestep)                       # :773-779
             kw = dict(encoder_hidden_states=encoder_hidden_states, cross_attention_kwargs=cross_attention_kwargs) \
                 if blk.has_cross_attention else {}
             sample = _call(blk, q, hidden_states=sample, temb=emb, res_hidden_states_tuple=res, **kw)
@@ -336,10 +398,11 @@ class UNet(_Model):
         sample = q(self.conv_out(sample))
         return types.SimpleNamespace(sample=sample) if return_dict else (sample,)
 
-    def _hook(self, sample, q):
-        """optimize_feature with iters = 0 (its AdaIN epilogue) and warp_tensor with the saliency, in the sample's dtype"""
+    def _hook(self, sample, q, timestep=None):
+        """optimize_feature with iters = 0 (its AdaIN epilogue) and warp_tensor with the saliency, in the sample's dtype; with
+        hook_steps only on those timesteps (`timestep in steps`, :775)"""
         f = self.fresco
-        if f is None or not f.hook:
+        if f is None or not f.hook or (f.hook_steps is not None and int(timestep) not in f.hook_steps):
             return sample
         from oracle import fresco_oracle as O
         sample = q(O.adain(q(sample), sample))
@@ -689,3 +752,239 @@ def fault_distance(models, fault, gold):
     r64, _, _ = models.loop(gold["loop_draws"], fault=fault)
     d = loop_distance(r64, {"steps": gold["loop_steps"], "final": gold["loop_final"]})
     return d, 4 * float(gold["loop_noise"][0]) * float(gold["loop_peak"][0])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the store pass, the spatial-guided call and the controller's sequence (tests/golden/unet_composed_seq_golden.npz)
+# ---------------------------------------------------------------------------------------------------------------------
+SEQ_GOLDEN_FILE = "unet_composed_seq_golden.npz"
+STORE_STEP = L.STEPS[-1]         # get_intraframe_paras runs at the scheduler's last timestep
+STORE_SEED, STALE_SEED = 79, 81  # of the store pass's inputs, and of the pass a store that was not cleared still holds
+STORED = 3                       # attn1 calls of up_blocks.2 / up_blocks.3 in this model
+END_OPT_STEP = 4                 # run_fresco.py: apply_FRESCO_opt(steps=timesteps[:end_opt_step]) -- 901 .. 451
+STEPS2 = L.STEPS[2:]             # the seq case: num_warmup_steps = 2 of loop_model's six steps
+SEQ_KW = dict(num_warmup_steps=2, seed=22, cond_scale=list(L.COND_SCALE), num_inference_steps=len(L.STEPS),
+              guidance_scale=L.GUIDANCE, num_intraattn_steps=1)
+# (use_intraattn, use_interattn, use_cfattn, index) at the UNet call of 601, 451, 301, 151: intra on the first step only,
+# temporal off once t < step_interattn_end = 350, cross-frame throughout, the index back at 0 each time
+SEQ_FLAGS = ((1, 1, 1, 0), (0, 1, 1, 0), (0, 0, 1, 0), (0, 0, 1, 0))
+FULL_FAULTS = ("rotated_refs", "no_intra", "uncleared_store", "own_refs")
+SEQ_FAULTS = ("intra_every_step", "temporal_never_off")
+GRAM_FAULTS = ("gram_unnormalised", "gram_transposed")
+
+
+def seq_golden(golden_dir):
+    return dict(np.load(os.path.join(golden_dir, SEQ_GOLDEN_FILE)))
+
+
+def thin_tokens(t):
+    """(n, h * w, C) tokens of a square plane, kept as R.thin keeps the (n, h, w, C) map"""
+    n, hw, C = t.shape
+    side = int(round(hw ** 0.5))
+    assert side * side == hw
+    return R.thin(t.reshape(n, side, side, C).double())
+
+
+def thin_gram(g):
+    """(B, hw, hw) kept as R.thin keeps a one-channel map: every s-th row and column plus the last ones"""
+    return R.thin(g.double()[..., None])
+
+
+def store_inputs(seed=STORE_SEED):
+    """(imgs (2, 3, 128, 128) in [-1, 1], the draw of prepare_latents (2, 4, 16, 16)) of the store pass, fp16 values.  The
+    images carry a level per frame and channel under the texture (an 8 x 8 mean of texture alone is next to nothing), so that
+    the latents are another set than call_inputs' and the loop's, and not noise alone"""
+    rs = np.random.RandomState(seed)
+    level = rs.uniform(-1.2, 1.2, (FRAMES, 3, 1, 1))
+    imgs = np.tanh(level + 0.6 * rs.standard_normal((FRAMES, 3, SIDE, SIDE)))
+    draw = rs.standard_normal((FRAMES, 4, LAT, LAT))
+    return torch.from_numpy(imgs).to(torch.float16), torch.from_numpy(draw).to(torch.float16)
+
+
+def store_latents(dtype, q=L.identity, seed=STORE_SEED):
+    """what get_intraframe_paras hands the UNet on `Pipe` (diffusion_hacked.py:863-877): the draw, loop_model.VAE's encoding of
+    the images times the scaling factor, add_noise at the last timestep, both CFG halves"""
+    imgs, draw = store_inputs(seed)
+    vae, sched = L.VAE(), L.Scheduler()
+    x0 = q(vae.config.scaling_factor * q(vae.encode(imgs.to(dtype)).latent_dist.sample()))
+    lat = q(sched.add_noise(x0, q(draw.to(dtype) * sched.init_noise_sigma), torch.tensor(STORE_STEP)))
+    return torch.cat([lat] * 2)
+
+
+def gram(feat, fault=None):
+    """oracle.gram_target of a (B, C, h, w) feature in float64; fault: a Gram a kernel at fault would give"""
+    from oracle import fresco_oracle as O
+    feat = feat.double()
+    if fault == "gram_transposed":         # the pixels enumerated column by column
+        feat = feat.transpose(2, 3)
+    if fault == "gram_unnormalised":
+        X = feat.reshape(feat.shape[0], feat.shape[1], -1).transpose(1, 2)
+        return X @ X.transpose(1, 2)
+    return O.gram_target(feat).double()
+
+
+def store_pass(unet, fresco, dtype, loop_q=L.identity, seed=STORE_SEED, clear=True, gram_fault=None):
+    """the pass get_intraframe_paras makes (diffusion_hacked.py:842-901) on `unet`, whose FRESCO sites read `fresco`: every
+    flag off, the hook collecting and optimising nothing, the store cleared (clear=False: the fault of a store that was not)
+    and storing; ONE UNet call without ControlNet residuals at STORE_STEP -> {"attn<i>": the i-th stored tensor thinned,
+    "gram<i>": gram_target of the i-th up block's input thinned}; the whole stored tensors stay in fresco.stored"""
+    fresco.disable_controller()
+    fresco.hook = False
+    if clear:
+        fresco.clear_store()
+    before = len(fresco.stored)
+    fresco.enable_store()
+    _, _, text, _ = call_inputs()
+    unet.ups = []
+    with torch.no_grad():
+        unet(store_latents(dtype, loop_q, seed), torch.tensor(STORE_STEP), encoder_hidden_states=text.to(dtype),
+             cross_attention_kwargs=None, return_dict=False)
+    ups, unet.ups = unet.ups, None
+    fresco.disable_store()
+    assert len(fresco.stored) == before + STORED and len(ups) == len(unet.up_blocks)
+    rec = {"attn%d" % i: thin_tokens(t) for i, t in enumerate(fresco.stored[before:])}
+    rec.update({"gram%d" % i: thin_gram(gram(u, gram_fault)) for i, u in enumerate(ups)})
+    return rec
+
+
+STORE_KEYS = tuple("attn%d" % i for i in range(STORED)) + tuple("gram%d" % i for i in range(4))
+
+
+def seq_record(unet, controlnet, fresco, dtype, randn, loop_q=L.identity, **overrides):
+    """four steps of loop_model.inference_model on the stand-ins with `fresco` as the working controller (its store filled
+    by store_pass), everything switched on as run_fresco.py does before inference(): enable_controller, the hook on
+    timesteps[:END_OPT_STEP] with iters = 0 -> {"steps": every UNet input's first half (4, 2, 4, 16, 16), "final": the
+    returned latents, "flags": Fresco.flags() at each UNet call (4, 4)}.  flows / occs / saliency are given, as run_fresco.py
+    gives them: with six steps no bg_smoothing_step is reached."""
+    pipe = Pipe("cpu", dtype, unet, controlnet)
+    pipe.frescoProc = types.SimpleNamespace(controller=fresco)
+    imgs, text, edges = loop_inputs("cpu", dtype)
+    fresco.enable_controller()
+    fresco.hook, fresco.hook_steps = True, set(L.STEPS[:END_OPT_STEP])
+    flags = []
+    keep, torch.randn, unet.on_call = torch.randn, randn, lambda: flags.append(fresco.flags())
+    try:
+        final = L.inference_model(pipe, pipe.controlnet, pipe.frescoProc, imgs, text, edges, pipe.scheduler.timesteps,
+                                  flows=fresco.flows, occs=fresco.occs, saliency=fresco.saliency, q=loop_q,
+                                  **dict(SEQ_KW, **overrides))
+    finally:
+        torch.randn, unet.on_call = keep, None
+    assert len(unet.inputs) == len(STEPS2)
+    return {"steps": torch.stack([s[:FRAMES] for s in unet.inputs]).double().numpy(), "final": final.double().numpy(),
+            "flags": np.array(flags)}
+
+
+class SeqModels:
+    """the store pass, `full` and `seq` on a Models' two pairs"""
+
+    def __init__(self, models):
+        self.m = models
+
+    def _sites(self, q=round16):
+        m = self.m
+        m.reset(q)
+        f64, f32 = make_fresco(torch.float64), make_fresco(torch.float32)
+        set_fresco(m.u64, f64)
+        set_fresco(m.u32, f32, q)
+        return f64, f32
+
+    def store(self, rounded=True, gram_fault=None):
+        """(float64 record, the rounded run's, the two Fresco objects with their stores filled and the sites installed)"""
+        f64, f32 = self._sites()
+        s64 = store_pass(self.m.u64, f64, torch.float64, gram_fault=gram_fault)
+        s16 = store_pass(self.m.u32, f32, torch.float32, L.round_half) if rounded else None
+        return s64, s16, f64, f32
+
+    def full(self, fault=None):
+        """(float64 record, the rounded run's) of `full`: the store pass, then call_inputs() through ControlNet + UNet with
+        intra, cross-frame and temporal attention on and the hook as in `fresco`.  fault (float64 pair only):
+          rotated_refs     the references one layer off: up_blocks.3's two, the only ones of one shape, change places
+                           (store[0], 64 x 640, has no peer: a rotation that reaches it cannot compute, the shapes differ)
+          no_intra         the spatial pass skipped
+          uncleared_store  six entries: the three of an earlier pass on other images are read, the index ends at 3
+          own_refs         the references are the call's own features"""
+        _, _, f64, f32 = self.store(rounded=fault is None)
+        m = self.m
+        if fault == "uncleared_store":
+            f64.clear_store()
+            store_pass(m.u64, f64, torch.float64, seed=STALE_SEED)
+            store_pass(m.u64, f64, torch.float64, clear=False)
+            assert len(f64.stored) == 2 * STORED
+        if fault == "rotated_refs":
+            f64.stored = [f64.stored[0], f64.stored[2], f64.stored[1]]
+        f64.own_refs = fault == "own_refs"
+        for f in (f64, f32):
+            f.enable_controller()
+            f.hook, f.hook_steps = True, None
+        if fault == "no_intra":
+            f64.disable_intraattn()
+        r64 = call_record(m.u64, m.c64, torch.float64)
+        r16 = call_record(m.u32, m.c32, torch.float32) if fault is None else None
+        if fault is None:
+            assert f64.flags() == (1, 1, 1, 0) and f32.flags() == (1, 1, 1, 0)
+        m.reset()
+        return r64, r16
+
+    def seq(self, draws=None, fault=None):
+        """(float64 record, the rounded run's, the draws) of `seq`.  fault: intra_every_step (num_intraattn_steps never
+        reached), temporal_never_off (step_interattn_end = 0)"""
+        _, _, f64, f32 = self.store(rounded=fault is None)
+        m = self.m
+        over = {"intra_every_step": dict(num_intraattn_steps=len(STEPS2) + 1), "temporal_never_off": dict(step_interattn_end=0),
+                None: {}}[fault]
+        if draws is None:
+            draws = []
+            r64 = seq_record(m.u64, m.c64, f64, torch.float64, recording_randn(draws), **over)
+        else:
+            r64 = seq_record(m.u64, m.c64, f64, torch.float64, L.replay_randn(list(draws), "cpu"), **over)
+        r16 = None
+        if fault is None:
+            r16 = seq_record(m.u32, m.c32, f32, torch.float32, L.replay_randn(list(draws), "cpu"), loop_q=L.round_half)
+            assert (r16["flags"] == r64["flags"]).all()
+        m.reset()
+        return r64, r16, draws
+
+
+def derive_seq(models, draws=None):
+    """every entry of the second golden file (draws: seq's recorded draws, or None to draw them)"""
+    sm = SeqModels(models)
+    out = {}
+    s64, s16, _, _ = sm.store()
+    models.reset()
+    noise, peak = noise_and_peak(s64, s16, STORE_KEYS)
+    for k in STORE_KEYS:
+        out["store_" + k] = s64[k]
+    out["store_noise"], out["store_peak"] = np.array(noise), np.array(peak)
+    r64, r16 = sm.full()
+    for k in CALL_KEYS:
+        out["full_" + k] = r64[k]
+    noise, peak = noise_and_peak(r64, r16, CALL_KEYS)
+    out["full_noise"], out["full_peak"] = np.array(noise), np.array(peak)
+    r64, r16, draws = sm.seq(draws)
+    out["seq_steps"], out["seq_final"], out["seq_draws"], out["seq_flags"] = r64["steps"], r64["final"], np.stack(draws), r64["flags"]
+    noise, peak = loop_noise_and_peak(r64, r16)
+    out["seq_noise"], out["seq_peak"] = np.array([noise]), np.array([peak])
+    return out
+
+
+def store_bars(gold):
+    """per STORE_KEYS entry 4 x noise x peak"""
+    return [4 * float(n) * float(p) for n, p in zip(gold["store_noise"], gold["store_peak"])]
+
+
+def seq_fault_distance(models, fault, gold):
+    """(distance of the float64 model with `fault` planted from its record, that record's bar): FULL_FAULTS on `full`'s noise
+    prediction, SEQ_FAULTS on `seq`'s step inputs and final latents, GRAM_FAULTS on the worst of the four Gram targets (in
+    its own bars: -> (the ratio, 1.0))"""
+    sm = SeqModels(models)
+    if fault in FULL_FAULTS:
+        r64, _ = sm.full(fault)
+        return distance(r64["out"], gold["full_out"]), 4 * float(gold["full_noise"][0]) * float(gold["full_peak"][0])
+    if fault in SEQ_FAULTS:
+        r64, _, _ = sm.seq(gold["seq_draws"], fault)
+        d = loop_distance(r64, {"steps": gold["seq_steps"], "final": gold["seq_final"]})
+        return d, 4 * float(gold["seq_noise"][0]) * float(gold["seq_peak"][0])
+    s64, _, _, _ = sm.store(rounded=False, gram_fault=fault)
+    models.reset()
+    bars = dict(zip(STORE_KEYS, store_bars(gold)))
+    return min(distance(s64[k], gold["store_" + k]) / bars[k] for k in STORE_KEYS if k.startswith("gram")), 1.0
